@@ -1,10 +1,23 @@
 #!/usr/bin/env python3
 """Headline benchmark: frames/s of the detecttrails hot path on N MI355X.
 
-    python bench.py --gpus 1 --steps 5 --warmup 1                      # BASELINE configs[2] (default) + secondary legs
+    python bench.py --gpus 1 --steps 5 --warmup 1                      # BASELINE configs[2] (default): the headline only
+    python bench.py --gpus 1 --steps 5 --warmup 1 --full               # ... + per-kernel table, stages and the secondary legs
     python bench.py --workload lsst                                     # BASELINE configs[4] as the headline of the run
+    python bench.py --dump-outputs bench_outputs                        # + the last timed step's records as bench_outputs/<field>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W           # what the driver's scaling step runs
+
+A plain run sets up, warms up, times --steps steps, writes --dump-outputs if given and prints the line: `value`,
+`ms_per_step`, `config` and the `roofline` of the dominant kernel (priced from the brackets inside the timed region).
+Everything else -- the per-kernel table and `stages` (one extra, fully bracketed step), `roofline.canny_hough` /
+`hough_votes`, the PCIe-inclusive `host_resident` leg, `one_call_in_flight`, `cpu_baseline` and the secondary legs
+listed below -- runs only with --full.
+
+--dump-outputs DIR: the records the timed path returned in its last timed step (lfd_amd._native.RESULT_DTYPE, one per
+frame; [scale, frame] for lsst), one DIR/<field>.npy per field: rho / theta as float32, the integer fields as float64
+(exact).  The frames are a pure function of the arguments (lfd_amd.synth: seeded per frame index), so two builds run
+with the same arguments can be compared file by file.  With several ranks, rank r > 0 writes into DIR/rank<r>/.
 
 workload sdss (BASELINE.json configs[2], the configuration the metric is quoted on): one "step" = one pass of the
 full pipe (remove_stars -> flip -> bright pass -> dim pass where the bright pass found nothing;
@@ -18,9 +31,9 @@ roofline: the library brackets launches with HIP events on the launch stream.  B
 step costs ~6 % of it, so inside the timed region only the few largest kernels are bracketed (nominated by the
 fully bracketed warm-up steps); the dominant one is priced with ITS share of SURVEY.md 8(d)'s algorithmic bytes
 (KERNEL_BYTES_PER_PX: every stage's bytes are charged exactly once across its kernels) x the frames its launches
-worked on.  `stages` and `canny_hough` come from one extra, fully bracketed step run after the timed region.
+worked on.  `stages` and `canny_hough` come from one extra, fully bracketed step run after the timed region (--full).
 
-Secondary fields of the default (N = 1, sdss) invocation -- never `value`:
+Secondary fields of the --full (N = 1, sdss) invocation -- never `value`:
   host_resident  the same step with the frames handed over as host buffers (PCIe-inclusive);
   sustained      the same device-resident step repeated for >= 3 s, GPU clock before / after;
   dropin         DetectTrails(run=...).process(batch=256) over a synthetic $BOSS tree of FITS files in /dev/shm (plain and
@@ -293,9 +306,9 @@ def stress_leg(args, env, headline):
     return out
 
 
-def measure(args, workload, n, steps, warmup, env, distinct=None, host_leg=True, sustained_s=0.0):
-    """One workload on this rank's GPU: generation, upload, warm-up, the timed region, the per-kernel table.  Returns
-    (out dict for rank 0 or None, state for the follow-up legs)."""
+def measure(args, workload, n, steps, warmup, env, distinct=None, host_leg=True, sustained_s=0.0, full=True):
+    """One workload on this rank's GPU: generation, upload, warm-up, the timed region; with `full`, the per-kernel table and
+    the measurements beside the headline.  Returns (out dict for rank 0 or None, state for the follow-up legs)."""
     import torch
     import torch.distributed as dist
     from lfd_amd import _native, synth
@@ -399,7 +412,7 @@ def measure(args, workload, n, steps, warmup, env, distinct=None, host_leg=True,
     elapsed = time.perf_counter() - t0
     timing = det.get_timing()
     one_call = None
-    if cif > 1:                                   # beside it: the same steps one synchronous call after the other
+    if cif > 1 and full:                          # beside it: the same steps one synchronous call after the other
         det.enable_timing(False)
         fence()
         t1 = time.perf_counter()
@@ -407,11 +420,13 @@ def measure(args, workload, n, steps, warmup, env, distinct=None, host_leg=True,
             step()
         fence()
         one_call = time.perf_counter() - t1
-    det.timing_select(None)
-    det.enable_timing(not args.no_kernel_timing)
-    step()                                        # untimed: the per-kernel table
-    torch.cuda.synchronize()
-    table = det.get_timing()
+    table = {}
+    if full:
+        det.timing_select(None)
+        det.enable_timing(not args.no_kernel_timing)
+        step()                                    # untimed: the per-kernel table
+        torch.cuda.synchronize()
+        table = det.get_timing()
     det.enable_timing(False)
     cnt = det.get_counters()[:n]  # last pass of every slot: Hough cost is 180 votes per non-zero pixel
     sustained = None
@@ -472,7 +487,7 @@ def measure(args, workload, n, steps, warmup, env, distinct=None, host_leg=True,
         finally:
             det2.close()
     host_res = None
-    if host_leg and host_ok and not args.host_frames and not args.no_host_leg:  # secondary: frames handed over as host buffers (PCIe-inclusive; never `value`)
+    if full and host_leg and host_ok and not args.host_frames and not args.no_host_leg:  # secondary: frames handed over as host buffers (PCIe-inclusive; never `value`)
         step_host()
         fence()
         t0 = time.perf_counter()
@@ -629,6 +644,11 @@ def measure(args, workload, n, steps, warmup, env, distinct=None, host_leg=True,
             "stages": stages,
             "kernels": kern,
         }
+        if not full:                              # (these come from the extra, fully bracketed step of a --full run)
+            for k in ("stages", "kernels"):
+                del out[k]
+            for k in ("canny_hough", "hough_votes"):
+                del out["roofline"][k]
         if host_res:
             out["host_resident"] = {"value": round(host_res[0], 2), "unit": "frames/s", "steps": host_res[1],
                                     "note": "same step with the frames handed over as host buffers (PCIe-inclusive); never `value`"}
@@ -803,6 +823,14 @@ def dropin_leg(state, args, dev_index):
     return out
 
 
+def dump_outputs(res, path):
+    """The records of the last timed step, one array per field: rho / theta as float32, the integer fields as float64."""
+    os.makedirs(path, exist_ok=True)
+    for name in res.dtype.names:
+        col = res[name]
+        np.save(os.path.join(path, name + ".npy"), col.astype(np.float32 if col.dtype.kind == "f" else np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -814,23 +842,30 @@ def main():
     ap.add_argument("--lanes", type=int, default=1, help="concurrent half-batches (streams) per GPU")
     ap.add_argument("--calls-in-flight", type=int, default=1,
                     help="BatchDetector(calls_in_flight=): contexts launching into one stream, a host thread each, step i + 1 queued while step i "
-                         "runs.  Default 1 (synchronous calls: HIP events bracket single kernels only then); the default run reports the rate with 2 "
+                         "runs.  Default 1 (synchronous calls: HIP events bracket single kernels only then); a --full run reports the rate with 2 "
                          "as the secondary `two_calls_in_flight`")
-    ap.add_argument("--cpu-sample", type=int, default=None, help="frames timed through the CPU oracle on one thread (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the per-kernel table and stages, the host-resident leg, the CPU baseline "
+                         "and, at N = 1 on sdss, the sustained / two-calls / dropin / stress / lsst legs (off: a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result records to DIR/<field>.npy (float32 / float64)")
+    ap.add_argument("--cpu-sample", type=int, default=None, help="--full: frames timed through the CPU oracle on one thread (0 = skip)")
     ap.add_argument("--gen-workers", type=int, default=-1)
     ap.add_argument("--no-removestars", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true",
                     help="developer: leave the per-launch HIP events off (no roofline entry) to see what they cost")
     ap.add_argument("--host-frames", action="store_true",
                     help="developer: time ONLY the host-resident (PCIe-inclusive) path as the headline value of this run")
-    ap.add_argument("--no-host-leg", action="store_true", help="skip the secondary PCIe-inclusive measurement")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the sustained / dropin / lsst legs of the default invocation (profiling runs)")
+    ap.add_argument("--no-host-leg", action="store_true", help="--full: skip the secondary PCIe-inclusive measurement")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the sustained / dropin / lsst legs (profiling runs)")
     ap.add_argument("--sustained-s", type=float, default=3.0)
     ap.add_argument("--dropin-bz2", type=int, default=64, help="distinct frames of the .bz2 sample of the dropin leg (0 = skip)")
     ap.add_argument("--dropin-bz2-frames", type=int, default=4096, help="fields of the .bz2 run (hard links to the distinct files)")
     ap.add_argument("--dropin-frames", type=int, default=4096, help="fields of the plain-FITS run of the dropin leg (hard links of the batch's frames)")
     ap.add_argument("--lsst-distinct", type=int, default=64, help="distinct frames of the secondary lsst leg (each used 256 / this times)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
@@ -867,15 +902,17 @@ def main():
     env = {"rank": rank, "world": world, "dev": dev, "dev_index": dev_index, "use_dist": use_dist, "red_dev": red_dev, "share": share}
 
     n = args.frames_per_gpu or 256
-    primary = world == 1 and args.workload == "sdss" and not args.host_frames and not args.no_secondary
+    primary = args.full and world == 1 and args.workload == "sdss" and not args.host_frames and not args.no_secondary
     out, state = measure(args, args.workload, n, args.steps, args.warmup, env,
-                         sustained_s=args.sustained_s if primary else 0.0)
+                         sustained_s=args.sustained_s if primary else 0.0, full=args.full)
+    if args.dump_outputs:
+        dump_outputs(state["res"], args.dump_outputs if rank == 0 else os.path.join(args.dump_outputs, "rank%d" % rank))
     if rank == 0:
         if ranks_seen:
             out["rccl_ranks_seen" if ranks_seen["backend"] == "nccl" else "ranks_seen"] = ranks_seen
-        if world > 1:
+        if args.full and world > 1:
             out["cpu_baseline"] = None  # (the host baseline is timed at N = 1 only: rank 0 would keep the other ranks waiting)
-        else:
+        elif args.full:
             out["cpu_baseline"] = cpu_baseline(state, args, world)
         if primary:
             try:

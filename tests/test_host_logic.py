@@ -224,6 +224,28 @@ def test_bench_finds_the_committed_traffic_counters():
             assert u and 0 < u["valu_pipe"] < 1 and 0 < u["waves_per_simd"] <= 8 and "hbm" in u, (workload, s_, u)
 
 
+def test_bench_dump_outputs_writes_every_record_field(tmp_path):
+    """bench.py --dump-outputs: one DIR/<field>.npy per field of the result records, float32 for rho / theta and float64 (exact)
+    for the integer fields, shape kept ([scale, frame] for lsst)."""
+    import importlib.util
+    from lfd_amd import _native
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    res = np.zeros((3, 5), _native.RESULT_DTYPE)
+    res["found"][1] = 2
+    res["rho"] = np.float32(-12.5)
+    res["theta"][2, 4] = np.float32(1.8325957)
+    res["x1"] = -(2 ** 31 - 1)
+    bench.dump_outputs(res, str(tmp_path / "out"))
+    assert sorted(os.listdir(tmp_path / "out")) == sorted(n + ".npy" for n in _native.RESULT_DTYPE.names)
+    for name in _native.RESULT_DTYPE.names:
+        a = np.load(tmp_path / "out" / (name + ".npy"))
+        assert a.shape == (3, 5) and a.dtype == (np.float32 if name in ("rho", "theta") else np.float64), name
+        assert np.array_equal(a, res[name]), name
+
+
 
 def test_resume_skips_frames_already_marked_done(tmp_path, monkeypatch):
     """process(resume=True) continues an interrupted run: the frames listed in <results>.progress are skipped, rows are not

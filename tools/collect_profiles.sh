@@ -10,11 +10,11 @@ R=${1:-r04}
 WHICH=${2:-both}
 O=gpurun_out/$R
 mkdir -p $O
-CMD="python3 bench.py --cpu-sample 0 --no-host-leg --no-secondary"
+CMD="python3 bench.py --full --cpu-sample 0 --no-host-leg --no-secondary"
 for w in sdss lsst; do
   if [ "$WHICH" != both ] && [ "$WHICH" != $w ]; then continue; fi
   WF=""; if [ $w = lsst ]; then WF="--workload lsst"; fi
-  if [ $w = sdss ]; then python3 bench.py > $O/bench_sdss.json 2> $O/bench_sdss.err; else python3 bench.py --workload lsst > $O/bench_lsst.json 2> $O/bench_lsst.err; fi
+  if [ $w = sdss ]; then python3 bench.py --full > $O/bench_sdss.json 2> $O/bench_sdss.err; else python3 bench.py --full --workload lsst > $O/bench_lsst.json 2> $O/bench_lsst.err; fi
   echo "bench $w done"
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$w -- $CMD $WF > $O/bench_${w}_under_rocprof.json 2> $O/kt_$w.err
   rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch_$w -- $CMD $WF --steps 2 > /dev/null 2> $O/pmc_fetch_$w.err

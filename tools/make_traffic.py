@@ -1,7 +1,7 @@
 """Build profiles/rNN_traffic*.json from the two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE) of a bench.py command.
 
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_fetch -- python3 bench.py --cpu-sample 0 --steps 2 --no-host-leg
-    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc_write -- python3 bench.py --cpu-sample 0 --steps 2 --no-host-leg
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d /tmp/pmc_fetch -- python3 bench.py --full --cpu-sample 0 --steps 2 --no-host-leg
+    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d /tmp/pmc_write -- python3 bench.py --full --cpu-sample 0 --steps 2 --no-host-leg
     python tools/make_traffic.py <fetch counter_collection.csv> <write counter_collection.csv> <out.json> [sdss|lsst] [frames_per_gpu]
 
 (the two counters do not fit one pass: MI355X_MICROARCH.md, rocprofv3 PMC slots; separate passes with --kernel-trace only.)
@@ -13,7 +13,7 @@ import sys
 
 ABOUT = (
     "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in two separate passes (with --kernel-trace only) of "
-    "`python3 bench.py --cpu-sample 0 --steps 2 --no-host-leg%s` on one MI355X.  Counters are in KB per dispatch, averaged over each "
+    "`python3 bench.py --full --cpu-sample 0 --steps 2 --no-host-leg%s` on one MI355X.  Counters are in KB per dispatch, averaged over each "
     "kernel's dispatches (bright- and dim-pass launches mixed).  Corrections per MI355X_MICROARCH.md (HBM section): FETCH_SIZE "
     "tallies the 128-B requests of a wide (16 B/lane) coalesced row stream as 64 B, so it is doubled for the kernels that stream "
     "whole float rows that way: k_prep_hist and k_prep_erode (fetch_factor 2; check: 2 x FETCH ~ the float32 input bytes, halo rows "

@@ -8,7 +8,7 @@ WL=${2:-sdss}          # sdss | lsst
 MARK=${3:-k_rs_boxes}  # the kernel a step begins with, or `gap` (after the GPU idled > 60 us)
 O=gpurun_out/${T}_tl
 mkdir -p $O
-rocprofv3 --kernel-trace --output-format csv -d $O -- python3 bench.py --workload $WL --cpu-sample 0 --no-host-leg --no-secondary --steps 3 --warmup 2 --no-kernel-timing > $O/bench.json 2> $O/err.txt
+rocprofv3 --kernel-trace --output-format csv -d $O -- python3 bench.py --full --workload $WL --cpu-sample 0 --no-host-leg --no-secondary --steps 3 --warmup 2 --no-kernel-timing > $O/bench.json 2> $O/err.txt
 python3 - "$O" "$MARK" "$WL" > gpurun_out/${T}_step_timeline.txt <<'PY'
 import csv, glob, sys
 rows = []
@@ -30,7 +30,7 @@ if len(starts) < 2:
 a, b = starts[-2], starts[-1]
 t0 = rows[a][0]
 queues = {}
-print("One 256-frame step of `bench.py --workload " + "%s" % sys.argv[3] + "` (the last but one of the run) under rocprofv3 --kernel-trace: start / end / duration in us from the step's")
+print("One 256-frame step of `bench.py --full --workload " + "%s" % sys.argv[3] + "` (the last but one of the run) under rocprofv3 --kernel-trace: start / end / duration in us from the step's")
 print("first kernel, hardware queue (q0 = the launch stream in order of first use), kernel, grid (threads).  The next step's first kernel follows.")
 print()
 for r in rows[a:b + 1]:
