@@ -16,7 +16,9 @@
  *   - a frame must fit the ctx in BOTH dimensions (h <= max_h and w <= max_w), not only in area.
  *   - a ctx is bound to one device, is not thread-safe, and runs everything on one HIP
  *     stream (its own, or the caller's via lfdmi_set_stream).  Calls return after the
- *     stream has drained (synchronous at the ABI).
+ *     stream has drained (synchronous at the ABI) -- except the `_begin` twins of
+ *     lfdmi_detect_batch_raw and lfdmi_process_multiscale, which enqueue a call and return;
+ *     lfdmi_end_oldest finishes it (see "calls in flight" below).
  *   - the library never retains or frees caller pointers.
  */
 #ifndef LFDMI_H
@@ -250,6 +252,46 @@ int lfdmi_detect_batch_raw(lfdmi_ctx *ctx, void *frames, int dtype, int n, int h
                            const lfdmi_catalog *cat, const lfdmi_rs_params *rs,
                            const lfdmi_params *bright, const lfdmi_params *dim, lfdmi_result *results,
                            int loc);
+/* ---- calls in flight ------------------------------------------------------------------------------------------------------
+ * A synchronous call ends with a host round trip, during which the GPU idles.  lfdmi_detect_batch_begin /
+ * lfdmi_process_multiscale_begin validate everything, enqueue every chunk of the call on the context's stream and return
+ * without waiting on the GPU; up to LFDMI_MAX_CALLS_IN_FLIGHT calls share the context's one workspace (only the page-locked
+ * areas their records are copied into are per call), and the next call's first kernel follows the previous call's last one.
+ *   Ordering     calls complete in FIFO order; lfdmi_end_oldest waits for the oldest, finishes it (records written, host frames
+ *                blotted) and returns its status.
+ *   Equivalence  begin + lfdmi_end_oldest gives byte-identical records to the synchronous call on the same inputs and leaves
+ *                the caller's frames as it does: LFDMI_F32 frames blotted by remove_stars, big-endian host frames untouched,
+ *                big-endian device frames swapped in place (by begin).
+ *   Lifetimes    params (structuring elements included), rs and rhos are copied by begin.  Frames, catalogue arrays and
+ *                results must stay valid and untouched until the matching lfdmi_end_oldest returns.
+ *   Frames       of two calls in flight must not overlap (LFDMI_ERR_ARG; two multi-scale passes, which only read, may share).
+ *   loc          LFDMI_DEVICE, or LFDMI_HOST_PINNED (memory from lfdmi_host_alloc; detect only).  LFDMI_HOST: LFDMI_ERR_ARG
+ *                (the runtime stages a pageable copy synchronously, so nothing would be left to overlap).
+ *   Refused      with LFDMI_ERR_ARG, the calls in flight unaffected: a begin beyond LFDMI_MAX_CALLS_IN_FLIGHT; a begin while
+ *                lfdmi_enable_timing is on; every other entry point that uses the workspace (lfdmi_detect_batch*,
+ *                lfdmi_process_*, the operators, lfdmi_get_stage, lfdmi_get_counters, lfdmi_set_stream, lfdmi_enable_timing(1))
+ *                while a call is in flight; lfdmi_end_oldest with nothing in flight.
+ *   Errors       an error from begin (including one after some chunks were enqueued: lfdmi_debug_fail_chunk applies to
+ *                lfdmi_detect_batch_begin too) or from lfdmi_end_oldest leaves the context usable: the failed call's work is
+ *                drained and discarded.
+ *   Destroy      lfdmi_ctx_destroy drains the calls in flight and frees everything (their results are not written).
+ * What a synchronous call decides on the host between chunks (table growth, a rerun with the general run kernels or after the
+ * run scan gave up, the worst-case spills) is decided at the end; a chunk that has to run again does so then, on a drained
+ * stream.  The threaded feed of pageable host frames stays synchronous-only.  Callers detect the feature by these symbols
+ * (LFDMI_VERSION is unchanged). */
+#define LFDMI_MAX_CALLS_IN_FLIGHT 2
+/* the non-blocking twin of lfdmi_detect_batch_raw: same arguments, same records, same side effects on the frames */
+int lfdmi_detect_batch_begin(lfdmi_ctx *ctx, void *frames, int dtype, int n, int h, int w, const lfdmi_catalog *cat,
+                             const lfdmi_rs_params *rs, const lfdmi_params *bright, const lfdmi_params *dim,
+                             lfdmi_result *results, int loc);
+/* the non-blocking twin of lfdmi_process_multiscale (LFDMI_DEVICE images only) */
+int lfdmi_process_multiscale_begin(lfdmi_ctx *ctx, const void *img, int dtype, int n, int h, int w, int flip, int dim,
+                                   int after_bright, const lfdmi_params *p, int n_scales, const double *rhos,
+                                   lfdmi_result *results, int loc);
+/* waits for the oldest call in flight, finishes it (results written, host frames blotted), returns its status */
+int lfdmi_end_oldest(lfdmi_ctx *ctx);
+/* calls begun and not yet ended (0 .. LFDMI_MAX_CALLS_IN_FLIGHT) */
+int lfdmi_calls_in_flight(lfdmi_ctx *ctx);
 /* page-locked host memory for LFDMI_HOST_PINNED frames, placed on the NUMA node next to ctx's GPU (the allocating thread
  * is bound to the GPU's local CPUs; LFDMI_NUMA_PIN=0 in the environment disables the binding).  Free with lfdmi_host_free
  * (any live ctx of the same device, or NULL). */

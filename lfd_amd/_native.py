@@ -18,6 +18,7 @@ U8, F32, F64, F32_BE = 0, 1, 2, 3
 PREP_NONE, PREP_BRIGHT, PREP_DIM, PREP_BRIGHT_THEN_DIM = 0, 1, 2, 3
 STAGE_GRAY, STAGE_EQU, STAGE_CANNY, STAGE_BOX, STAGE_ERODED, STAGE_EQUALIZED = 0, 1, 2, 3, 4, 5
 MAX_SCALES = 4
+MAX_CALLS_IN_FLIGHT = 2
 MAX_SET_LINES = 64
 MAX_MORPH_K = 31
 
@@ -33,6 +34,7 @@ SYMBOLS = (
     "lfdmi_hough_dims", "lfdmi_remove_stars", "lfdmi_process_bright", "lfdmi_process_dim",
     "lfdmi_detect_batch", "lfdmi_detect_batch_raw", "lfdmi_host_alloc", "lfdmi_host_free", "lfdmi_fits_read_frames", "lfdmi_fits_read_photoobj", "lfdmi_bz2_find_blocks", "lfdmi_bz2_create", "lfdmi_bz2_destroy", "lfdmi_bz2_last_error", "lfdmi_bz2_decode_batch", "lfdmi_bz2_fetch", "lfdmi_bz2_fetch_many", "lfdmi_bz2_frames", "lfdmi_bz2_reserve", "lfdmi_bz2_timings", "lfdmi_set_stage_images", "lfdmi_get_stage", "lfdmi_get_counters", "lfdmi_enable_timing", "lfdmi_timing_select", "lfdmi_get_timing",
     "lfdmi_timing_slots", "lfdmi_timing_name",
+    "lfdmi_detect_batch_begin", "lfdmi_process_multiscale_begin", "lfdmi_end_oldest", "lfdmi_calls_in_flight",
 )
 
 
@@ -312,6 +314,29 @@ class Bz2Decoder:
         return dict(zip(("upload+magics", "huffman+mtf", "sort", "walk", "rle+crc+out"), (float(x) for x in ms)))
 
 
+class Pending:
+    """A call in flight on a ``Context`` (``detect_batch_begin`` / ``process_multiscale_begin``).  It holds every object the
+    library reads until the call ends (ctypes structs, params, catalogue arrays, converted frames, rhos) and the result array
+    the records land in.  ``result()`` ends the context's calls in FIFO order up to and including this one."""
+
+    def __init__(self, ctx, res, keep, squeeze=False):
+        self._ctx, self._res, self._keep, self._squeeze = ctx, res, keep, squeeze
+        self._done, self._err = False, None
+
+    def done(self):
+        return self._done
+
+    def _finish(self, err):
+        self._done, self._err, self._keep = True, err, None
+
+    def result(self):
+        while not self._done:
+            self._ctx._end_oldest()
+        if self._err is not None:
+            raise self._err
+        return self._res[:, 0] if self._squeeze else self._res
+
+
 class Context:
     """One GPU, one HIP stream, workspace for ``max_inflight`` frames of up to max_h x max_w."""
 
@@ -339,10 +364,13 @@ class Context:
                 self._lib.lfdmi_ctx_destroy(h)
             raise NativeError(rc, msg)
         self.device, self.max_h, self.max_w, self.max_inflight = device, max_h, max_w, max_inflight
+        self._inflight = []                                  # Pending calls, oldest first
 
     def close(self):
         h = getattr(self, "_h", None)
         if h:
+            while getattr(self, "_inflight", None):          # (calls in flight end first: their results stay readable)
+                self._end_oldest()
             self._h = None
             self._lib.lfdmi_ctx_destroy(h)
 
@@ -664,6 +692,63 @@ class Context:
                                                    C.byref(rs) if rs is not None else None,
                                                    C.byref(pb), C.byref(pd), _ptr(res), loc))
         return res
+
+    # -- calls in flight (lfdmi_detect_batch_begin / lfdmi_process_multiscale_begin / lfdmi_end_oldest) ---------------------------
+    def calls_in_flight(self):
+        return int(self._lib.lfdmi_calls_in_flight(self._h))
+
+    def _end_oldest(self):
+        pend = self._inflight.pop(0)
+        rc = self._lib.lfdmi_end_oldest(self._h)
+        pend._finish(NativeError(rc, self._lib.lfdmi_last_error(self._h).decode()) if rc else None)
+
+    def _begin(self, fn, args, res, keep, squeeze=False):
+        self._chk(fn(self._h, *args))
+        pend = Pending(self, res, keep, squeeze)
+        self._inflight.append(pend)
+        return pend
+
+    def detect_batch_begin(self, frames, params_bright, params_dim, cat=None, rs=None, pinned=False):
+        """``detect_batch`` without waiting: returns a ``Pending`` whose ``result()`` is what ``detect_batch`` returns.  Frames
+        are device-resident (torch CUDA tensor, ``DeviceFrames``) or, with ``pinned=True``, in ``PinnedBuffer`` memory; they and
+        the catalogue must stay untouched until the call has ended (LFDMI_MAX_CALLS_IN_FLIGHT = 2 calls at a time)."""
+        if isinstance(frames, DeviceFrames):
+            n, h, w = frames.shape
+            code = F32_BE
+        elif not _is_dev(frames) and isinstance(frames, np.ndarray) and frames.dtype == np.dtype(">f4"):
+            if not frames.flags.c_contiguous:
+                raise ValueError("big-endian frames must be C-contiguous")
+            shp = frames.shape
+            n, h, w = (1, *shp) if len(shp) == 2 else shp
+            code = F32_BE
+        else:
+            if not _is_dev(frames) and not (isinstance(frames, np.ndarray) and frames.flags.c_contiguous):
+                raise ValueError("frames of a call in flight must be C-contiguous (they are used, and blotted, in place)")
+            frames, n, h, w, sq = self._batch(frames)
+            code = _dtype_code(frames)
+            if code != F32:
+                raise TypeError("detect_batch_begin needs float32 frames")
+        if pinned and _is_dev(frames):
+            raise ValueError("pinned=True is for host arrays")
+        pb, k1 = make_params(params_bright)
+        pd, k2 = make_params(params_dim, dim=True)
+        c, k3 = self._catalog(cat)
+        res = np.zeros(n, RESULT_DTYPE)
+        loc = DEVICE if _is_dev(frames) else (HOST_PINNED if pinned else HOST)
+        args = (_ptr(frames), code, n, h, w, C.byref(c) if c is not None else None, C.byref(rs) if rs is not None else None,
+                C.byref(pb), C.byref(pd), _ptr(res), loc)
+        return self._begin(self._lib.lfdmi_detect_batch_begin, args, res, [frames, pb, pd, c, rs, k1, k2, k3, cat, args])
+
+    def process_multiscale_begin(self, img, params, rhos, dim=True, flip=False, after_bright=False):
+        """``process_multiscale`` without waiting (device-resident images): a ``Pending`` whose ``result()`` is its array."""
+        img, n, h, w, sq = self._batch(img)
+        if not _is_dev(img):
+            raise ValueError("process_multiscale_begin needs device-resident images")
+        p, keep = make_params(params, dim=dim)
+        rh = (C.c_double * len(rhos))(*[float(r) for r in rhos])
+        res = np.zeros((len(rhos), n), RESULT_DTYPE)
+        args = (_ptr(img), _dtype_code(img), n, h, w, int(flip), int(dim), int(after_bright), C.byref(p), len(rhos), rh, _ptr(res), DEVICE)
+        return self._begin(self._lib.lfdmi_process_multiscale_begin, args, res, [img, p, keep, rh, args], squeeze=sq)
 
     def pinned_buffer(self, nbytes):
         """Page-locked host memory next to this context's GPU (lfdmi_host_alloc) as a ``PinnedBuffer``."""

@@ -141,6 +141,28 @@ class BatchDetector:
     def multiscale_async(self, frames, params, rhos, dim=True, flip=True, after_bright=False):
         return self._in_turn("process_multiscale", (frames, params, rhos, dim, flip, after_bright))
 
+    # ---- calls in flight on one workspace ------------------------------------------------------------------------------------
+    # ``submit`` / ``submit_multiscale`` enqueue a call on the detector's single context (lfdmi_detect_batch_begin /
+    # lfdmi_process_multiscale_begin) and return its ``Pending``: the next call is queued behind the current one on the same
+    # stream, in the same workspace, with no host thread and no second context (half the device memory of ``detect_async``).
+    # Two calls are in flight at most; a third submit first ends the oldest (its records wait in its ``Pending``).
+    def _submit_ctx(self):
+        if self.lanes != 1 or self.calls_in_flight != 1:
+            raise RuntimeError("submit needs BatchDetector(lanes=1, calls_in_flight=1): one context that takes the calls in flight")
+        ctx = self.ctx
+        while ctx.calls_in_flight() >= _native.MAX_CALLS_IN_FLIGHT:
+            ctx._end_oldest()
+        return ctx
+
+    def submit(self, frames, params_bright, params_dim, catalogs=None, rs=None, pinned=False):
+        """``detect`` without waiting: returns a ``Pending`` (``.result()`` = ``detect``'s records).  Frames are device-resident
+        (or ``PinnedBuffer`` memory with ``pinned=True``) and, with the catalogue, must stay untouched until the call has ended."""
+        return self._submit_ctx().detect_batch_begin(frames, params_bright, params_dim, catalogs, rs, pinned=pinned)
+
+    def submit_multiscale(self, frames, params, rhos, dim=True, flip=True, after_bright=False):
+        """``multiscale`` without waiting (device-resident frames): a ``Pending`` whose ``.result()`` is its records."""
+        return self._submit_ctx().process_multiscale_begin(frames, params, rhos, dim=dim, flip=flip, after_bright=after_bright)
+
     def enable_timing(self, on=True):
         for c in self.ctxs:
             c.enable_timing(on)

@@ -49,6 +49,40 @@ static const char *const KID_NAMES[TG_COUNT] = {
 
 struct TimedSpan { hipEvent_t a, b; int group, pass, det; };
 
+// A call in flight (lfdmi_detect_batch_begin / lfdmi_process_multiscale_begin): its arguments, copied where the header says
+// they are copied, what each chunk was enqueued with, and a page-locked area the chunks' flags, records and (host frames)
+// remove_stars squares are copied into in stream order.  lfdmi_end_oldest finishes it.
+struct CallChunk {
+    int c0, nc;
+    bool general_on, scan_fused;       // what the chunk's passes ran with (the finish decides on a rerun from these)
+    long long growths;                 // n_cap_growths when it was enqueued: tables enlarged since then hold what it overflowed
+};
+struct PendingCall {
+    int kind = 0;                      // 0: lfdmi_detect_batch_begin, 1: lfdmi_process_multiscale_begin
+    int status = 0;                    // finished inside begin (the worst-case workspace took the call): its return value
+    bool finished = false;
+    void *frames = nullptr;            // frames / image as the caller passed them
+    size_t frame_bytes = 0;            // bytes of the whole batch (overlap check)
+    int dtype = 0, n = 0, h = 0, w = 0, loc = 0;
+    bool be = false, host_blot = false;
+    lfdmi_catalog cat{};
+    bool has_cat = false, has_rs = false;
+    lfdmi_rs_params rs{};
+    lfdmi_params p1{}, p2{};           // bright + dim (detect) / the pass (multiscale); kernels point into `kern`
+    std::vector<uint8_t> kern;
+    int flip = 0, dim = 0, prep_mode = 0, n_scales = 1;
+    double rhos[LFDMI_MAX_SCALES] = {0};
+    lfdmi_result *results = nullptr;
+    std::vector<CallChunk> chunks;
+    // reused across calls of this slot
+    void *pin = nullptr;               // page-locked: n flags | n_scales * n records | n * max_obj squares
+    size_t pin_bytes = 0;
+    int *flags_h = nullptr;
+    lfdmi_result *rec_h = nullptr;
+    int4 *boxes_h = nullptr;
+    hipEvent_t done = nullptr;         // recorded behind the call's last copy
+};
+
 struct lfdmi_ctx {
     int device = 0, H = 0, W = 0, G = 0, wq = 0;
     size_t N = 0;
@@ -219,6 +253,12 @@ struct lfdmi_ctx {
     int cur_pass = 0;                  // 0 = bright / stand-alone operator, 1 = dim pass of detect_batch
     int *pass_flags = nullptr;         // per slot: bit0 bright detection, bit1 dim pass ran, bit2 dim detection
     std::vector<void *> allocs;
+    // calls in flight (FIFO ring of LFDMI_MAX_CALLS_IN_FLIGHT) and what the second one's uploads wait for
+    PendingCall calls[LFDMI_MAX_CALLS_IN_FLIGHT];
+    int call_first = 0, n_calls = 0;
+    int internal = 0;                  // > 0: the library itself is running a call (begin / end): the in-flight refusal is off
+    hipEvent_t feed_free[2] = {nullptr, nullptr}; // recorded behind the last kernel that read feed_dev[i] (calls in flight)
+    bool feed_free_set[2] = {false, false};
 };
 
 static int fail(lfdmi_ctx *c, int code, const std::string &msg) {
@@ -243,6 +283,14 @@ static int fail(lfdmi_ctx *c, int code, const std::string &msg) {
         int rc_ = (expr);           \
         if (rc_) return rc_;        \
     } while (0)
+
+// every entry point that uses the workspace refuses while calls are in flight (they are queued on it)
+static int idle(lfdmi_ctx *ctx) {
+    if (!ctx) return LFDMI_ERR_ARG;
+    if (ctx->n_calls && !ctx->internal) return fail(ctx, LFDMI_ERR_ARG, "calls in flight on this context: lfdmi_end_oldest them first");
+    return 0;
+}
+struct Internal { lfdmi_ctx *c; explicit Internal(lfdmi_ctx *ctx) : c(ctx) { c->internal++; } ~Internal() { c->internal--; } };
 
 struct Span {
     lfdmi_ctx *c;
@@ -517,16 +565,19 @@ extern "C" int lfdmi_get_stats(lfdmi_ctx *ctx, int64_t *out, int n) {
 // goes back to three launches per scan and the chunk is run again -- cheaper than the worst-case rerun of every flagged frame.
 // The one-launch scan is tried again after scan_rearm quiet chunks (doubling with every give-up: a GPU that stays shared
 // settles on the three launches, one that was shared for a moment gets its fast scan back).
-static bool scan_gave_up(lfdmi_ctx *ctx, const int *flags, int nc) {
+// (ran_fused: the chunk ran with the one-launch scan -- a call in flight is finished after later chunks were enqueued)
+static bool scan_gave_up(lfdmi_ctx *ctx, const int *flags, int nc, bool ran_fused) {
     bool gave = false;
     for (int i = 0; i < nc; i++) gave = gave || (flags[i] & PASS_FLAG_SCAN_GAVEUP);
-    if (!gave || !ctx->scan_fused) return false;
+    if (!gave || !ran_fused) return false;
+    if (!ctx->scan_fused) return true; // (already switched off by an earlier chunk's give-up)
     ctx->scan_fused = false;
     ctx->n_scan_giveups++;
     ctx->scan_quiet = 0;
     ctx->scan_rearm = std::min(ctx->scan_rearm * 2, 1 << 16);
     return true;
 }
+static bool scan_gave_up(lfdmi_ctx *ctx, const int *flags, int nc) { return scan_gave_up(ctx, flags, nc, ctx->scan_fused); }
 static void chunk_done(lfdmi_ctx *ctx) {
     ctx->n_chunks++;
     if (!ctx->scan_fused && ctx->scan_fused_cfg && ++ctx->scan_quiet >= ctx->scan_rearm) { ctx->scan_fused = true; ctx->scan_quiet = 0; }
@@ -644,6 +695,13 @@ extern "C" void lfdmi_ctx_destroy(lfdmi_ctx *ctx) {
     if (ctx->spill) lfdmi_ctx_destroy(ctx->spill);
     hipSetDevice(ctx->device);
     if (ctx->stream) hipStreamSynchronize(ctx->stream);
+    ctx->n_calls = 0; // (calls in flight: their work has drained with the stream, their results are dropped)
+    for (auto &pc : ctx->calls) {
+        if (pc.pin) hipHostFree(pc.pin);
+        if (pc.done) hipEventDestroy(pc.done);
+    }
+    for (int i = 0; i < 2; i++)
+        if (ctx->feed_free[i]) hipEventDestroy(ctx->feed_free[i]);
     for (void *p : ctx->allocs) hipFree(p);
     if (ctx->stage) hipFree(ctx->stage);
     for (int i = 0; i < 2; i++) {
@@ -675,7 +733,7 @@ extern "C" const char *lfdmi_last_error(lfdmi_ctx *ctx) { return ctx ? ctx->err.
 extern "C" int lfdmi_max_inflight(lfdmi_ctx *ctx) { return ctx ? ctx->G : 0; }
 
 extern "C" int lfdmi_set_stream(lfdmi_ctx *ctx, void *hip_stream) {
-    if (!ctx) return LFDMI_ERR_ARG;
+    RET(idle(ctx));
     HIPCHK(hipSetDevice(ctx->device));
     if (ctx->own_stream && ctx->stream) { hipStreamSynchronize(ctx->stream); hipStreamDestroy(ctx->stream); }
     if (hip_stream) { ctx->stream = (hipStream_t)hip_stream; ctx->own_stream = false; }
@@ -685,6 +743,7 @@ extern "C" int lfdmi_set_stream(lfdmi_ctx *ctx, void *hip_stream) {
 
 extern "C" int lfdmi_enable_timing(lfdmi_ctx *ctx, int on) {
     if (!ctx) return LFDMI_ERR_ARG;
+    if (on) RET(idle(ctx)); // (calls in flight are not timed)
     ctx->timing = on != 0;
     memset(ctx->t_ms, 0, sizeof ctx->t_ms);
     memset(ctx->t_n, 0, sizeof ctx->t_n);
@@ -711,7 +770,7 @@ extern "C" const char *lfdmi_timing_name(int i) { return (i >= 0 && i < TG_COUNT
 
 // ---- helpers ------------------------------------------------------------------------------
 static int check_shape(lfdmi_ctx *ctx, int n, int h, int w) {
-    if (!ctx) return LFDMI_ERR_ARG;
+    RET(idle(ctx));
     if (n < 0 || h <= 0 || w <= 0) return fail(ctx, LFDMI_ERR_ARG, "bad shape");
     // both sides, not only the area: the band / tile tables (cellbm, candmask, fullbits, tile_list) are sized by max_h and
     // max_w separately, so a taller-but-narrower frame of the same area would index past them
@@ -1918,7 +1977,7 @@ static int run_removestars(lfdmi_ctx *ctx, float *frames_dev, int f0, int nc, in
 // zero-filled in the caller's array by host threads, while the GPU runs the rest of the pipe -- the blotted
 // frames are not copied back (24.4 MB over PCIe per frame instead of 12.2 MB halves the host-fed rate)
 static void bind_thread(const std::vector<int> &cpus);
-static void blot_host_frames(float *frames, int nc, int h, int w, const lfdmi_catalog *cat, int f0, const std::vector<int4> &boxes,
+static void blot_host_frames(float *frames, int nc, int h, int w, const lfdmi_catalog *cat, int f0, const int4 *boxes,
                              const std::vector<int> &cpus) {
     size_t N = (size_t)h * w;
     auto work = [&](int a, int b) {
@@ -1960,31 +2019,96 @@ extern "C" int lfdmi_remove_stars(lfdmi_ctx *ctx, float *img, int n, int h, int 
 // Whole-pass entry points launch the general run kernels only once the context has met a frame the per-frame
 // LDS kernels could not take; a chunk that meets the first such frame is run again with them.
 #define GENERAL_QUIET_CHUNKS 8
+static bool general_again(lfdmi_ctx *c, bool on, const int *flags, int n);
 struct GeneralGuard {
     lfdmi_ctx *c;
     explicit GeneralGuard(lfdmi_ctx *ctx) : c(ctx) { c->general_on = !c->frame_ccl || c->general_seen; }
     ~GeneralGuard() { c->general_on = true; }
-    bool again(const int *flags, int n) {
-        bool need = false;
-        for (int i = 0; i < n; i++) need = need || (flags[i] & PASS_FLAG_GENERAL);
-        if (c->general_on) {
-            c->n_general_chunks++;
-            // the ~22 extra launches per pass are dropped again once GENERAL_QUIET_CHUNKS chunks in a row did without them
-            if (need) c->quiet_chunks = 0;
-            else if (c->frame_ccl && ++c->quiet_chunks >= GENERAL_QUIET_CHUNKS) { c->general_seen = false; c->quiet_chunks = 0; }
-            return false;
-        }
-        if (!need) return false;
-        c->general_seen = true;
-        c->general_on = true;
-        c->quiet_chunks = 0;
-        c->n_general_reruns++;
-        return true;
-    }
+    bool again(const int *flags, int n) { return general_again(c, c->general_on, flags, n); }
 };
+// on: the chunk ran with the general run kernels; true: run it again with them
+static bool general_again(lfdmi_ctx *c, bool on, const int *flags, int n) {
+    bool need = false;
+    for (int i = 0; i < n; i++) need = need || (flags[i] & PASS_FLAG_GENERAL);
+    if (on) {
+        c->n_general_chunks++;
+        // the ~22 extra launches per pass are dropped again once GENERAL_QUIET_CHUNKS chunks in a row did without them
+        if (need) c->quiet_chunks = 0;
+        else if (c->frame_ccl && ++c->quiet_chunks >= GENERAL_QUIET_CHUNKS) { c->general_seen = false; c->quiet_chunks = 0; }
+        return false;
+    }
+    if (!need) return false;
+    c->general_seen = true;
+    c->general_on = true;
+    c->quiet_chunks = 0;
+    c->n_general_reruns++;
+    return true;
+}
 
 // results[s * rstride + i]: frame i at Hough scale s (rhos == nullptr: one scale, p->houghMethod)
 struct KeepEqu { lfdmi_ctx *c; bool old; KeepEqu(lfdmi_ctx *c_, bool v) : c(c_), old(c_->keep_equ) { c->keep_equ = v; } ~KeepEqu() { c->keep_equ = old; } };
+
+// one chunk of a pass, enqueued: its records (rec_h[s * hstride + i]), flags and (hl != nullptr) line sets are copied to the
+// host in stream order
+static int enqueue_pass_chunk(lfdmi_ctx *ctx, const void *d, int dtype, int nc, int h, int w, int flip, int prep_mode, bool dim,
+                              const lfdmi_params *p, int n_scales, const double *rhos, lfdmi_result *rec_h, size_t hstride, int *flags_h,
+                              float *hl) {
+    const size_t G = (size_t)ctx->G;
+    for (int s = 0; s < n_scales; s++) {
+        k_init_results<<<(nc + 63) / 64, 64, 0, ctx->stream>>>(ctx->res_dev + s * G, ctx->pass_flags, nc);
+        KCHK("k_init_results");
+    }
+    RET(run_front(ctx, d, dtype, nc, h, w, flip, prep_mode, dim, p, nullptr));
+    for (int s = 0; s < n_scales; s++) {
+        RET(run_tail(ctx, nc, h, w, rhos[s], dim, p, nullptr, nullptr, ctx->res_dev + s * G, s > 0));
+        HIPCHK(hipMemcpyAsync(rec_h + s * hstride, ctx->res_dev + s * G, (size_t)nc * sizeof(lfdmi_result), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (hl) HIPCHK(hipMemcpyAsync(hl, ctx->lines, (size_t)nc * 2 * p->nlinesInSet * 2 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(flags_h, ctx->pass_flags, (size_t)nc * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    return 0;
+}
+
+static int pass_api(lfdmi_ctx *ctx, const void *img, int dtype, int n, int h, int w, int flip, int prep_mode, bool dim,
+                    const lfdmi_params *p, int n_scales, const double *rhos, lfdmi_result *results, size_t rstride, float *lines_equ,
+                    float *lines_box, int loc);
+
+// the records of a finished chunk (frames c0 .. c0 + nc, host[s * hstride + i]) into results: frames whose tables overflowed are
+// run again, alone, in the worst-case workspace; the rest are dictified.  hl: the chunk's line sets (lines_equ / lines_box)
+static int finish_pass_frames(lfdmi_ctx *ctx, const void *img, int dtype, int c0, int nc, int h, int w, int flip, int prep_mode, bool dim,
+                              const lfdmi_params *p, int n_scales, const double *rhos, lfdmi_result *host, size_t hstride, const float *hl,
+                              lfdmi_result *results, size_t rstride, float *lines_equ, float *lines_box, int loc) {
+    const size_t N = (size_t)h * w, es = dtype_size(dtype);
+    const int K = p->nlinesInSet;
+    for (int i = 0; i < nc; i++) {
+        bool spill = false;
+        for (int s = 0; s < n_scales; s++) spill = spill || host[s * hstride + i].status == LFDMI_ERR_CAPACITY;
+        if (spill) { // a table of this workspace was too small for the frame: once more, alone, in the worst-case workspace
+            lfdmi_ctx *sp = get_spill(ctx);
+            if (sp) {
+                lfdmi_result one[LFDMI_MAX_SCALES];
+                int rc = pass_api(sp, (const char *)img + (size_t)(c0 + i) * N * es, dtype, 1, h, w, flip, prep_mode, dim, p, n_scales, rhos,
+                                  one, 1, lines_equ ? lines_equ + (size_t)(c0 + i) * 2 * K : nullptr,
+                                  lines_box ? lines_box + (size_t)(c0 + i) * 2 * K : nullptr, loc);
+                if (rc) { ctx->err = sp->err; return rc; }
+                for (int s = 0; s < n_scales; s++) results[s * rstride + c0 + i] = one[s];
+                ctx->n_spilled++;
+                continue;
+            }
+        }
+        for (int s = 0; s < n_scales; s++) {
+            dictify(h, w, &host[s * hstride + i]);
+            results[s * rstride + c0 + i] = host[s * hstride + i];
+        }
+        const lfdmi_result &last = host[(size_t)(n_scales - 1) * hstride + i]; // (the lines of the last scale are the ones still in the workspace)
+        bool have = last.detection && last.status == 0;
+        for (int s = 0; s < 2; s++) {
+            float *dst = s ? lines_box : lines_equ;
+            if (!dst) continue;
+            for (int k = 0; k < 2 * K; k++) dst[(size_t)(c0 + i) * 2 * K + k] = have ? hl[((size_t)i * 2 + s) * 2 * K + k] : 0.f;
+        }
+    }
+    return 0;
+}
 
 static int pass_api(lfdmi_ctx *ctx, const void *img, int dtype, int n, int h, int w, int flip, int prep_mode, bool dim,
                     const lfdmi_params *p, int n_scales, const double *rhos, lfdmi_result *results, size_t rstride, float *lines_equ,
@@ -2020,17 +2144,7 @@ static int pass_api(lfdmi_ctx *ctx, const void *img, int dtype, int n, int h, in
         GeneralGuard gg(ctx);
         int grow_tries = 0;
         for (;;) { // (again, with the general run kernels, if a frame turned out to need them)
-            for (int s = 0; s < n_scales; s++) {
-                k_init_results<<<(nc + 63) / 64, 64, 0, ctx->stream>>>(ctx->res_dev + s * G, ctx->pass_flags, nc);
-                KCHK("k_init_results");
-            }
-            RET(run_front(ctx, d, dtype, nc, h, w, flip, prep_mode, dim, p, nullptr));
-            for (int s = 0; s < n_scales; s++) {
-                RET(run_tail(ctx, nc, h, w, rhos[s], dim, p, nullptr, nullptr, ctx->res_dev + s * G, s > 0));
-                HIPCHK(hipMemcpyAsync(host.data() + s * G, ctx->res_dev + s * G, (size_t)nc * sizeof(lfdmi_result), hipMemcpyDeviceToHost, ctx->stream));
-            }
-            HIPCHK(hipMemcpyAsync(hl.data(), ctx->lines, (size_t)nc * 2 * K * 2 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(hipMemcpyAsync(flags.data(), ctx->pass_flags, (size_t)nc * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+            RET(enqueue_pass_chunk(ctx, d, dtype, nc, h, w, flip, prep_mode, dim, p, n_scales, rhos, host.data(), G, flags.data(), hl.data()));
             HIPCHK(hipStreamSynchronize(ctx->stream));
             if (scan_gave_up(ctx, flags.data(), nc)) continue; // (see lfdmi_detect_batch)
             if (grow_tries < 4 && grow_caps(ctx, host.data(), nc, G, n_scales)) { grow_tries++; continue; } // tables enlarged: once more
@@ -2042,34 +2156,8 @@ static int pass_api(lfdmi_ctx *ctx, const void *img, int dtype, int n, int h, in
             for (int i = 0; i < nc; i++) nd[0] += (flags[i] & (dim ? 4 : 1)) != 0;
             RET(sync(ctx, nc, na, nd));
         }
-        for (int i = 0; i < nc; i++) {
-            bool spill = false;
-            for (int s = 0; s < n_scales; s++) spill = spill || host[s * G + i].status == LFDMI_ERR_CAPACITY;
-            if (spill) { // a table of this workspace was too small for the frame: once more, alone, in the worst-case workspace
-                lfdmi_ctx *sp = get_spill(ctx);
-                if (sp) {
-                    lfdmi_result one[LFDMI_MAX_SCALES];
-                    int rc = pass_api(sp, (const char *)img + (size_t)(c0 + i) * N * es, dtype, 1, h, w, flip, prep_mode, dim, p, n_scales, rhos,
-                                      one, 1, lines_equ ? lines_equ + (size_t)(c0 + i) * 2 * K : nullptr,
-                                      lines_box ? lines_box + (size_t)(c0 + i) * 2 * K : nullptr, loc);
-                    if (rc) { ctx->err = sp->err; return rc; }
-                    for (int s = 0; s < n_scales; s++) results[s * rstride + c0 + i] = one[s];
-                    ctx->n_spilled++;
-                    continue;
-                }
-            }
-            for (int s = 0; s < n_scales; s++) {
-                dictify(h, w, &host[s * G + i]);
-                results[s * rstride + c0 + i] = host[s * G + i];
-            }
-            const lfdmi_result &last = host[(size_t)(n_scales - 1) * G + i]; // (the lines of the last scale are the ones still in the workspace)
-            bool have = last.detection && last.status == 0;
-            for (int s = 0; s < 2; s++) {
-                float *dst = s ? lines_box : lines_equ;
-                if (!dst) continue;
-                for (int k = 0; k < 2 * K; k++) dst[(size_t)(c0 + i) * 2 * K + k] = have ? hl[((size_t)i * 2 + s) * 2 * K + k] : 0.f;
-            }
-        }
+        RET(finish_pass_frames(ctx, img, dtype, c0, nc, h, w, flip, prep_mode, dim, p, n_scales, rhos, host.data(), G, hl.data(), results, rstride,
+                               lines_equ, lines_box, loc));
     }
     return 0;
 }
@@ -2335,9 +2423,108 @@ static int pinned_upload(lfdmi_ctx *ctx, const char *src, size_t bytes, int kc) 
     return 0;
 }
 
+// the two passes of one chunk of lfdmi_detect_batch (remove_stars already enqueued), up to the point where the chunk's flags and
+// records may be copied out: the deferred zero fill of device-resident frames is joined
+static int enqueue_detect_passes(lfdmi_ctx *ctx, const void *d, int nc, int h, int w, const lfdmi_params *bright, const lfdmi_params *dim,
+                                 bool dual, bool delta) {
+    k_init_results<<<(nc + 63) / 64, 64, 0, ctx->stream>>>(ctx->res_dev, ctx->pass_flags, nc);
+    KCHK("k_init_results");
+    struct DualState { lfdmi_ctx *c; ~DualState() { c->dual_state = 0; } } dual_guard{ctx};
+    struct DeltaState { lfdmi_ctx *c; ~DeltaState() { c->delta_state = 0; } } delta_guard{ctx};
+    ctx->cur_pass = 0;
+    ctx->dual_state = 0;
+    ctx->delta_state = delta ? 1 : 0;
+    RET(run_pass(ctx, d, LFDMI_F32, nc, h, w, 1, LFDMI_PREP_BRIGHT, false, bright, nullptr, ctx->need_dim, (dual || delta) ? dim : nullptr));
+    ctx->cur_pass = 1;
+    ctx->dual_state = dual ? 2 : 0;
+    ctx->delta_state = delta ? 2 : 0;
+    RET(run_pass(ctx, d, LFDMI_F32, nc, h, w, 1, LFDMI_PREP_BRIGHT_THEN_DIM, true, dim, ctx->need_dim, nullptr));
+    ctx->cur_pass = 0;
+    ctx->dual_state = 0;
+    ctx->delta_state = 0;
+    RET(rs_fill_point(ctx, -1)); // (a fill no stage has started yet)
+    if (ctx->rs_fill_inflight) { HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_rsfill, 0)); ctx->rs_fill_inflight = false; }
+    return 0;
+}
+
 static int detect_impl(lfdmi_ctx *ctx, void *frames_v, int dtype, int n, int h, int w, const lfdmi_catalog *cat,
                        const lfdmi_rs_params *rs, const lfdmi_params *bright, const lfdmi_params *dim,
-                       lfdmi_result *results, int loc, int cat_f0 = 0) { // cat_f0: catalogue entry of frame 0 (a frame run again alone)
+                       lfdmi_result *results, int loc, int cat_f0 = 0);
+
+// the records of a finished chunk of lfdmi_detect_batch (frames c0 .. c0 + nc) into results: frames whose tables overflowed are
+// run again, alone, in the worst-case workspace (remove_stars has already blotted them -- device copy and caller's array -- so
+// without the catalogue, except big-endian frames: a read-only input, what the rerun uploads is not blotted); the rest are
+// dictified.  loc: LFDMI_HOST for pinned frames, as detect_impl treats them.
+static int finish_detect_frames(lfdmi_ctx *ctx, float *frames, int dtype, int c0, int nc, int h, int w, const lfdmi_catalog *cat,
+                                const lfdmi_rs_params *rs, const lfdmi_params *bright, const lfdmi_params *dim, lfdmi_result *host,
+                                lfdmi_result *results, int loc, int cat_f0, std::thread *blotter) {
+    const size_t N = (size_t)h * w;
+    const bool be = dtype == LFDMI_F32_BE;
+    for (int i = 0; i < nc; i++) {
+        if (host[i].status == LFDMI_ERR_CAPACITY) {
+            lfdmi_ctx *sp = get_spill(ctx);
+            if (sp) {
+                if (blotter && blotter->joinable()) blotter->join(); // (a host frame is read again below: its blotting must be complete)
+                int rc = detect_impl(sp, frames + (size_t)(c0 + i) * N, dtype, 1, h, w, be ? cat : nullptr, be ? rs : nullptr, bright, dim,
+                                     &results[c0 + i], loc, cat_f0 + c0 + i);
+                if (rc) { ctx->err = sp->err; return rc; }
+                ctx->n_spilled++;
+                continue;
+            }
+        }
+        dictify(h, w, &host[i]);
+        results[c0 + i] = host[i];
+    }
+    return 0;
+}
+
+// frames per chunk of host / pinned frames (see detect_impl)
+static int feed_chunk_frames(const lfdmi_ctx *ctx, int n, size_t N, bool pinned) {
+    size_t fpc = (ctx->feed_chunk_bytes ? ctx->feed_chunk_bytes : (size_t)(800u << 20)) / (N * 4);
+    int per = (int)std::min<size_t>((size_t)ctx->G, std::max<size_t>(1, fpc));
+    // pinned frames: one upload per call unless asked otherwise.  Cutting a call into k upload chunks (LFDMI_PINNED_CHUNKS=k,
+    // developer knob, read per call) overlaps chunk c + 1's upload with chunk c's passes, but a 64-frame call is 14 ms of PCIe
+    // for 1.5 ms of kernels, and what the overlap buys depends on which hardware queues HIP happens to give the five streams
+    // of a context: measured 2 940 - 3 650 frames/s with k = 4 across process states (torch initialised or not, a second
+    // context alive, GPU_MAX_HW_QUEUES=8, high-priority copy streams) against 3 430 - 3 500 in all of them with k = 1
+    // (profiles/README.md, round-3 log)
+    if (pinned) {
+        const char *pe = getenv("LFDMI_PINNED_CHUNKS");
+        const int pin_div = pe ? std::max(1, atoi(pe)) : 1;
+        per = std::max(std::min(per, 8), std::min(per, (n + pin_div - 1) / pin_div));
+    }
+    return per;
+}
+
+// how the dim pass of lfdmi_detect_batch gets its front end: from the bright pass's sweep (dual / delta) or a sweep of its own
+static void dim_front_end(lfdmi_ctx *ctx, int w, const lfdmi_params *dim, bool *dual_out, bool *delta_out) {
+    // both passes read the same float frames: one sweep feeds both where the dim pass's front end can be fused at all
+    const bool dual = ctx->fuse_dual && can_fuse_prep_erode(ctx, LFDMI_F32, w, dim->erodeKernel, dim->erode_kh, dim->erode_kw);
+    // ... or, cheaper, the bright pass's sweep leaves one bit per pixel from which the dim pass rebuilds its 8-bit image
+    // (dim value = bright value + bit, for 0 <= addFlux <= 1 and minFlux <= 0.5) together with that image's histogram
+    // (small erosion kernels only: k_bits_erode fetches kh x kw values per surviving pixel, which is nothing on sky frames but
+    // would be slow on a dense image with a large kernel; those keep the band kernel)
+    // (addFlux must stay clear of 1: x = 0.5 gives bright rne(0.5) = 0 but dim rne(1.5) = 2, and an addFlux within half an ulp
+    // of 1 rounds x + addFlux up to the same tie; up to 0.999 the float sum of an even k + 0.5 < 256 stays below k + 1.5)
+    const bool delta = !dual && ctx->delta_dim && (w % 32) == 0 && (float)dim->addFlux >= 0.0f && (float)dim->addFlux <= 0.999f &&
+                       (float)dim->minFlux <= 0.5f &&
+                       dim->erode_kh * dim->erode_kw <= 25 &&
+                       can_fuse_prep_erode(ctx, LFDMI_F32, w, dim->erodeKernel, dim->erode_kh, dim->erode_kw);
+    *dual_out = dual;
+    *delta_out = delta;
+}
+
+struct FoldState { // (an error return in the middle of a chunk must not leave the fill running on the caller's frames)
+    lfdmi_ctx *c;
+    ~FoldState() {
+        if (c->rs_fill_inflight) { (void)hipStreamSynchronize(c->side[0]); (void)hipStreamSynchronize(c->side[1]); c->rs_fill_inflight = false; }
+        c->rs_fold = false; c->rs_fill_frames = nullptr; c->rs_fill_part = 0;
+    }
+};
+
+static int detect_impl(lfdmi_ctx *ctx, void *frames_v, int dtype, int n, int h, int w, const lfdmi_catalog *cat,
+                       const lfdmi_rs_params *rs, const lfdmi_params *bright, const lfdmi_params *dim,
+                       lfdmi_result *results, int loc, int cat_f0) { // cat_f0: catalogue entry of frame 0 (a frame run again alone)
     RET(check_shape(ctx, n, h, w));
     RET(check_params(ctx, bright, false));
     RET(check_params(ctx, dim, true));
@@ -2369,37 +2556,15 @@ static int detect_impl(lfdmi_ctx *ctx, void *frames_v, int dtype, int n, int h, 
     std::vector<int4> boxes;
     KeepEqu keep_guard(ctx, ctx->stage_mode == 1);
     ctx->stages_valid = ctx->keep_equ;
-    // both passes read the same float frames: one sweep feeds both where the dim pass's front end can be fused at all
-    const bool dual = ctx->fuse_dual && can_fuse_prep_erode(ctx, LFDMI_F32, w, dim->erodeKernel, dim->erode_kh, dim->erode_kw);
-    // ... or, cheaper, the bright pass's sweep leaves one bit per pixel from which the dim pass rebuilds its 8-bit image
-    // (dim value = bright value + bit, for 0 <= addFlux <= 1 and minFlux <= 0.5) together with that image's histogram
-    // (small erosion kernels only: k_bits_erode fetches kh x kw values per surviving pixel, which is nothing on sky frames but
-    // would be slow on a dense image with a large kernel; those keep the band kernel)
-    // (addFlux must stay clear of 1: x = 0.5 gives bright rne(0.5) = 0 but dim rne(1.5) = 2, and an addFlux within half an ulp
-    // of 1 rounds x + addFlux up to the same tie; up to 0.999 the float sum of an even k + 0.5 < 256 stays below k + 1.5)
-    const bool delta = !dual && ctx->delta_dim && (w % 32) == 0 && (float)dim->addFlux >= 0.0f && (float)dim->addFlux <= 0.999f &&
-                       (float)dim->minFlux <= 0.5f &&
-                       dim->erode_kh * dim->erode_kw <= 25 &&
-                       can_fuse_prep_erode(ctx, LFDMI_F32, w, dim->erodeKernel, dim->erode_kh, dim->erode_kw);
+    bool dual, delta;
+    dim_front_end(ctx, w, dim, &dual, &delta);
     // Host frames: chunks of up to ~feed_chunk_bytes (and at most G frames) go through the pinned double buffer
     // (feed_* above), chunk k+1 uploading while chunk k is processed.  Device frames (LFDMI_FEED_MB=0, tiny batches):
     // chunks of G frames, used in place / staged by the runtime.
     int per = ctx->G;
     const bool feed = !pinned && loc == LFDMI_HOST && ctx->feed_chunk_bytes > 0 && (size_t)n * N * 4 >= (64u << 20);
     if (feed || pinned) {
-        size_t fpc = (ctx->feed_chunk_bytes ? ctx->feed_chunk_bytes : (size_t)(800u << 20)) / (N * 4);
-        per = (int)std::min<size_t>((size_t)ctx->G, std::max<size_t>(1, fpc));
-        // pinned frames: one upload per call unless asked otherwise.  Cutting a call into k upload chunks (LFDMI_PINNED_CHUNKS=k,
-        // developer knob, read per call) overlaps chunk c + 1's upload with chunk c's passes, but a 64-frame call is 14 ms of PCIe
-        // for 1.5 ms of kernels, and what the overlap buys depends on which hardware queues HIP happens to give the five streams
-        // of a context: measured 2 940 - 3 650 frames/s with k = 4 across process states (torch initialised or not, a second
-        // context alive, GPU_MAX_HW_QUEUES=8, high-priority copy streams) against 3 430 - 3 500 in all of them with k = 1
-        // (profiles/README.md, round-3 log)
-        if (pinned) {
-            const char *pe = getenv("LFDMI_PINNED_CHUNKS");
-            const int pin_div = pe ? std::max(1, atoi(pe)) : 1;
-            per = std::max(std::min(per, 8), std::min(per, (n + pin_div - 1) / pin_div));
-        }
+        per = feed_chunk_frames(ctx, n, N, pinned);
         RET(feed_prepare(ctx, (size_t)std::min(per, n) * N * 4, feed));
     }
     FeedState fs;
@@ -2445,13 +2610,7 @@ static int detect_impl(lfdmi_ctx *ctx, void *frames_v, int dtype, int n, int h, 
         const bool copy_back = cat && loc == LFDMI_HOST && !host_blot && !be;
         ctx->rs_fold = cat && cat->max_obj > 0 && ctx->rs_fold_on && delta && w <= RS_MAXW && !copy_back;
         ctx->rs_fill_frames = nullptr;
-        struct FoldState { // (an error return in the middle of a chunk must not leave the fill running on the caller's frames)
-            lfdmi_ctx *c;
-            ~FoldState() {
-                if (c->rs_fill_inflight) { (void)hipStreamSynchronize(c->side[0]); (void)hipStreamSynchronize(c->side[1]); c->rs_fill_inflight = false; }
-                c->rs_fold = false; c->rs_fill_frames = nullptr; c->rs_fill_part = 0;
-            }
-        } fold_guard{ctx};
+        FoldState fold_guard{ctx};
         if (cat) {
             RET(run_removestars(ctx, (float *)d, cat_f0 + c0, nc, h, w, cat, rs, host_blot ? &boxes : nullptr, !ctx->rs_fold));
             if (ctx->rs_fold && loc == LFDMI_DEVICE) { ctx->rs_fill_frames = (float *)d; ctx->rs_fill_part = 0; ctx->rs_fill_nc = nc; ctx->rs_fill_h = h; ctx->rs_fill_w = w; }
@@ -2466,28 +2625,12 @@ static int detect_impl(lfdmi_ctx *ctx, void *frames_v, int dtype, int n, int h, 
         GeneralGuard gg(ctx);
         int grow_tries = 0;
         for (;;) { // (again, with the general run kernels, if a frame turned out to need them)
-        k_init_results<<<(nc + 63) / 64, 64, 0, ctx->stream>>>(ctx->res_dev, ctx->pass_flags, nc);
-        KCHK("k_init_results");
-        struct DualState { lfdmi_ctx *c; ~DualState() { c->dual_state = 0; } } dual_guard{ctx};
-        struct DeltaState { lfdmi_ctx *c; ~DeltaState() { c->delta_state = 0; } } delta_guard{ctx};
-        ctx->cur_pass = 0;
-        ctx->dual_state = 0;
-        ctx->delta_state = delta ? 1 : 0;
-        RET(run_pass(ctx, d, LFDMI_F32, nc, h, w, 1, LFDMI_PREP_BRIGHT, false, bright, nullptr, ctx->need_dim, (dual || delta) ? dim : nullptr));
-        ctx->cur_pass = 1;
-        ctx->dual_state = dual ? 2 : 0;
-        ctx->delta_state = delta ? 2 : 0;
-        RET(run_pass(ctx, d, LFDMI_F32, nc, h, w, 1, LFDMI_PREP_BRIGHT_THEN_DIM, true, dim, ctx->need_dim, nullptr));
-        ctx->cur_pass = 0;
-        ctx->dual_state = 0;
-        ctx->delta_state = 0;
+        RET(enqueue_detect_passes(ctx, d, nc, h, w, bright, dim, dual, delta));
         if (host_blot && !blotted) { // host threads zero-fill the caller's frames in the background (joined below / at the end)
             if (blotter.joinable()) blotter.join();
-            blotter = std::thread([=, bx = boxes, cpus = ctx->feed_cpus] { blot_host_frames(frames + (size_t)c0 * N, nc, h, w, cat, cat_f0 + c0, bx, cpus); });
+            blotter = std::thread([=, bx = boxes, cpus = ctx->feed_cpus] { blot_host_frames(frames + (size_t)c0 * N, nc, h, w, cat, cat_f0 + c0, bx.data(), cpus); });
             blotted = true;
         }
-        RET(rs_fill_point(ctx, -1)); // (a fill no stage has started yet)
-        if (ctx->rs_fill_inflight) { HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_rsfill, 0)); ctx->rs_fill_inflight = false; }
         HIPCHK(hipMemcpyAsync(ctx->res_host, ctx->pass_flags, (size_t)ctx->G * sizeof(int) + (size_t)nc * sizeof(lfdmi_result), hipMemcpyDeviceToHost, ctx->stream));
         { double t0_ = feed && getenv("LFDMI_FEED_TRACE") ? feed_now() : 0;
         HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -2506,24 +2649,7 @@ static int detect_impl(lfdmi_ctx *ctx, void *frames_v, int dtype, int n, int h, 
             RET(sync(ctx, nc, na, nd));
         }
         if (feed) feed_done(&fs, kc + 1); // this chunk's two buffers are free again: chunk kc + 2 may start
-        for (int i = 0; i < nc; i++) {
-            if (host[i].status == LFDMI_ERR_CAPACITY) {
-                // a table of this workspace was too small for the frame: once more, alone, in the worst-case workspace.
-                // remove_stars has already blotted the frame (device copy and, by now, the caller's array): no catalogue.
-                lfdmi_ctx *sp = get_spill(ctx);
-                if (sp) {
-                    if (blotter.joinable()) blotter.join(); // (a host frame is read again below: its blotting must be complete)
-                    // (a big-endian frame is a read-only input: what the rerun uploads is not blotted, it needs the frame's catalogue entry)
-                    int rc = detect_impl(sp, frames + (size_t)(c0 + i) * N, dtype, 1, h, w, be ? cat : nullptr, be ? rs : nullptr, bright, dim,
-                                         &results[c0 + i], loc, cat_f0 + c0 + i);
-                    if (rc) { ctx->err = sp->err; return rc; }
-                    ctx->n_spilled++;
-                    continue;
-                }
-            }
-            dictify(h, w, &host[i]);
-            results[c0 + i] = host[i];
-        }
+        RET(finish_detect_frames(ctx, frames, dtype, c0, nc, h, w, cat, rs, bright, dim, host, results, loc, cat_f0, &blotter));
     }
     return 0;
 }
@@ -2538,6 +2664,325 @@ extern "C" int lfdmi_detect_batch_raw(lfdmi_ctx *ctx, void *frames, int dtype, i
                                       lfdmi_result *results, int loc) {
     return detect_impl(ctx, frames, dtype, n, h, w, cat, rs, bright, dim, results, loc);
 }
+
+// ---- C-ABI: calls in flight -----------------------------------------------------------------------------------------------
+// lfdmi_detect_batch_begin / lfdmi_process_multiscale_begin enqueue every chunk of a call on the context's stream, exactly the
+// chunks the synchronous call runs (enqueue_detect_passes / enqueue_pass_chunk), and copy each chunk's flags and records into
+// the call's page-locked area in stream order.  What the synchronous call decides on the host between chunks -- a rerun after
+// the scan's give-up, after table growth or with the general run kernels, the worst-case spills, dictify -- is decided by
+// lfdmi_end_oldest once the call's last copy has landed (finish_detect_frames / finish_pass_frames).  A chunk that has to run
+// again does so then, through the synchronous path, after the stream has drained: later calls' chunks were queued on the same
+// tables and growth reallocates them.  Their records were copied out in stream order and stay valid; each call handles its own
+// overflow at its own end.
+
+static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
+    const char *x = (const char *)a, *y = (const char *)b;
+    return na && nb && x < y + nb && y < x + na;
+}
+
+// the checks both begins share; the call then takes ring entry (call_first + n_calls)
+static int begin_check(lfdmi_ctx *ctx, const void *frames, size_t bytes, int loc, bool multiscale) {
+    if (!ctx) return LFDMI_ERR_ARG;
+    if (ctx->n_calls >= LFDMI_MAX_CALLS_IN_FLIGHT) return fail(ctx, LFDMI_ERR_ARG, "LFDMI_MAX_CALLS_IN_FLIGHT calls in flight: lfdmi_end_oldest first");
+    if (ctx->timing) return fail(ctx, LFDMI_ERR_ARG, "calls in flight are not timed: lfdmi_enable_timing(ctx, 0) first");
+    if (loc == LFDMI_HOST)
+        return fail(ctx, LFDMI_ERR_ARG, "pageable host frames cannot be enqueued (the runtime stages their copy synchronously): "
+                                        "use memory from lfdmi_host_alloc (LFDMI_HOST_PINNED) or device memory");
+    if (multiscale ? loc != LFDMI_DEVICE : (loc != LFDMI_DEVICE && loc != LFDMI_HOST_PINNED)) return fail(ctx, LFDMI_ERR_ARG, "bad loc");
+    for (int k = 0; k < ctx->n_calls; k++) { // (two multi-scale passes only read their images: they may share them)
+        const PendingCall &o = ctx->calls[(ctx->call_first + k) % LFDMI_MAX_CALLS_IN_FLIGHT];
+        if ((!multiscale || o.kind == 0) && ranges_overlap(frames, bytes, o.frames, o.frame_bytes))
+            return fail(ctx, LFDMI_ERR_ARG, "frames overlap those of a call in flight");
+    }
+    return 0;
+}
+
+// the call's own copies of the params and their structuring elements
+static void own_params(PendingCall &pc, const lfdmi_params *a, const lfdmi_params *b) {
+    const lfdmi_params *src[2] = {a, b};
+    lfdmi_params *dst[2] = {&pc.p1, &pc.p2};
+    auto ksize = [](const uint8_t *k, int kh, int kw) -> size_t { return k && kh > 0 && kw > 0 ? (size_t)kh * kw : 0; };
+    size_t total = 0;
+    for (const lfdmi_params *p : src)
+        if (p) total += ksize(p->dilateKernel, p->dilate_kh, p->dilate_kw) + ksize(p->erodeKernel, p->erode_kh, p->erode_kw);
+    pc.kern.assign(total, 0);
+    size_t o = 0;
+    for (int i = 0; i < 2; i++) {
+        if (!src[i]) continue;
+        *dst[i] = *src[i];
+        if (size_t k = ksize(src[i]->dilateKernel, src[i]->dilate_kh, src[i]->dilate_kw)) {
+            memcpy(pc.kern.data() + o, src[i]->dilateKernel, k);
+            dst[i]->dilateKernel = pc.kern.data() + o;
+            o += k;
+        }
+        if (size_t k = ksize(src[i]->erodeKernel, src[i]->erode_kh, src[i]->erode_kw)) {
+            memcpy(pc.kern.data() + o, src[i]->erodeKernel, k);
+            dst[i]->erodeKernel = pc.kern.data() + o;
+            o += k;
+        }
+    }
+}
+
+// the call's page-locked area: n flags | n_scales x n records | n_boxes remove_stars squares (grown, never shrunk)
+static int call_area(lfdmi_ctx *ctx, PendingCall &pc, int n, int n_scales, size_t n_boxes) {
+    const size_t fb = ((size_t)n * sizeof(int) + 255) & ~(size_t)255;
+    const size_t rb = ((size_t)n_scales * n * sizeof(lfdmi_result) + 255) & ~(size_t)255;
+    const size_t need = std::max<size_t>(256, fb + rb + n_boxes * sizeof(int4));
+    if (pc.pin_bytes < need) {
+        if (pc.pin) { HIPCHK(hipHostFree(pc.pin)); pc.pin = nullptr; pc.pin_bytes = 0; }
+        HIPCHK(hipHostMalloc(&pc.pin, need, hipHostMallocDefault));
+        pc.pin_bytes = need;
+    }
+    if (!pc.done) HIPCHK(hipEventCreateWithFlags(&pc.done, hipEventDisableTiming));
+    pc.flags_h = (int *)pc.pin;
+    pc.rec_h = (lfdmi_result *)((char *)pc.pin + fb);
+    pc.boxes_h = (int4 *)((char *)pc.pin + fb + rb);
+    return 0;
+}
+
+// a begin that fails after enqueueing chunks: what it enqueued is drained and discarded (the calls in flight stay as they are)
+struct BeginAbort {
+    lfdmi_ctx *c;
+    bool armed = true;
+    ~BeginAbort() {
+        c->general_on = true;
+        if (!armed) return;
+        (void)hipStreamSynchronize(c->stream);
+        for (hipStream_t st : {c->feed_copy, c->feed_copy2, c->side[0], c->side[1]})
+            if (st) (void)hipStreamSynchronize(st);
+    }
+};
+
+// pinned frames of a call in flight: the upload into feed_dev[kc & 1] waits for the last kernel that read that buffer (chunk
+// kc - 2, possibly the previous call's)
+static int async_upload(lfdmi_ctx *ctx, const char *src, size_t bytes, int kc) {
+    const int j = kc & 1;
+    if (ctx->feed_free_set[j]) {
+        HIPCHK(hipStreamWaitEvent(ctx->feed_copy, ctx->feed_free[j], 0));
+        HIPCHK(hipStreamWaitEvent(ctx->feed_copy2, ctx->feed_free[j], 0));
+    }
+    return pinned_upload(ctx, src, bytes, kc);
+}
+
+static PendingCall &next_call(lfdmi_ctx *ctx) {
+    PendingCall &pc = ctx->calls[(ctx->call_first + ctx->n_calls) % LFDMI_MAX_CALLS_IN_FLIGHT];
+    pc.status = 0;
+    pc.finished = false;
+    pc.chunks.clear();
+    return pc;
+}
+
+extern "C" int lfdmi_detect_batch_begin(lfdmi_ctx *ctx, void *frames, int dtype, int n, int h, int w, const lfdmi_catalog *cat,
+                                        const lfdmi_rs_params *rs, const lfdmi_params *bright, const lfdmi_params *dim,
+                                        lfdmi_result *results, int loc) {
+    const size_t N = h > 0 && w > 0 ? (size_t)h * w : 0;
+    RET(begin_check(ctx, frames, n > 0 ? (size_t)n * N * 4 : 0, loc, false));
+    Internal internal(ctx);
+    RET(check_shape(ctx, n, h, w));
+    RET(check_params(ctx, bright, false));
+    RET(check_params(ctx, dim, true));
+    if (!frames || !results) return fail(ctx, LFDMI_ERR_ARG, "NULL argument");
+    if (dtype != LFDMI_F32 && dtype != LFDMI_F32_BE) return fail(ctx, LFDMI_ERR_DTYPE, "lfdmi_detect_batch_begin: frames must be LFDMI_F32 or LFDMI_F32_BE");
+    if (cat && cat->max_obj > 0 && (!rs || rs->filter_index < 0 || rs->filter_index > 4)) return fail(ctx, LFDMI_ERR_ARG, "removestars params");
+    PendingCall &pc = next_call(ctx);
+    pc.kind = 0;
+    pc.frames = frames; pc.frame_bytes = (size_t)n * N * 4;
+    pc.n = n; pc.h = h; pc.w = w; pc.loc = loc;
+    pc.results = results;
+    pc.has_cat = cat != nullptr; if (cat) pc.cat = *cat;
+    pc.has_rs = rs != nullptr; if (rs) pc.rs = *rs;
+    own_params(pc, bright, dim);
+    const lfdmi_catalog *cc = pc.has_cat ? &pc.cat : nullptr;
+    const lfdmi_rs_params *rr = pc.has_rs ? &pc.rs : nullptr;
+    const bool pinned = loc == LFDMI_HOST_PINNED;
+    if (dtype == LFDMI_F32_BE && !pinned) { // (as lfdmi_detect_batch_raw: device frames are swapped in place, once)
+        RET(run_bswap(ctx, frames, pc.frame_bytes));
+        dtype = LFDMI_F32;
+    }
+    pc.dtype = dtype;
+    pc.be = dtype == LFDMI_F32_BE;
+    if (!hough_fits(ctx, h, w, bright->houghMethod, LFD_PI / 180) || !hough_fits(ctx, h, w, dim->houghMethod, LFD_PI / 180)) {
+        // rho finer than this workspace's accumulators: the worst-case workspace takes the call, here and now
+        lfdmi_ctx *sp = get_spill(ctx);
+        if (!sp || !hough_fits(sp, h, w, bright->houghMethod, LFD_PI / 180) || !hough_fits(sp, h, w, dim->houghMethod, LFD_PI / 180))
+            return fail(ctx, LFDMI_ERR_CAPACITY, "Hough accumulator larger than the workspace (rho < 1 px)");
+        int rc = detect_impl(sp, frames, dtype, n, h, w, cc, rr, &pc.p1, &pc.p2, results, loc);
+        if (rc) { ctx->err = sp->err; return rc; }
+        pc.finished = true;
+        ctx->n_calls++;
+        return 0;
+    }
+    KeepEqu keep_guard(ctx, ctx->stage_mode == 1); // (before the front-end choice, which depends on it, as in detect_impl)
+    ctx->stages_valid = ctx->keep_equ;
+    bool dual, delta;
+    dim_front_end(ctx, w, &pc.p2, &dual, &delta);
+    const int per = pinned ? feed_chunk_frames(ctx, n, N, true) : ctx->G;
+    pc.host_blot = cc && pinned && cc->loc == LFDMI_HOST && !pc.be;
+    const int max_obj = cc ? std::max(0, cc->max_obj) : 0;
+    RET(call_area(ctx, pc, n, 1, pc.host_blot ? (size_t)n * max_obj : 0));
+    if (pinned && n > 0) {
+        RET(feed_prepare(ctx, (size_t)std::min(per, n) * N * 4, false));
+        for (int i = 0; i < 2; i++)
+            if (!ctx->feed_free[i]) HIPCHK(hipEventCreateWithFlags(&ctx->feed_free[i], hipEventDisableTiming));
+    }
+    const int fail_chunk = ctx->fail_chunk;
+    ctx->fail_chunk = -1;
+    BeginAbort abort_guard{ctx};
+    if (pinned && n > 0) RET(async_upload(ctx, (const char *)frames, (size_t)std::min(per, n) * N * 4, 0));
+    for (int c0 = 0, kc = 0; c0 < n; c0 += per, kc++) {
+        const int nc = n - c0 < per ? n - c0 : per;
+        if (kc == fail_chunk) return fail(ctx, LFDMI_ERR_ARG, "lfdmi_debug_fail_chunk: injected failure");
+        const void *d;
+        if (pinned) { // (chunk kc + 1 uploads while chunk kc runs, as in detect_impl)
+            d = ctx->feed_dev[kc & 1];
+            if (c0 + per < n)
+                RET(async_upload(ctx, (const char *)frames + (size_t)(c0 + per) * N * 4, (size_t)std::min(per, n - c0 - per) * N * 4, kc + 1));
+            HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->feed_up[kc & 1], 0));
+        } else d = (const float *)frames + (size_t)c0 * N;
+        if (pc.be) RET(run_bswap(ctx, (void *)d, (size_t)nc * N * 4));
+        // remove_stars as in detect_impl, except that the squares a host catalogue gives pinned frames are copied into the call's
+        // area in stream order and the caller's array is blotted at the end
+        const bool copy_back = cc && pinned && !pc.host_blot && !pc.be;
+        ctx->rs_fold = cc && cc->max_obj > 0 && ctx->rs_fold_on && delta && w <= RS_MAXW && !copy_back;
+        ctx->rs_fill_frames = nullptr;
+        FoldState fold_guard{ctx};
+        if (cc) {
+            RET(run_removestars(ctx, (float *)d, c0, nc, h, w, cc, rr, nullptr, !ctx->rs_fold));
+            if (ctx->rs_fold && !pinned) { ctx->rs_fill_frames = (float *)d; ctx->rs_fill_part = 0; ctx->rs_fill_nc = nc; ctx->rs_fill_h = h; ctx->rs_fill_w = w; }
+            if (copy_back) RET(out_copy(ctx, frames, (size_t)c0 * N * 4, d, (size_t)nc * N * 4, LFDMI_HOST));
+            if (pc.host_blot && max_obj > 0)
+                HIPCHK(hipMemcpyAsync(pc.boxes_h + (size_t)c0 * max_obj, ctx->rs_boxes, (size_t)nc * max_obj * sizeof(int4), hipMemcpyDeviceToHost, ctx->stream));
+        }
+        CallChunk ch{c0, nc, !ctx->frame_ccl || ctx->general_seen, ctx->scan_fused, ctx->n_cap_growths};
+        ctx->general_on = ch.general_on;
+        RET(enqueue_detect_passes(ctx, d, nc, h, w, &pc.p1, &pc.p2, dual, delta));
+        ctx->general_on = true;
+        if (pinned) { HIPCHK(hipEventRecord(ctx->feed_free[kc & 1], ctx->stream)); ctx->feed_free_set[kc & 1] = true; }
+        HIPCHK(hipMemcpyAsync(pc.flags_h + c0, ctx->pass_flags, (size_t)nc * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(pc.rec_h + c0, ctx->res_dev, (size_t)nc * sizeof(lfdmi_result), hipMemcpyDeviceToHost, ctx->stream));
+        pc.chunks.push_back(ch);
+    }
+    HIPCHK(hipEventRecord(pc.done, ctx->stream));
+    abort_guard.armed = false;
+    ctx->n_calls++;
+    return 0;
+}
+
+extern "C" int lfdmi_process_multiscale_begin(lfdmi_ctx *ctx, const void *img, int dtype, int n, int h, int w, int flip, int dim,
+                                              int after_bright, const lfdmi_params *p, int n_scales, const double *rhos,
+                                              lfdmi_result *results, int loc) {
+    const size_t N = h > 0 && w > 0 ? (size_t)h * w : 0, es = dtype_size(dtype);
+    RET(begin_check(ctx, img, n > 0 ? (size_t)n * N * es : 0, loc, true));
+    Internal internal(ctx);
+    RET(check_shape(ctx, n, h, w));
+    RET(check_params(ctx, p, dim != 0));
+    if (!img || !results || !rhos || dtype < 0 || dtype > 2) return fail(ctx, LFDMI_ERR_ARG, "bad argument");
+    if (n_scales < 1 || n_scales > LFDMI_MAX_SCALES) return fail(ctx, LFDMI_ERR_ARG, "n_scales out of range");
+    if (dtype == LFDMI_U8 && dim) return fail(ctx, LFDMI_ERR_DTYPE, "dim pass needs a float image (numpy refuses uint8 += float)");
+    PendingCall &pc = next_call(ctx);
+    pc.kind = 1;
+    pc.frames = (void *)img; pc.frame_bytes = (size_t)n * N * es;
+    pc.dtype = dtype; pc.n = n; pc.h = h; pc.w = w; pc.loc = loc;
+    pc.flip = flip; pc.dim = dim != 0; pc.n_scales = n_scales;
+    pc.prep_mode = dim ? (after_bright ? LFDMI_PREP_BRIGHT_THEN_DIM : LFDMI_PREP_DIM) : LFDMI_PREP_BRIGHT;
+    for (int s = 0; s < n_scales; s++) pc.rhos[s] = rhos[s];
+    pc.results = results;
+    own_params(pc, p, nullptr);
+    for (int s = 0; s < n_scales; s++)
+        if (!hough_fits(ctx, h, w, rhos[s], LFD_PI / 180)) { // (as lfdmi_process_multiscale: the worst-case workspace, here and now)
+            lfdmi_ctx *sp = get_spill(ctx);
+            if (!sp || !hough_fits(sp, h, w, rhos[s], LFD_PI / 180)) return fail(ctx, LFDMI_ERR_CAPACITY, "Hough accumulator larger than the workspace (rho < 1 px)");
+            int rc = pass_api(sp, img, dtype, n, h, w, flip, pc.prep_mode, pc.dim, &pc.p1, n_scales, pc.rhos, results, (size_t)n, nullptr, nullptr, loc);
+            if (rc) { ctx->err = sp->err; return rc; }
+            pc.finished = true;
+            ctx->n_calls++;
+            return 0;
+        }
+    RET(call_area(ctx, pc, n, n_scales, 0));
+    KeepEqu keep_guard(ctx, ctx->stage_mode != 0);
+    ctx->stages_valid = ctx->keep_equ;
+    ctx->cur_pass = 0;
+    BeginAbort abort_guard{ctx};
+    for (int c0 = 0; c0 < n; c0 += ctx->G) {
+        const int nc = n - c0 < ctx->G ? n - c0 : ctx->G;
+        CallChunk ch{c0, nc, !ctx->frame_ccl || ctx->general_seen, ctx->scan_fused, ctx->n_cap_growths};
+        ctx->general_on = ch.general_on;
+        RET(enqueue_pass_chunk(ctx, (const char *)img + (size_t)c0 * N * es, dtype, nc, h, w, flip, pc.prep_mode, pc.dim, &pc.p1, n_scales,
+                               pc.rhos, pc.rec_h + c0, (size_t)n, pc.flags_h + c0, nullptr));
+        ctx->general_on = true;
+        pc.chunks.push_back(ch);
+    }
+    HIPCHK(hipEventRecord(pc.done, ctx->stream));
+    abort_guard.armed = false;
+    ctx->n_calls++;
+    return 0;
+}
+
+// the host half of a call in flight, once its last copy has landed
+static int finish_call(lfdmi_ctx *ctx, PendingCall &pc) {
+    HIPCHK(hipEventSynchronize(pc.done));
+    const size_t N = (size_t)pc.h * pc.w;
+    const lfdmi_catalog *cc = pc.has_cat ? &pc.cat : nullptr;
+    const lfdmi_rs_params *rr = pc.has_rs ? &pc.rs : nullptr;
+    if (pc.host_blot) // remove_stars on the caller's pinned array (before any rerun reads it again)
+        blot_host_frames((float *)pc.frames, pc.n, pc.h, pc.w, cc, 0, pc.boxes_h, ctx->feed_cpus);
+    const size_t rstride = pc.kind ? (size_t)pc.n : 1;
+    const int n_scales = pc.kind ? pc.n_scales : 1;
+    for (const CallChunk &ch : pc.chunks) {
+        const int *flags = pc.flags_h + ch.c0;
+        lfdmi_result *rec = pc.rec_h + ch.c0;
+        bool again = scan_gave_up(ctx, flags, ch.nc, ch.scan_fused);
+        if (!again) {
+            bool over = false;
+            for (int s = 0; s < n_scales; s++)
+                for (int i = 0; i < ch.nc; i++) over = over || rec[s * rstride + i].status == LFDMI_ERR_CAPACITY;
+            // (tables that have grown since the chunk was enqueued may hold it already)
+            again = over && (ctx->n_cap_growths > ch.growths || grow_caps(ctx, rec, ch.nc, rstride, n_scales));
+        }
+        if (!again) again = general_again(ctx, ch.general_on, flags, ch.nc);
+        ctx->general_on = true;
+        if (again) { // through the synchronous path, on a drained stream
+            HIPCHK(hipStreamSynchronize(ctx->stream));
+            if (pc.kind == 0) {
+                // device frames are swapped and blotted by now, pinned ones blotted (above, or by the copy back): no catalogue but
+                // for big-endian host frames, a read-only input
+                RET(detect_impl(ctx, (float *)pc.frames + (size_t)ch.c0 * N, pc.dtype, ch.nc, pc.h, pc.w, pc.be ? cc : nullptr, pc.be ? rr : nullptr,
+                                &pc.p1, &pc.p2, pc.results + ch.c0, pc.loc, ch.c0));
+            } else {
+                RET(pass_api(ctx, (const char *)pc.frames + (size_t)ch.c0 * N * dtype_size(pc.dtype), pc.dtype, ch.nc, pc.h, pc.w, pc.flip, pc.prep_mode,
+                             pc.dim, &pc.p1, pc.n_scales, pc.rhos, pc.results + ch.c0, rstride, nullptr, nullptr, pc.loc));
+            }
+            continue;
+        }
+        chunk_done(ctx);
+        if (pc.kind == 0)
+            RET(finish_detect_frames(ctx, (float *)pc.frames, pc.dtype, ch.c0, ch.nc, pc.h, pc.w, cc, rr, &pc.p1, &pc.p2, rec, pc.results,
+                                     pc.loc == LFDMI_HOST_PINNED ? LFDMI_HOST : pc.loc, 0, nullptr));
+        else
+            RET(finish_pass_frames(ctx, pc.frames, pc.dtype, ch.c0, ch.nc, pc.h, pc.w, pc.flip, pc.prep_mode, pc.dim, &pc.p1, pc.n_scales, pc.rhos,
+                                   rec, rstride, nullptr, pc.results, rstride, nullptr, nullptr, pc.loc));
+    }
+    return 0;
+}
+
+extern "C" int lfdmi_end_oldest(lfdmi_ctx *ctx) {
+    if (!ctx) return LFDMI_ERR_ARG;
+    if (!ctx->n_calls) return fail(ctx, LFDMI_ERR_ARG, "lfdmi_end_oldest: no call in flight");
+    PendingCall &pc = ctx->calls[ctx->call_first];
+    ctx->call_first = (ctx->call_first + 1) % LFDMI_MAX_CALLS_IN_FLIGHT;
+    ctx->n_calls--;
+    if (pc.finished) return pc.status;
+    HIPCHK(hipSetDevice(ctx->device));
+    Internal internal(ctx);
+    int rc = finish_call(ctx, pc);
+    if (rc) { // (the context stays usable: nothing of this call is left on the stream)
+        (void)hipStreamSynchronize(ctx->stream);
+        ctx->general_on = true;
+    }
+    return rc;
+}
+
+extern "C" int lfdmi_calls_in_flight(lfdmi_ctx *ctx) { return ctx ? ctx->n_calls : LFDMI_ERR_ARG; }
 
 // pinned host memory for LFDMI_HOST_PINNED frames: allocated (and first touched) by a thread bound to the CPUs next to the GPU
 extern "C" int lfdmi_host_alloc(lfdmi_ctx *ctx, uint64_t bytes, void **out) {
@@ -2568,6 +3013,7 @@ extern "C" int lfdmi_host_free(lfdmi_ctx *ctx, void *p) {
 
 extern "C" int lfdmi_get_counters(lfdmi_ctx *ctx, int slot0, int n, int32_t *dst) {
     if (!ctx || !dst || slot0 < 0 || n < 0 || slot0 + n > ctx->G) return LFDMI_ERR_ARG;
+    RET(idle(ctx));
     static_assert(C_COUNT == LFDMI_COUNTERS, "counter layout");
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(hipMemcpyAsync(dst, ctx->counters + (size_t)slot0 * C_COUNT, (size_t)n * C_COUNT * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
@@ -2586,6 +3032,7 @@ extern "C" int lfdmi_debug_fail_chunk(lfdmi_ctx *ctx, int chunk) {
 // developer tool: phase clocks of the last k_frame_contours launch
 extern "C" int lfdmi_debug_frame_profile(lfdmi_ctx *ctx, int n, long long *dst) {
     if (!ctx || !ctx->prof || n < 0 || n > ctx->G) return LFDMI_ERR_ARG;
+    RET(idle(ctx));
     HIPCHK(hipMemcpyAsync(dst, ctx->prof, (size_t)n * 16 * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;
@@ -2599,6 +3046,7 @@ extern "C" int lfdmi_debug_tail(lfdmi_ctx *ctx, int n, int kmax, const float *h1
                                 int navg, double dro, double thetaTresh, double lineSetTresh, int which, int h, int w, lfdmi_result *out) {
     if (!ctx || n < 0 || !h1 || !h2 || !n1 || !n2 || !out || kmax < 1 || navg < 1 || navg > LFDMI_MAX_SET_LINES || (which != 1 && which != 2))
         return fail(ctx, LFDMI_ERR_ARG, "lfdmi_debug_tail: bad argument");
+    RET(idle(ctx));
     HIPCHK(hipSetDevice(ctx->device));
     const int G = ctx->G, K = navg;
     std::vector<float> lines((size_t)G * 2 * K * 2);
@@ -2634,6 +3082,7 @@ extern "C" int lfdmi_debug_tail(lfdmi_ctx *ctx, int n, int kmax, const float *h1
 
 extern "C" int lfdmi_debug_trig(lfdmi_ctx *ctx, int n, const double *y, const double *x, float *angle_deg, float *cos_half, float *sin_half) {
     if (!ctx || n < 0 || !y || !x || !angle_deg || !cos_half || !sin_half) return LFDMI_ERR_ARG;
+    RET(idle(ctx));
     if (n == 0) return 0;
     HIPCHK(hipSetDevice(ctx->device));
     RET(ensure_scratch(ctx, (size_t)n * (2 * sizeof(double) + 3 * sizeof(float))));
@@ -2658,6 +3107,7 @@ extern "C" int lfdmi_set_stage_images(lfdmi_ctx *ctx, int mode) {
 
 extern "C" int lfdmi_get_stage(lfdmi_ctx *ctx, int slot, int which, int h, int w, uint8_t *dst, int loc) {
     if (!ctx || !dst || slot < 0 || slot >= ctx->G) return LFDMI_ERR_ARG;
+    RET(idle(ctx));
     if (ctx->last_h <= 0) return fail(ctx, LFDMI_ERR_ARG, "no call has run yet");
     if (h != ctx->last_h || w != ctx->last_w) return fail(ctx, LFDMI_ERR_ARG, "lfdmi_get_stage: the last call worked on a different shape");
     size_t N = (size_t)h * w, BW = (size_t)h * LFD_WQ(w);
