@@ -403,6 +403,86 @@ int lfdmi_debug_fail_chunk(lfdmi_ctx *ctx, int chunk);
  * n host operand pairs -- compared with the host libm by tests/test_gpu_stages.py */
 int lfdmi_debug_trig(lfdmi_ctx *ctx, int n, const double *y, const double *x, float *angle_deg, float *cos_half, float *sin_half);
 
+/* ---- trail profiles ---------------------------------------------------------------------------------------------------------
+ * lfdmi_measure_trails refines the Hough line of every frame whose detection record has found != 0 and measures the trail's
+ * cross-section along it.  The reference defines the quantities (lfd/analysis/profiles: the observed FWHM of
+ * ConvolutionObject.calc_fwhm, convolutionobj.py:160-178, and the per-cent depth of the central dip, samplers.py:158-162) but
+ * measures them on no frame.  The procedure below is the definition; tests/trail_ref.py restates it in numpy and the device
+ * reproduces it exactly.  Notation: R = half_width, L = seg_len, P = prof_half, K = P / prof_step (an integer).
+ *
+ * 1. Frame and line.  Coordinates are the detection's: x = column, y = row of the flipped frame (cv2.flip(img, 0),
+ *    detecttrails.py:124), so (x, y) reads buffer row H-1-y.  The start line is x cos(th) + y sin(th) = rho with the record's
+ *    float32 rho / theta widened to double; c = cos(th), s = sin(th) are taken once on the host (C library, double).  The line
+ *    is then carried as a foot point f = (rho c, rho s) and a unit direction d = (-s, c); its normal is n = (d.y, -d.x).
+ *    A point at position t and offset u is p = (f.x + t*d.x + u*n.x, f.y + t*d.y + u*n.y), double, evaluated left to right.
+ * 2. Samples.  Bilinear in float32: x0 = floor(p.x), y0 = floor(p.y), a = (float)(p.x - x0), b = (float)(p.y - y0); with
+ *    v00, v10, v01, v11 the values at (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1):
+ *        top = v00 + a*(v10 - v00);  bot = v01 + a*(v11 - v01);  value = top + b*(bot - top)
+ *    (float32, each operation rounded, no FMA contraction).  A sample is valid only when all four taps lie inside the frame
+ *    (0 <= x0, x0+1 <= W-1, 0 <= y0, y0+1 <= H-1), are finite, and lie outside every square remove_stars zeroes for the
+ *    frame's catalogue (removestars.py:212-231, the library's own k_rs_boxes geometry); so blotted LFDMI_F32 frames and
+ *    unblotted LFDMI_F32_BE ones measure the same.
+ *    Positions: tlo / thi are the bounds of {t : 0 <= p.x <= W-1, 0 <= p.y <= H-1} at u = 0 (per axis with d != 0: the
+ *    quotients (0 - f)/d and (max - f)/d; an axis with d == 0 and f outside [0, max] leaves none); the positions are the
+ *    integers t_j = tmin + j, tmin = ceil(tlo), j = 0 .. npos-1, npos = floor(thi) - tmin + 1.
+ * 3. Statistic.  Every profile value m(u) is the lower median (rank floor((m-1)/2) in ascending order) of the m valid samples
+ *    over the positions, at one offset u; NaN when m == 0.
+ * 4. Refinement.  Passes i = 0 .. n_iter:
+ *    - npos < 2L: status TOO_SHORT, stop.  Segments: j in [sL, sL+L); a last partial one is kept when it has >= L/2 positions.
+ *    - per segment s, m_s(u) at integer u in [-R, R]; in double: b_s = lower median of m_s over the wings |u| > R - wing;
+ *      sig_s = 1.4826 * lower median of |m_s - b_s| over the wings; A_s = max_u (m_s - b_s); s is significant when no
+ *      m_s(u) is NaN, A_s > k_sig * sig_s and A_s > 0; its centre c_s = sum(u w_u) / sum(w_u), w_u = max((m_s(u) - b_s) - A_s/2, 0).
+ *    - the extent is the longest run of consecutive significant segments (a tie: the first); fewer than 2 segments: status
+ *      TOO_FAINT, stop.  Pass n_iter only determines the extent (on the final line).
+ *    - otherwise c = a + b t is fitted by least squares weighted by A_s over the run, t = tmin + sL + (n_s - 1)/2 at the
+ *      segment middles: S = sum w, St = sum w t, Stt = sum w t t, Sc = sum w c, Stc = sum w t c (in run order);
+ *      b = (S Stc - St Sc) / (S Stt - St St), a = (Sc - b St) / S.  Then f += a n, d = (d + b n) / |d + b n| (sqrt of
+ *      d.x d.x + d.y d.y), n from d.  All of step 4 in double, sequential in index order, no contraction.
+ * 5. Result.  Over the extent's positions (j from the run's first segment start to its last segment end), m(u_k) at
+ *    u_k = (k - K) * prof_step, k = 0 .. 2K (float32).  background = lower median of the non-NaN m(u_k) with |u_k| >= P - wing;
+ *    the profile is v_k = m(u_k) - background (float32), peak = max of the non-NaN v_k (<= 0: TOO_FAINT).  fwhm follows
+ *    calc_fwhm literally: left / right = first / last k with v_k >= peak/2, fwhm = |u_right| + |u_left|, 0 when left == right;
+ *    fwhm_arcsec = fwhm * pixscale.  depth = (peak - v_K) / peak * 100 (double).  noise = 1.4826 * lower median of |v_k| over
+ *    the same wing bins (double).  (x1, y1), (x2, y2) = p at the extent's first and last position (u = 0); rho / theta are
+ *    the final line's (host: the normal pointing into theta in [0, pi], rho = f . n).
+ * status: LFDMI_TRAIL_OK, or LFDMI_TRAIL_NOT_FOUND (record found == 0), _TOO_SHORT, _TOO_FAINT; every double of a record
+ * without LFDMI_TRAIL_OK is NaN, and so is its profile row. */
+typedef struct {
+    int32_t half_width;  /* R: refinement window, +-R px around the line (1 .. 64); default 32 */
+    int32_t seg_len;     /* L: positions per segment (2 .. 64); default 64 */
+    int32_t n_iter;      /* refinement passes (0 .. 16); default 3 */
+    int32_t wing;        /* wing width in px for background and noise (1 .. R); default 8 */
+    double k_sig;        /* significance of a segment, in sigmas; default 5 */
+    double prof_half;    /* P: profile half-width in px; default 24 */
+    double prof_step;    /* profile bin step in px (P / prof_step an integer, at most 512); default 0.1: calc_fwhm takes the
+                            innermost bins at or above half maximum, so it reads low by up to 2 steps (0.5 px at 0.25, 11 %
+                            of a sigma = 2 px trail; 0.2 px, 4 %, at 0.1) */
+    double pixscale;     /* arcsec per px; default 0.396 (SDSS) */
+} lfdmi_trail_params;
+enum { LFDMI_TRAIL_OK = 0, LFDMI_TRAIL_NOT_FOUND = 1, LFDMI_TRAIL_TOO_SHORT = 2, LFDMI_TRAIL_TOO_FAINT = 3 };
+typedef struct {
+    int32_t status;          /* LFDMI_TRAIL_* */
+    int32_t n_pos;           /* positions of the extent */
+    int32_t n_seg;           /* segments of the extent */
+    int32_t min_valid;       /* fewest valid samples in any profile bin */
+    double rho, theta;       /* the refined line (flipped frame, as the record's) */
+    double x1, y1, x2, y2;   /* the extent's end points (flipped frame, as in results.txt) */
+    double background, noise, peak;
+    double fwhm, fwhm_arcsec, depth;
+} lfdmi_trail;
+void lfdmi_default_trail_params(lfdmi_trail_params *out);
+/* frames: n frames of h x w, LFDMI_F32 or LFDMI_F32_BE (the bytes as they are now: big-endian device frames that
+ * lfdmi_detect_batch_raw has swapped in place are LFDMI_F32 afterwards), loc LFDMI_HOST, LFDMI_HOST_PINNED or LFDMI_DEVICE;
+ * rec: the n records lfdmi_detect_batch_raw returned for them (host) -- records of the FLIPPED frame (step 1); the per-pass
+ * entry points give such records only with flip = 1 (records of flip = 0 calls describe the unflipped buffer and would be
+ * measured along the mirrored line); cat / rs: the catalogue and remove_stars parameters
+ * of that call (cat may be NULL: no squares); p NULL: the defaults; out: n records (host); profiles: n x (2K+1) float32 (host,
+ * may be NULL).  The frames are only read.  Only frames with found != 0 are worked on; the workspace for it is allocated on
+ * the first call. */
+int lfdmi_measure_trails(lfdmi_ctx *ctx, const void *frames, int dtype, int n, int h, int w, int loc, const lfdmi_result *rec,
+                         const lfdmi_catalog *cat, const lfdmi_rs_params *rs, const lfdmi_trail_params *p, lfdmi_trail *out,
+                         float *profiles);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,7 @@ SYMBOLS = (
     "lfdmi_detect_batch", "lfdmi_detect_batch_raw", "lfdmi_host_alloc", "lfdmi_host_free", "lfdmi_fits_read_frames", "lfdmi_fits_read_photoobj", "lfdmi_bz2_find_blocks", "lfdmi_bz2_create", "lfdmi_bz2_destroy", "lfdmi_bz2_last_error", "lfdmi_bz2_decode_batch", "lfdmi_bz2_fetch", "lfdmi_bz2_fetch_many", "lfdmi_bz2_frames", "lfdmi_bz2_reserve", "lfdmi_bz2_timings", "lfdmi_set_stage_images", "lfdmi_get_stage", "lfdmi_get_counters", "lfdmi_enable_timing", "lfdmi_timing_select", "lfdmi_get_timing",
     "lfdmi_timing_slots", "lfdmi_timing_name",
     "lfdmi_detect_batch_begin", "lfdmi_process_multiscale_begin", "lfdmi_end_oldest", "lfdmi_calls_in_flight",
+    "lfdmi_default_trail_params", "lfdmi_measure_trails",
 )
 
 
@@ -86,6 +87,37 @@ RESULT_DTYPE = np.dtype([("status", "<i4"), ("found", "<i4"), ("rho", "<f4"), ("
                          ("x1", "<i4"), ("y1", "<i4"), ("x2", "<i4"), ("y2", "<i4"),
                          ("n_lines_equ", "<i4"), ("n_lines_box", "<i4"), ("detection", "<i4"),
                          ("rejected_by_theta", "<i4")])
+
+class TrailParams(C.Structure):
+    """lfdmi_trail_params (include/lfdmi.h: trail profiles)."""
+    _fields_ = [("half_width", C.c_int32), ("seg_len", C.c_int32), ("n_iter", C.c_int32), ("wing", C.c_int32),
+                ("k_sig", C.c_double), ("prof_half", C.c_double), ("prof_step", C.c_double), ("pixscale", C.c_double)]
+
+
+# lfdmi_trail: one record per frame of lfdmi_measure_trails
+TRAIL_DTYPE = np.dtype([("status", "<i4"), ("n_pos", "<i4"), ("n_seg", "<i4"), ("min_valid", "<i4"),
+                        ("rho", "<f8"), ("theta", "<f8"), ("x1", "<f8"), ("y1", "<f8"), ("x2", "<f8"), ("y2", "<f8"),
+                        ("background", "<f8"), ("noise", "<f8"), ("peak", "<f8"),
+                        ("fwhm", "<f8"), ("fwhm_arcsec", "<f8"), ("depth", "<f8")])
+TRAIL_OK, TRAIL_NOT_FOUND, TRAIL_TOO_SHORT, TRAIL_TOO_FAINT = 0, 1, 2, 3
+
+
+def make_trail_params(**params):
+    """lfdmi_default_trail_params with the given fields replaced (unknown names raise)."""
+    p = TrailParams()
+    lib().lfdmi_default_trail_params(C.byref(p))
+    names = {k for k, _ in TrailParams._fields_}
+    for k, v in params.items():
+        if k not in names:
+            raise TypeError(f"unknown trail parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def trail_bins(p):
+    """2K+1 profile bins of a TrailParams"""
+    return 2 * int(round(p.prof_half / p.prof_step)) + 1
+
 
 _lib = None
 
@@ -749,6 +781,43 @@ class Context:
         res = np.zeros((len(rhos), n), RESULT_DTYPE)
         args = (_ptr(img), _dtype_code(img), n, h, w, int(flip), int(dim), int(after_bright), C.byref(p), len(rhos), rh, _ptr(res), DEVICE)
         return self._begin(self._lib.lfdmi_process_multiscale_begin, args, res, [img, p, keep, rh, args], squeeze=sq)
+
+    # -- trail profiles (lfdmi_measure_trails) ----------------------------------------------------------------------------------
+    def measure_trails(self, frames, records, cat=None, rs=None, pinned=False, native_device=False, **params):
+        """Refined line, extent, cross-section profile, fwhm and depth of every frame whose detection record has found != 0
+        (include/lfdmi.h: trail profiles).  frames: what ``detect_batch`` took ('<f4' or '>f4' numpy, torch CUDA float32,
+        ``DeviceFrames``), only read; records: its result array -- records of the flipped frame, as ``detect_batch`` (and
+        ``process_bright`` / ``_dim`` / ``_multiscale`` with flip=True) return them.  ``DeviceFrames`` hold big-endian data
+        until ``detect_batch`` has swapped them in place: ``native_device=True`` after that call.  Returns (TRAIL_DTYPE array
+        [n], float32 profiles [n, 2K+1]); frames without a measurement have NaN rows."""
+        if isinstance(frames, DeviceFrames):
+            n, h, w = frames.shape
+            code = F32 if native_device else F32_BE
+        elif not _is_dev(frames) and isinstance(frames, np.ndarray) and frames.dtype == np.dtype(">f4"):
+            if not frames.flags.c_contiguous:
+                raise ValueError("big-endian frames must be C-contiguous")
+            shp = frames.shape
+            n, h, w = (1, *shp) if len(shp) == 2 else shp
+            code = F32_BE
+        else:
+            frames, n, h, w, sq = self._batch(frames)
+            code = _dtype_code(frames)
+            if code != F32:
+                raise TypeError("measure_trails needs float32 frames")
+        if pinned and _is_dev(frames):
+            raise ValueError("pinned=True is for host arrays")
+        rec = np.ascontiguousarray(records, RESULT_DTYPE).reshape(-1)
+        if len(rec) != n:
+            raise ValueError(f"{len(rec)} records for {n} frames")
+        p = make_trail_params(**params)
+        c, keep = self._catalog(cat)
+        out = np.zeros(n, TRAIL_DTYPE)
+        prof = np.empty((n, trail_bins(p)), np.float32)
+        loc = DEVICE if _is_dev(frames) else (HOST_PINNED if pinned else HOST)
+        self._chk(self._lib.lfdmi_measure_trails(self._h, _ptr(frames), code, n, h, w, loc, _ptr(rec),
+                                                 C.byref(c) if c is not None else None, C.byref(rs) if rs is not None else None,
+                                                 C.byref(p), _ptr(out), _ptr(prof)))
+        return out, prof
 
     def pinned_buffer(self, nbytes):
         """Page-locked host memory next to this context's GPU (lfdmi_host_alloc) as a ``PinnedBuffer``."""

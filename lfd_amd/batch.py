@@ -229,3 +229,20 @@ class BatchDetector:
                                  self._slice_cat(catalogs, a, b), rs)
                 for c, (a, b) in zip(self.ctxs, bounds) if b > a]
         return np.concatenate([f.result() for f in futs])
+
+    def measure_trails(self, frames, records, catalogs=None, rs=None, **params):
+        """``Context.measure_trails`` over the batch (trail profiles of the frames whose record has found != 0), sharded like
+        ``detect``.  With calls in flight it runs after them: the calls that produced ``records`` have ended by then."""
+        if self.lanes == 1:
+            for f in list(self._pending):
+                f.result()
+            self._pending = []
+            while self.ctx.calls_in_flight():
+                self.ctx._end_oldest()
+            return self.ctx.measure_trails(frames, records, catalogs, rs, **params)
+        n = frames.shape[0]
+        bounds = shard_bounds(n, self.lanes)
+        futs = [self.pool.submit(c.measure_trails, frames[a:b], records[a:b], self._slice_cat(catalogs, a, b), rs, **params)
+                for c, (a, b) in zip(self.ctxs, bounds) if b > a]
+        res = [f.result() for f in futs]
+        return np.concatenate([r[0] for r in res]), np.concatenate([r[1] for r in res])

@@ -28,6 +28,7 @@
 #include "k_image.h"
 #include "k_rect.h"
 #include "k_frame.h"
+#include "k_trail.h"
 #include "fits_reader.h"
 
 #define LFD_PI 3.1415926535897932384626433832795
@@ -259,6 +260,14 @@ struct lfdmi_ctx {
     int internal = 0;                  // > 0: the library itself is running a call (begin / end): the in-flight refusal is off
     hipEvent_t feed_free[2] = {nullptr, nullptr}; // recorded behind the last kernel that read feed_dev[i] (calls in flight)
     bool feed_free_set[2] = {false, false};
+    // lfdmi_measure_trails' workspace (k_trail.h), allocated by its first call and grown on demand
+    struct TrailWs {
+        void *st = nullptr, *segm = nullptr, *sA = nullptr, *sC = nullptr, *sSig = nullptr, *planes = nullptr, *boxes = nullptr,
+             *prof = nullptr, *cnt = nullptr, *rec = nullptr, *stage = nullptr;
+        size_t st_c = 0, segm_c = 0, sA_c = 0, sC_c = 0, sSig_c = 0, planes_c = 0, boxes_c = 0, prof_c = 0, cnt_c = 0, rec_c = 0,
+               stage_c = 0;
+        size_t bytes = 0;
+    } trail;
 };
 
 static int fail(lfdmi_ctx *c, int code, const std::string &msg) {
@@ -551,7 +560,9 @@ extern "C" int lfdmi_ctx_create(int device, int max_h, int max_w, int max_inflig
 extern "C" int lfdmi_ctx_create_sized(int device, int max_h, int max_w, int max_inflight, const lfdmi_caps *caps, lfdmi_ctx **out) {
     return create_impl(device, max_h, max_w, max_inflight, caps, out);
 }
-extern "C" int64_t lfdmi_ctx_bytes(lfdmi_ctx *ctx) { return ctx ? (int64_t)(ctx->bytes + (ctx->spill ? ctx->spill->bytes : 0)) : 0; }
+extern "C" int64_t lfdmi_ctx_bytes(lfdmi_ctx *ctx) {
+    return ctx ? (int64_t)(ctx->bytes + ctx->trail.bytes + (ctx->spill ? ctx->spill->bytes : 0)) : 0;
+}
 extern "C" int64_t lfdmi_spill_count(lfdmi_ctx *ctx) { return ctx ? ctx->n_spilled : 0; }
 extern "C" int lfdmi_get_stats(lfdmi_ctx *ctx, int64_t *out, int n) {
     if (!ctx || !out || n < 0 || n > LFDMI_STAT_COUNT) return LFDMI_ERR_ARG;
@@ -717,6 +728,9 @@ extern "C" void lfdmi_ctx_destroy(lfdmi_ctx *ctx) {
     if (ctx->rs_sboxes) hipFree(ctx->rs_sboxes);
     if (ctx->rs_rowstart) hipFree(ctx->rs_rowstart);
     if (ctx->cat_dev) hipFree(ctx->cat_dev);
+    for (void *p : {ctx->trail.st, ctx->trail.segm, ctx->trail.sA, ctx->trail.sC, ctx->trail.sSig, ctx->trail.planes, ctx->trail.boxes,
+                    ctx->trail.prof, ctx->trail.cnt, ctx->trail.rec, ctx->trail.stage})
+        if (p) hipFree(p);
     for (auto e : ctx->ev_pool) hipEventDestroy(e);
     if (ctx->own_stream && ctx->stream) hipStreamDestroy(ctx->stream);
     for (int i = 0; i < 2; i++) {
@@ -3133,4 +3147,173 @@ extern "C" int lfdmi_get_stage(lfdmi_ctx *ctx, int slot, int which, int h, int w
     } else return fail(ctx, LFDMI_ERR_ARG, "unknown stage");
     RET(out_copy(ctx, dst, 0, src, N, loc));
     return sync(ctx, 1);
+}
+
+// ---- C-ABI: trail profiles (include/lfdmi.h, k_trail.h) ---------------------------------------------------------------------
+extern "C" void lfdmi_default_trail_params(lfdmi_trail_params *o) {
+    if (!o) return;
+    o->half_width = 32; o->seg_len = 64; o->n_iter = 3; o->wing = 8;
+    o->k_sig = 5.0; o->prof_half = 24.0; o->prof_step = 0.1; o->pixscale = 0.396;
+}
+
+// one table of the trail workspace, at least `need` bytes (its contents are not kept when it grows)
+static int trail_buf(lfdmi_ctx *ctx, void **p, size_t *cap, size_t need) {
+    if (*cap >= need) return 0;
+    if (*p) { HIPCHK(hipStreamSynchronize(ctx->stream)); HIPCHK(hipFree(*p)); *p = nullptr; ctx->trail.bytes -= *cap; *cap = 0; }
+    HIPCHK(hipMalloc(p, need));
+    *cap = need;
+    ctx->trail.bytes += need;
+    return 0;
+}
+
+static void trail_blank(lfdmi_trail *o, int status) {
+    const double nan = NAN;
+    o->status = status; o->n_pos = 0; o->n_seg = 0; o->min_valid = 0;
+    o->rho = o->theta = o->x1 = o->y1 = o->x2 = o->y2 = nan;
+    o->background = o->noise = o->peak = o->fwhm = o->fwhm_arcsec = o->depth = nan;
+}
+
+#define TRAIL_CHUNK 64 // frames per chunk of a call (staging slots of host frames, mask planes, segment tables)
+
+extern "C" int lfdmi_measure_trails(lfdmi_ctx *ctx, const void *frames, int dtype, int n, int h, int w, int loc, const lfdmi_result *rec,
+                                    const lfdmi_catalog *cat, const lfdmi_rs_params *rs, const lfdmi_trail_params *p_in, lfdmi_trail *out,
+                                    float *profiles) {
+    RET(check_shape(ctx, n, h, w));
+    if (n > 0 && (!frames || !rec || !out)) return fail(ctx, LFDMI_ERR_ARG, "NULL argument");
+    if (dtype != LFDMI_F32 && dtype != LFDMI_F32_BE) return fail(ctx, LFDMI_ERR_DTYPE, "lfdmi_measure_trails takes LFDMI_F32 / LFDMI_F32_BE frames");
+    if (loc != LFDMI_HOST && loc != LFDMI_DEVICE && loc != LFDMI_HOST_PINNED) return fail(ctx, LFDMI_ERR_ARG, "bad loc");
+    if (h < 2 || w < 2) return fail(ctx, LFDMI_ERR_ARG, "frame smaller than 2 x 2");
+    lfdmi_trail_params q;
+    if (p_in) q = *p_in; else lfdmi_default_trail_params(&q);
+    const double kd = q.prof_half / q.prof_step;
+    const int K = (std::isfinite(kd) && kd >= 1 && kd <= TRAIL_MAX_K) ? (int)llround(kd) : 0;
+    if (q.half_width < 1 || q.half_width > TRAIL_MAX_R || q.seg_len < 2 || q.seg_len > 64 || q.n_iter < 0 || q.n_iter > 16 ||
+        q.wing < 1 || q.wing > q.half_width || !std::isfinite(q.k_sig) || !std::isfinite(q.pixscale) || !(q.prof_step > 0) ||
+        K == 0 || fabs((double)K * q.prof_step - q.prof_half) > 1e-9 * q.prof_half || q.wing > q.prof_half)
+        return fail(ctx, LFDMI_ERR_ARG, "trail params out of range (include/lfdmi.h: lfdmi_trail_params)");
+    const bool stars = cat && cat->max_obj > 0;
+    if (stars && (!rs || rs->filter_index < 0 || rs->filter_index > 4)) return fail(ctx, LFDMI_ERR_ARG, "removestars params");
+    const int nb = 2 * K + 1;
+    const size_t N = (size_t)h * w;
+    std::vector<int> act;
+    for (int i = 0; i < n; i++) {
+        if (rec[i].found) act.push_back(i);
+        else trail_blank(&out[i], LFDMI_TRAIL_NOT_FOUND);
+        if (profiles && !rec[i].found) for (int b = 0; b < nb; b++) profiles[(size_t)i * nb + b] = NAN;
+    }
+    const int nact = (int)act.size();
+    if (nact == 0) return 0;
+
+    TrailDev dp;
+    dp.R = q.half_width; dp.L = q.seg_len; dp.n_iter = q.n_iter; dp.wing = q.wing; dp.K = K;
+    dp.maxpos = (int)ceil(sqrt((double)ctx->H * ctx->H + (double)ctx->W * ctx->W)) + 2; // a line crosses a frame of the ctx in fewer
+    dp.maxseg = dp.maxpos / dp.L + 1;
+    dp.be = dtype == LFDMI_F32_BE; dp.h = h; dp.w = w; dp.wq = (w + 31) / 32;
+    dp.k_sig = q.k_sig; dp.P = q.prof_half; dp.step = q.prof_step; dp.pixscale = q.pixscale;
+    const int nu = 2 * dp.R + 1;
+    const int CH = std::min(ctx->G, TRAIL_CHUNK);
+    auto &T = ctx->trail;
+    RET(trail_buf(ctx, &T.st, &T.st_c, (size_t)nact * sizeof(TrailState)));
+    RET(trail_buf(ctx, &T.segm, &T.segm_c, (size_t)CH * dp.maxseg * nu * sizeof(float)));
+    RET(trail_buf(ctx, &T.sA, &T.sA_c, (size_t)CH * dp.maxseg * sizeof(double)));
+    RET(trail_buf(ctx, &T.sC, &T.sC_c, (size_t)CH * dp.maxseg * sizeof(double)));
+    RET(trail_buf(ctx, &T.sSig, &T.sSig_c, (size_t)CH * dp.maxseg * sizeof(int)));
+    RET(trail_buf(ctx, &T.prof, &T.prof_c, (size_t)nact * nb * sizeof(float)));
+    RET(trail_buf(ctx, &T.cnt, &T.cnt_c, (size_t)CH * nb * sizeof(int)));
+    RET(trail_buf(ctx, &T.rec, &T.rec_c, (size_t)nact * 10 * sizeof(double)));
+    if (stars) {
+        RET(trail_buf(ctx, &T.planes, &T.planes_c, (size_t)CH * ctx->H * ((ctx->W + 31) / 32) * sizeof(uint32_t)));
+        RET(trail_buf(ctx, &T.boxes, &T.boxes_c, (size_t)CH * cat->max_obj * sizeof(int4)));
+    }
+    if (loc != LFDMI_DEVICE) RET(trail_buf(ctx, &T.stage, &T.stage_c, (size_t)CH * N * 4));
+
+    // the start lines (definition step 1: cos / sin once, here, in double) and where each frame is read from
+    std::vector<TrailState> hs(nact);
+    std::vector<int> first(1, 0); // first active index of each chunk
+    for (int k = 0, c0 = 0; c0 < n; c0 += CH) {
+        int slot = 0;
+        for (; k < nact && act[k] < c0 + CH; k++, slot++) {
+            const int i = act[k];
+            TrailState &s = hs[k];
+            memset(&s, 0, sizeof(s));
+            const double th = (double)rec[i].theta, rho = (double)rec[i].rho, c = cos(th), sn = sin(th);
+            s.fx = rho * c; s.fy = rho * sn; s.dx = -sn; s.dy = c;
+            s.img = loc == LFDMI_DEVICE ? (const void *)((const char *)frames + (size_t)i * N * 4)
+                                        : (const void *)((char *)T.stage + (size_t)slot * N * 4);
+            s.frame = k; s.slot = slot; s.chunk_frame = i - c0;
+        }
+        first.push_back(k);
+    }
+    HIPCHK(hipMemcpyAsync(T.st, hs.data(), (size_t)nact * sizeof(TrailState), hipMemcpyHostToDevice, ctx->stream));
+    TrailState *st = (TrailState *)T.st;
+    const uint32_t *planes = stars ? (const uint32_t *)T.planes : nullptr;
+    for (int ci = 0, c0 = 0; c0 < n; c0 += CH, ci++) {
+        const int a0 = first[ci], na = first[ci + 1] - a0, nc = std::min(CH, n - c0);
+        if (na == 0) continue;
+        if (loc != LFDMI_DEVICE)
+            for (int k = a0; k < a0 + na; k++)
+                HIPCHK(hipMemcpyAsync((char *)T.stage + (size_t)(k - a0) * N * 4, (const char *)frames + (size_t)act[k] * N * 4, N * 4,
+                                      hipMemcpyHostToDevice, ctx->stream));
+        if (stars) {
+            lfdmi_catalog dev;
+            RET(stage_catalog(ctx, cat, c0, nc, &dev));
+            RsDev rp;
+            rp.defaultxy = rs->defaultxy; rp.maxxy = rs->maxxy; rp.magcount = rs->magcount; rp.filter_index = rs->filter_index;
+            rp.pixscale = rs->pixscale; rp.maxmagdiff = rs->maxmagdiff; rp.filter_cap = rs->filter_cap;
+            k_rs_boxes<<<dim3((cat->max_obj + 255) / 256, nc), 256, 0, ctx->stream>>>(h, w, cat->max_obj, dev.count, dev.rowc, dev.colc,
+                                                                                   dev.psfmag, dev.petro90, dev.nobserve, dev.ndetect, rp,
+                                                                                   (int4 *)T.boxes);
+            KCHK("k_rs_boxes");
+            HIPCHK(hipMemsetAsync(T.planes, 0, (size_t)na * h * dp.wq * sizeof(uint32_t), ctx->stream));
+            k_trail_mask<<<dim3((cat->max_obj + 3) / 4, na), 256, 0, ctx->stream>>>(st + a0, na, cat->max_obj, (const int4 *)T.boxes,
+                                                                                   (uint32_t *)T.planes, dp);
+            KCHK("k_trail_mask");
+        }
+        k_trail_init<<<(na + 63) / 64, 64, 0, ctx->stream>>>(st + a0, na, dp);
+        KCHK("k_trail_init");
+        for (int it = 0; it <= dp.n_iter; it++) {
+            k_trail_seg<<<dim3(dp.maxseg, na), TRAIL_SEG_THREADS, 0, ctx->stream>>>(st + a0, na, planes, (float *)T.segm, dp);
+            KCHK("k_trail_seg");
+            k_trail_fit<<<na, 64, 0, ctx->stream>>>(st + a0, na, (const float *)T.segm, (double *)T.sA, (double *)T.sC, (int *)T.sSig,
+                                                    it == dp.n_iter, dp);
+            KCHK("k_trail_fit");
+        }
+        k_trail_prof<<<dim3(nb, na), 256, (size_t)dp.maxpos * sizeof(uint32_t), ctx->stream>>>(st + a0, na, planes, (float *)T.prof,
+                                                                                              (int *)T.cnt, dp);
+        KCHK("k_trail_prof");
+        k_trail_final<<<na, 64, 0, ctx->stream>>>(st + a0, na, (float *)T.prof, (const int *)T.cnt, (double *)T.rec, dp);
+        KCHK("k_trail_final");
+    }
+    std::vector<float> hp((size_t)nact * nb);
+    std::vector<double> hr((size_t)nact * 10);
+    HIPCHK(hipMemcpyAsync(hs.data(), T.st, (size_t)nact * sizeof(TrailState), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(hp.data(), T.prof, hp.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(hr.data(), T.rec, hr.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    RET(sync(ctx));
+    for (int k = 0; k < nact; k++) {
+        const TrailState &s = hs[k];
+        const int i = act[k];
+        if (s.status < 0) return fail(ctx, s.status, "lfdmi_measure_trails: a line longer than the workspace's tables");
+        lfdmi_trail *o = &out[i];
+        if (s.status != 0 || !s.done) {
+            trail_blank(o, s.status ? s.status : LFDMI_TRAIL_TOO_FAINT);
+            if (profiles) for (int b = 0; b < nb; b++) profiles[(size_t)i * nb + b] = NAN;
+            continue;
+        }
+        const double *r = &hr[(size_t)k * 10];
+        o->status = LFDMI_TRAIL_OK;
+        o->n_pos = std::min(s.s1 * dp.L + dp.L, s.npos) - s.s0 * dp.L;
+        o->n_seg = s.s1 - s.s0 + 1;
+        o->min_valid = s.min_valid;
+        // the final line's rho / theta: the normal turned into theta in [0, pi]
+        double nx = s.dy, ny = -s.dx;
+        if (ny < 0.0 || (ny == 0.0 && nx < 0.0)) { nx = -nx; ny = -ny; }
+        o->theta = atan2(ny, nx);
+        o->rho = s.fx * nx + s.fy * ny;
+        o->x1 = r[0]; o->y1 = r[1]; o->x2 = r[2]; o->y2 = r[3];
+        o->background = r[4]; o->noise = r[5]; o->peak = r[6];
+        o->fwhm = r[7]; o->fwhm_arcsec = r[8]; o->depth = r[9];
+        if (profiles) memcpy(profiles + (size_t)i * nb, &hp[(size_t)k * nb], nb * sizeof(float));
+    }
+    return 0;
 }

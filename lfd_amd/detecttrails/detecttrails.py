@@ -27,7 +27,8 @@ from .removestars import read_photoObj_arrays
 RETR_EXTERNAL, RETR_LIST, RETR_CCOMP, RETR_TREE = 0, 1, 2, 3
 CHAIN_APPROX_NONE, CHAIN_APPROX_SIMPLE, CHAIN_APPROX_TC89_L1, CHAIN_APPROX_TC89_KCOS = 1, 2, 3, 4
 
-__all__ = ["DetectTrails", "process_field", "process_fields_batched", "process_frame_arrays", "default_params"]
+__all__ = ["DetectTrails", "process_field", "process_fields_batched", "process_frame_arrays", "default_params", "measure_trail",
+           "profile_row"]
 
 _HEADER_KEYS = ("TAI", "CRPIX1", "CRPIX2", "CRVAL1", "CRVAL2", "CD1_1", "CD1_2", "CD2_1", "CD2_2")
 
@@ -85,6 +86,59 @@ def process_frame_arrays(img, cat, filter, params_bright, params_dim, params_rem
     return False, None, rec
 
 
+def _pack_one(cat):
+    if cat is None or not len(cat["NOBSERVE"]):
+        return None
+    from .removestars import _check_finite
+    _check_finite(cat)
+    n = len(cat["NOBSERVE"])
+    packed = {"count": _np.array([n], _np.int32)}
+    for key in ("ROWC", "COLC", "PSFMAG", "PETROTH90"):
+        packed[key] = _np.ascontiguousarray(cat[key], _np.float32).reshape(1, n, 5)
+    for key in ("NOBSERVE", "NDETECT"):
+        packed[key] = _np.ascontiguousarray(cat[key], _np.int32).reshape(1, n)
+    return packed
+
+
+def measure_trail(img, record, cat=None, filter=None, params_removestars=None, **params):
+    """Trail profile of one frame (include/lfdmi.h: trail profiles): ``img`` in the orientation ``process_frame_arrays`` takes
+    (blotted or not: remove_stars' squares of ``cat`` are left out of the samples either way), ``record`` the detection record
+    it returned.  ``params``: fields of lfdmi_trail_params.  Returns (record of TRAIL_DTYPE, float32 profile [2K+1])."""
+    img = _np.ascontiguousarray(img)
+    if img.ndim != 2 or img.dtype not in (_np.dtype("<f4"), _np.dtype(">f4")):
+        raise TypeError("measure_trail needs a 2-d float32 frame")
+    packed = _pack_one(cat)
+    rs = None
+    if packed is not None:
+        if filter is None or params_removestars is None:
+            raise ValueError("a catalogue needs its filter and params_removestars")
+        rs = _rs_struct(filter, params_removestars)
+    with use_context(*img.shape) as ctx:
+        out, prof = ctx.measure_trails(img, _np.asarray(record, _native.RESULT_DTYPE).reshape(1), packed, rs, **params)
+    return out[0], prof[0]
+
+
+def profile_row(key, trail, profile):
+    """One profiles.txt row: ``run camcol filter field``, the scalar fields of the trail record (TRAIL_DTYPE order), then the
+    2K+1 profile values; floats as ``repr`` (exact round trip)."""
+    vals = []
+    for name in _native.TRAIL_DTYPE.names:
+        v = trail[name].item()
+        vals.append(str(v) if isinstance(v, int) else repr(float(v)))
+    vals += [repr(float(v)) for v in profile]
+    return " ".join([" ".join(str(x) for x in key)] + vals) + "\n"
+
+
+def _write_profile(profiles, errors, key, meas, debug):
+    """the frame's profiles row, or its errors entry when the measurement raised (results.txt is written before, untouched)"""
+    try:
+        if isinstance(meas, Exception):
+            raise meas
+        profiles.write(profile_row(key, *meas))
+    except Exception as e:  # noqa: BLE001
+        _log_error(errors, key, e, debug)
+
+
 def _load_frame(run, camcol, filter, field):
     """Frame image (float32, C-contiguous), results-row head, photoObj columns; raises like the
     reference when neither the .fits nor the .fits.bz2 exists (detecttrails.py:81-87)."""
@@ -111,22 +165,32 @@ def _log_error(errors, ids, exc, debug):
 
 
 def process_field(results, errors, run, camcol, filter, field, params_bright, params_dim,
-                  params_removestars):
+                  params_removestars, profiles=None, trail_params=None):
     """One frame end to end (reference: detecttrails.py:30-143): locate the frame (or its .bz2),
     read image + header + photoObj, detect, append ``run camcol filter field tai crpix1 crpix2
     crval1 crval2 cd11 cd12 cd21 cd22 x1 y1 x2 y2`` to ``results``; every exception is logged
-    to ``errors`` (ids, 3-frame traceback, message) and swallowed."""
+    to ``errors`` (ids, 3-frame traceback, message) and swallowed.  ``profiles``: a file the frame's trail profile row
+    (``profile_row``) is appended to when it has a detection."""
+    debug = params_bright.get("debug") or params_dim.get("debug")
     try:
         img, head, cat = _load_frame(run, camcol, filter, field)
-        detection, res, _ = process_frame_arrays(img, cat, filter, params_bright, params_dim,
-                                                 params_removestars)
+        detection, res, rec = process_frame_arrays(img, cat, filter, params_bright, params_dim,
+                                                   params_removestars)
         if detection:
             results.write(f"{head} {res['x1']} {res['y1']} {res['x2']} {res['y2']}\n")
     except Exception as e:  # noqa: BLE001 - the reference swallows everything per frame
-        _log_error(errors, (run, camcol, filter, field), e, params_bright.get("debug") or params_dim.get("debug"))
+        _log_error(errors, (run, camcol, filter, field), e, debug)
+        return
+    if detection and profiles is not None:
+        try:
+            meas = measure_trail(img, rec, cat, filter, params_removestars, **(trail_params or {}))
+        except Exception as e:  # noqa: BLE001
+            meas = e
+        _write_profile(profiles, errors, (run, camcol, filter, field), meas, debug)
 
 
-def process_fields_batched(results, errors, ids, params_bright, params_dim, params_removestars, loaded=None):
+def process_fields_batched(results, errors, ids, params_bright, params_dim, params_removestars, loaded=None, profiles=None,
+                           trail_params=None):
     """Same outcome as calling process_field for every (run, camcol, filter, field) in ``ids``, in order -- the same
     results rows, the same errors entries, a bad frame costs only itself (detecttrails.py:119-139) -- but all frames
     that load go through ONE lfdmi_detect_batch call per (filter, shape) group (frames with different filters use
@@ -135,6 +199,8 @@ def process_fields_batched(results, errors, ids, params_bright, params_dim, para
     if loaded is None:
         loaded = _load_many(ids)
     rows = {}
+    meas = {}                                         # key -> (trail record, profile) or the measurement's exception
+    tp = trail_params or {}
     debug = params_bright.get("debug") or params_dim.get("debug")
     groups = {}
     for item in loaded:
@@ -153,14 +219,28 @@ def process_fields_batched(results, errors, ids, params_bright, params_dim, para
         try:
             frames = _np.stack([it[1] for it in group])
             packed = pack_catalogs([it[3] for it in group])
+            rs = _rs_struct(flt, params_removestars)
             with use_context(*shape, inflight=min(32, len(group))) as ctx:
-                recs = ctx.detect_batch(frames, params_bright, params_dim, packed, _rs_struct(flt, params_removestars))
+                recs = ctx.detect_batch(frames, params_bright, params_dim, packed, rs)
+                if profiles is not None:
+                    try:
+                        tr, pr = ctx.measure_trails(frames, recs, packed, rs, **tp)
+                        for j, it in enumerate(group):
+                            meas[it[0]] = (tr[j], pr[j])
+                    except Exception as e:  # noqa: BLE001 - the group's measurement failed: each detected frame logs it
+                        for it in group:
+                            meas[it[0]] = e
             for it, rec in zip(group, recs):
                 rows[it[0]] = rec
         except Exception:  # noqa: BLE001 - a call-level failure: every frame of the group on its own, under its own try
             for it in group:
                 try:
                     rows[it[0]] = process_frame_arrays(it[1], it[3], flt, params_bright, params_dim, params_removestars)[2]
+                    if profiles is not None and rows[it[0]]["found"]:
+                        try:
+                            meas[it[0]] = measure_trail(it[1], rows[it[0]], it[3], flt, params_removestars, **tp)
+                        except Exception as e:  # noqa: BLE001
+                            meas[it[0]] = e
                 except Exception as e:  # noqa: BLE001
                     rows[it[0]] = e
     for item in loaded:
@@ -181,6 +261,9 @@ def process_fields_batched(results, errors, ids, params_bright, params_dim, para
                 results.write(f"{item[2]} {res['x1']} {res['y1']} {res['x2']} {res['y2']}\n")
         except Exception as e:  # noqa: BLE001
             _log_error(errors, key, e, debug)
+            continue
+        if profiles is not None and rec["found"]:
+            _write_profile(profiles, errors, key, meas.get(key, RuntimeError("no trail measurement")), debug)
 
 
 def _load_many(ids):
@@ -219,7 +302,7 @@ def _frame_shape(keys):
     return 1489, 2048
 
 
-def process_loaded(results, errors, loaded, params_bright, params_dim, params_removestars):
+def process_loaded(results, errors, loaded, params_bright, params_dim, params_removestars, profiles=None, trail_params=None):
     """process_fields_batched for a chunk the loader has read (``loader.Loaded``): the frames that sit in pinned memory go to
     the GPU as contiguous same-filter slices of that memory with the matching rows of the padded catalogue arrays (no copy
     of a frame on the host, no per-frame Python), the others take the per-frame path; rows and errors entries come out in
@@ -232,6 +315,15 @@ def process_loaded(results, errors, loaded, params_bright, params_dim, params_re
     debug = params_bright.get("debug") or params_dim.get("debug")
     n = len(loaded.keys)
     rows = [None] * n
+    meas = [None] * n                                 # (trail record, profile) or the measurement's exception
+    tp = trail_params or {}
+
+    def measure_one(i, img, cat, flt):
+        if profiles is not None and rows[i]["found"]:
+            try:
+                meas[i] = measure_trail(img, rows[i], cat, flt, params_removestars, **tp)
+            except Exception as e:  # noqa: BLE001
+                meas[i] = e
     by_slot = {}
     for i in range(n):
         if loaded.error[i] is not None:
@@ -255,13 +347,25 @@ def process_loaded(results, errors, loaded, params_bright, params_dim, params_re
             m = max(1, int(cats["count"][a:b].max()))
             packed = {k: _np.ascontiguousarray(v[a:b, :m]) for k, v in cats.items() if k != "count"}
             packed["count"] = cats["count"][a:b]
+            rs = _rs_struct(flt, params_removestars)
             with use_context(h, w, inflight=min(256, len(idx))) as ctx:
                 t_g = time.perf_counter()
                 if loaded.device is not None:                 # decompressed on the GPU and still there
-                    recs = ctx.detect_batch(loaded.device.slice(a, b), params_bright, params_dim, packed, _rs_struct(flt, params_removestars))
+                    recs = ctx.detect_batch(loaded.device.slice(a, b), params_bright, params_dim, packed, rs)
                 else:
-                    recs = ctx.detect_batch(loaded.buffer[a:b], params_bright, params_dim, packed, _rs_struct(flt, params_removestars), pinned=True)
+                    recs = ctx.detect_batch(loaded.buffer[a:b], params_bright, params_dim, packed, rs, pinned=True)
                 t_gpu += time.perf_counter() - t_g
+                if profiles is not None:
+                    try:                                      # device frames: swapped (and blotted) in place by the call above
+                        if loaded.device is not None:
+                            tr, pr = ctx.measure_trails(loaded.device.slice(a, b), recs, packed, rs, native_device=True, **tp)
+                        else:
+                            tr, pr = ctx.measure_trails(loaded.buffer[a:b], recs, packed, rs, pinned=True, **tp)
+                        for j, i in enumerate(idx):
+                            meas[i] = (tr[j], pr[j])
+                    except Exception as e:  # noqa: BLE001 - the slice's measurement failed: each detected frame logs it
+                        for i in idx:
+                            meas[i] = e
             for i, rec in zip(idx, recs):
                 rows[i] = rec
         except Exception:  # noqa: BLE001 - a call-level failure: every frame of the slice on its own, under its own try
@@ -271,6 +375,7 @@ def process_loaded(results, errors, loaded, params_bright, params_dim, params_re
                         raise
                     img = loaded.buffer[sl].astype(_np.float32)
                     rows[i] = process_frame_arrays(img, loaded.cat_of(i), flt, params_bright, params_dim, params_removestars)[2]
+                    measure_one(i, img, loaded.cat_of(i), flt)
                 except Exception as e:  # noqa: BLE001
                     rows[i] = e
     for i in range(n):
@@ -278,6 +383,7 @@ def process_loaded(results, errors, loaded, params_bright, params_dim, params_re
             try:
                 rows[i] = process_frame_arrays(loaded.array[i], loaded.cat_of(i), loaded.keys[i][2], params_bright, params_dim,
                                                params_removestars)[2]
+                measure_one(i, loaded.array[i], loaded.cat_of(i), loaded.keys[i][2])
             except Exception as e:  # noqa: BLE001
                 rows[i] = e
     for i, key in enumerate(loaded.keys):
@@ -297,6 +403,9 @@ def process_loaded(results, errors, loaded, params_bright, params_dim, params_re
                 results.write(f"{head} {res['x1']} {res['y1']} {res['x2']} {res['y2']}\n")
         except Exception as e:  # noqa: BLE001
             _log_error(errors, key, e, debug)
+            continue
+        if profiles is not None and rec["found"]:
+            _write_profile(profiles, errors, key, meas[i] if meas[i] is not None else RuntimeError("no trail measurement"), debug)
     if trace:
         print("[loader]   process_loaded: %.1f ms in all, %.1f ms inside lfdmi_detect_batch_raw" %
               (1e3 * (time.perf_counter() - t_in), 1e3 * t_gpu), flush=True)
@@ -311,6 +420,10 @@ class DetectTrails:
     ``savepath`` choose the output files (appended to), ``debug`` switches all three parameter
     dictionaries to debug mode, ``params_bright`` / ``params_dim`` / ``params_removestars``
     replace the defaults; the dictionaries can also be edited on the instance afterwards.
+    ``trail_profiles=True`` (default off) also measures the trail of every detected frame (``measure_trail``; include/lfdmi.h:
+    trail profiles) and appends its ``profile_row`` to ``profiles`` (default ``<savepath>/profiles.txt``), one row per
+    results.txt row, in the same order; ``trail_params`` (dict) replaces fields of lfdmi_trail_params.  Rank files, resume
+    and ``Jobs`` merging treat profiles.txt as they treat results.txt.
     """
 
     _FILTERS = ('u', 'g', 'r', 'i', 'z')
@@ -322,6 +435,11 @@ class DetectTrails:
         self.params_bright, self.params_dim, self.params_removestars = default_params()
         self.results = kwargs.get("results", os.path.join(save, "results.txt"))
         self.errors = kwargs.get("errors", os.path.join(save, "errors.txt"))
+        self.trail_profiles = bool(kwargs.get("trail_profiles", False))
+        self.profiles = kwargs.get("profiles", os.path.join(save, "profiles.txt"))
+        self.trail_params = dict(kwargs.get("trail_params") or {})
+        if self.trail_profiles:
+            _native.make_trail_params(**self.trail_params)      # (unknown names raise here, not per frame)
         for name in ("params_bright", "params_dim", "params_removestars"):
             if name in kwargs:
                 setattr(self, name, kwargs[name])
@@ -466,8 +584,11 @@ class DetectTrails:
                            "skipped_by_resume": skipped}
         # resume=False starts a new record of marks (an earlier run's marks must never make a later resume skip frames this
         # run did not process); rows and errors are appended to, as in the reference
+        import contextlib
         with open(self.results + suffix, "a") as results, open(self.errors + suffix, "a") as errors, \
-                open(progress_path, "w" if fresh else "a") as progress:
+                open(progress_path, "w" if fresh else "a") as progress, \
+                (open(self.profiles + suffix, "a") if self.trail_profiles else contextlib.nullcontext()) as profiles:
+            prof_kw = {"profiles": profiles, "trail_params": self.trail_params} if self.trail_profiles else {}
             if fresh:
                 progress.write(header + "\n")
                 progress.flush()
@@ -475,12 +596,14 @@ class DetectTrails:
             def mark(done_keys):                     # rows first, then the marks: a crash in between repeats a chunk, never loses one
                 results.flush()
                 errors.flush()
+                if profiles is not None:
+                    profiles.flush()
                 progress.write("".join("%s %s %s %s\n" % tuple(k) for k in done_keys))
                 progress.flush()
 
             if batch <= 1:
                 for key in keys:
-                    process_field(results, errors, *key, self.params_bright, self.params_dim, self.params_removestars)
+                    process_field(results, errors, *key, self.params_bright, self.params_dim, self.params_removestars, **prof_kw)
                     mark([key])
                 self.last_stats["seconds"] = time.perf_counter() - t_start
                 return
@@ -522,7 +645,7 @@ class DetectTrails:
                         # (chunk i sits in buffer i % (depth + 1); the loads in flight fill the other `depth` buffers)
                         if nxt_i < len(chunks):
                             submit()
-                        process_loaded(results, errors, loaded, self.params_bright, self.params_dim, self.params_removestars)
+                        process_loaded(results, errors, loaded, self.params_bright, self.params_dim, self.params_removestars, **prof_kw)
                         mark(chunk)
                         self.last_stats["chunk_done_s"].append(time.perf_counter() - t_start)
                         if trace:

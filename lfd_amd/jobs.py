@@ -46,7 +46,8 @@ def merge_rank_files(path, world_size, remove=False):
 
 class Jobs:
     """``n_workers`` worker processes, one per entry of ``devices`` (default 0 .. n_workers - 1), over the selection the remaining
-    keyword arguments describe to ``DetectTrails`` (run / runs / camcol / filter / field, params_*, savepath, results, errors)."""
+    keyword arguments describe to ``DetectTrails`` (run / runs / camcol / filter / field, params_*, savepath, results, errors,
+    trail_profiles, profiles, trail_params).  With ``trail_profiles=True`` the workers' profiles files are joined like results.txt."""
 
     def __init__(self, n_workers, devices=None, python=None, **detecttrails_kwargs):
         self.n = int(n_workers)
@@ -74,8 +75,9 @@ class Jobs:
         from .detecttrails import DetectTrails
         probe = DetectTrails(**self.kwargs)                          # (validates the selection; gives the output paths)
         results, errors = probe.results, probe.errors
+        joined = [results, errors] + ([probe.profiles] if probe.trail_profiles else [])
         if not resume:
-            for path in (results, errors):                           # the joined files are rewritten by this launch
+            for path in joined:                           # the joined files are rewritten by this launch
                 if self.n > 1 and os.path.exists(path):
                     os.remove(path)
         log_dir = log_dir or os.path.dirname(os.path.abspath(results))
@@ -110,8 +112,8 @@ class Jobs:
         if bad:
             raise RuntimeError(f"workers {bad} failed (exit codes {self.returncodes}); see worker<r>.log in {log_dir}")
         if merge and self.n > 1:
-            merge_rank_files(results, self.n, remove=True)
-            merge_rank_files(errors, self.n, remove=True)
+            for path in joined:
+                merge_rank_files(path, self.n, remove=True)
         return results, errors
 
 
