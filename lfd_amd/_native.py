@@ -693,14 +693,14 @@ class Context:
                                                      int(after_bright), C.byref(p), len(rhos), rh, _ptr(res), loc))
         return res[:, 0] if sq else res
 
-    def detect_batch(self, frames, params_bright, params_dim, cat=None, rs=None, pinned=False):
-        """frames: float32 (n,h,w) numpy or torch-CUDA; returns a structured array of n results.
-
-        numpy frames of dtype '>f4' (the raw data unit of a FITS image) are accepted as they are and byte-swapped on the
-        device.  ``pinned=True``: the array lives in memory from ``PinnedBuffer`` (DMA'd in place, no staging copy)."""
-        if isinstance(frames, DeviceFrames):                  # decompressed on the device (Bz2Decoder.frames): swapped in place there
+    def _frames(self, frames, pinned, what, contiguous=False, native_device=False):
+        """The frames of detect_batch / detect_batch_begin / measure_trails -> (frames, dtype code, n, h, w, loc).
+        ``DeviceFrames`` (decompressed on the device by Bz2Decoder.frames) are big-endian until ``detect_batch`` has swapped
+        them in place (``native_device``); '>f4' numpy frames go as they are; float32 numpy / torch CUDA frames through
+        ``_batch``, which copies a non-contiguous array (``contiguous``: refused instead)."""
+        if isinstance(frames, DeviceFrames):
             n, h, w = frames.shape
-            code = F32_BE
+            code = F32 if native_device else F32_BE
         elif not _is_dev(frames) and isinstance(frames, np.ndarray) and frames.dtype == np.dtype(">f4"):
             if not frames.flags.c_contiguous:
                 raise ValueError("big-endian frames must be C-contiguous")
@@ -708,17 +708,27 @@ class Context:
             n, h, w = (1, *shp) if len(shp) == 2 else shp
             code = F32_BE
         else:
+            if contiguous and not _is_dev(frames) and not (isinstance(frames, np.ndarray) and frames.flags.c_contiguous):
+                raise ValueError("frames of a call in flight must be C-contiguous (they are used, and blotted, in place)")
             frames, n, h, w, sq = self._batch(frames)
             code = _dtype_code(frames)
             if code != F32:
-                raise TypeError("detect_batch needs float32 frames")
+                raise TypeError(f"{what} needs float32 frames")
         if pinned and _is_dev(frames):
             raise ValueError("pinned=True is for host arrays")
+        return frames, code, n, h, w, DEVICE if _is_dev(frames) else (HOST_PINNED if pinned else HOST)
+
+    def detect_batch(self, frames, params_bright, params_dim, cat=None, rs=None, pinned=False):
+        """frames: float32 (n,h,w) numpy or torch-CUDA; returns a structured array of n results.
+
+        numpy frames of dtype '>f4' (the raw data unit of a FITS image) are accepted as they are and byte-swapped on the
+        device, ``DeviceFrames`` swapped in place there.  ``pinned=True``: the array lives in memory from ``PinnedBuffer``
+        (DMA'd in place, no staging copy)."""
+        frames, code, n, h, w, loc = self._frames(frames, pinned, "detect_batch")
         pb, k1 = make_params(params_bright)
         pd, k2 = make_params(params_dim, dim=True)
         c, k3 = self._catalog(cat)
         res = np.zeros(n, RESULT_DTYPE)
-        loc = DEVICE if _is_dev(frames) else (HOST_PINNED if pinned else HOST)
         self._chk(self._lib.lfdmi_detect_batch_raw(self._h, _ptr(frames), code, n, h, w,
                                                    C.byref(c) if c is not None else None,
                                                    C.byref(rs) if rs is not None else None,
@@ -744,29 +754,11 @@ class Context:
         """``detect_batch`` without waiting: returns a ``Pending`` whose ``result()`` is what ``detect_batch`` returns.  Frames
         are device-resident (torch CUDA tensor, ``DeviceFrames``) or, with ``pinned=True``, in ``PinnedBuffer`` memory; they and
         the catalogue must stay untouched until the call has ended (LFDMI_MAX_CALLS_IN_FLIGHT = 2 calls at a time)."""
-        if isinstance(frames, DeviceFrames):
-            n, h, w = frames.shape
-            code = F32_BE
-        elif not _is_dev(frames) and isinstance(frames, np.ndarray) and frames.dtype == np.dtype(">f4"):
-            if not frames.flags.c_contiguous:
-                raise ValueError("big-endian frames must be C-contiguous")
-            shp = frames.shape
-            n, h, w = (1, *shp) if len(shp) == 2 else shp
-            code = F32_BE
-        else:
-            if not _is_dev(frames) and not (isinstance(frames, np.ndarray) and frames.flags.c_contiguous):
-                raise ValueError("frames of a call in flight must be C-contiguous (they are used, and blotted, in place)")
-            frames, n, h, w, sq = self._batch(frames)
-            code = _dtype_code(frames)
-            if code != F32:
-                raise TypeError("detect_batch_begin needs float32 frames")
-        if pinned and _is_dev(frames):
-            raise ValueError("pinned=True is for host arrays")
+        frames, code, n, h, w, loc = self._frames(frames, pinned, "detect_batch_begin", contiguous=True)
         pb, k1 = make_params(params_bright)
         pd, k2 = make_params(params_dim, dim=True)
         c, k3 = self._catalog(cat)
         res = np.zeros(n, RESULT_DTYPE)
-        loc = DEVICE if _is_dev(frames) else (HOST_PINNED if pinned else HOST)
         args = (_ptr(frames), code, n, h, w, C.byref(c) if c is not None else None, C.byref(rs) if rs is not None else None,
                 C.byref(pb), C.byref(pd), _ptr(res), loc)
         return self._begin(self._lib.lfdmi_detect_batch_begin, args, res, [frames, pb, pd, c, rs, k1, k2, k3, cat, args])
@@ -790,22 +782,7 @@ class Context:
         ``process_bright`` / ``_dim`` / ``_multiscale`` with flip=True) return them.  ``DeviceFrames`` hold big-endian data
         until ``detect_batch`` has swapped them in place: ``native_device=True`` after that call.  Returns (TRAIL_DTYPE array
         [n], float32 profiles [n, 2K+1]); frames without a measurement have NaN rows."""
-        if isinstance(frames, DeviceFrames):
-            n, h, w = frames.shape
-            code = F32 if native_device else F32_BE
-        elif not _is_dev(frames) and isinstance(frames, np.ndarray) and frames.dtype == np.dtype(">f4"):
-            if not frames.flags.c_contiguous:
-                raise ValueError("big-endian frames must be C-contiguous")
-            shp = frames.shape
-            n, h, w = (1, *shp) if len(shp) == 2 else shp
-            code = F32_BE
-        else:
-            frames, n, h, w, sq = self._batch(frames)
-            code = _dtype_code(frames)
-            if code != F32:
-                raise TypeError("measure_trails needs float32 frames")
-        if pinned and _is_dev(frames):
-            raise ValueError("pinned=True is for host arrays")
+        frames, code, n, h, w, loc = self._frames(frames, pinned, "measure_trails", native_device=native_device)
         rec = np.ascontiguousarray(records, RESULT_DTYPE).reshape(-1)
         if len(rec) != n:
             raise ValueError(f"{len(rec)} records for {n} frames")
@@ -813,7 +790,6 @@ class Context:
         c, keep = self._catalog(cat)
         out = np.zeros(n, TRAIL_DTYPE)
         prof = np.empty((n, trail_bins(p)), np.float32)
-        loc = DEVICE if _is_dev(frames) else (HOST_PINNED if pinned else HOST)
         self._chk(self._lib.lfdmi_measure_trails(self._h, _ptr(frames), code, n, h, w, loc, _ptr(rec),
                                                  C.byref(c) if c is not None else None, C.byref(rs) if rs is not None else None,
                                                  C.byref(p), _ptr(out), _ptr(prof)))

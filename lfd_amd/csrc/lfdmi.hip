@@ -65,7 +65,7 @@ struct PendingCall {
     void *frames = nullptr;            // frames / image as the caller passed them
     size_t frame_bytes = 0;            // bytes of the whole batch (overlap check)
     int dtype = 0, n = 0, h = 0, w = 0, loc = 0;
-    bool be = false, host_blot = false;
+    bool host_blot = false;
     lfdmi_catalog cat{};
     bool has_cat = false, has_rs = false;
     lfdmi_rs_params rs{};
@@ -793,7 +793,10 @@ static int check_shape(lfdmi_ctx *ctx, int n, int h, int w) {
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, LFDMI_ERR_HIP, "hipSetDevice");
     (void)hipGetLastError(); // a failed earlier call must not poison this one
     ctx->last_h = h; ctx->last_w = w;
-    ctx->stages_valid = true; // (the pass-level entry points overwrite this with what they keep)
+    // every call starts from the stand-alone operators' settings; the pass-level entry points set their own per call / chunk
+    // (so a call that failed half way leaves nothing behind)
+    ctx->stages_valid = ctx->keep_equ = ctx->general_on = true;
+    ctx->cur_pass = 0;
     return 0;
 }
 
@@ -1311,6 +1314,21 @@ static bool hough_fits(const lfdmi_ctx *ctx, int h, int w, double rho_d, double 
     return na > 0 && nr > 0 && na <= MAX_ANGLES && (size_t)(na + 2) * (nr + 2) <= ctx->acc_cap && (ctx->worst ? (size_t)na * nr <= ctx->peak_cap : true);
 }
 
+// the workspace that takes a call whose HoughLines run at rhos[0 .. n_rhos) and theta: this one, or -- a rho finer than its
+// accumulators hold -- the worst-case one (get_spill)
+static int call_workspace(lfdmi_ctx *ctx, int h, int w, const double *rhos, int n_rhos, double theta, lfdmi_ctx **ws) {
+    auto fits = [&](const lfdmi_ctx *c) {
+        for (int s = 0; s < n_rhos; s++)
+            if (!hough_fits(c, h, w, rhos[s], theta)) return false;
+        return true;
+    };
+    *ws = ctx;
+    if (fits(ctx)) return 0;
+    *ws = get_spill(ctx);
+    if (*ws && fits(*ws)) return 0;
+    return fail(ctx, LFDMI_ERR_CAPACITY, "Hough accumulator larger than the workspace (rho < 1 px or theta < 1 deg)");
+}
+
 static int ensure_tables(lfdmi_ctx *ctx, int h, int w, double rho_d, double theta_d) {
     for (int i = 0; i < LFDMI_MAX_SCALES; i++) {
         auto &t = ctx->tabs[i];
@@ -1822,11 +1840,12 @@ static int hough_api(lfdmi_ctx *ctx, const uint8_t *img, int n, int h, int w, do
                      int max_lines, float *lines, int32_t *n_lines, int32_t *accum, int loc) {
     RET(check_shape(ctx, n, h, w));
     if (!img) return fail(ctx, LFDMI_ERR_ARG, "NULL image");
-    if (!hough_fits(ctx, h, w, rho, theta) && !ctx->worst) { // finer than this workspace's accumulators: the worst-case one takes the call
-        lfdmi_ctx *sp = get_spill(ctx);
-        if (!sp) return fail(ctx, LFDMI_ERR_CAPACITY, "Hough accumulator larger than the workspace");
-        int rc = hough_api(sp, img, n, h, w, rho, theta, threshold, max_lines, lines, n_lines, accum, loc);
-        if (rc) ctx->err = sp->err;
+    if (!((float)rho > 0) || !((float)theta > 0)) return fail(ctx, LFDMI_ERR_ARG, "rho and theta must be positive");
+    lfdmi_ctx *ws;
+    RET(call_workspace(ctx, h, w, &rho, 1, theta, &ws));
+    if (ws != ctx) {
+        int rc = hough_api(ws, img, n, h, w, rho, theta, threshold, max_lines, lines, n_lines, accum, loc);
+        if (rc) ctx->err = ws->err;
         return rc;
     }
     RET(ensure_tables(ctx, h, w, rho, theta));
@@ -1932,7 +1951,7 @@ static int stage_catalog(lfdmi_ctx *ctx, const lfdmi_catalog *cat, int f0, int n
 }
 
 static int run_removestars(lfdmi_ctx *ctx, float *frames_dev, int f0, int nc, int h, int w, const lfdmi_catalog *cat,
-                           const lfdmi_rs_params *rs, std::vector<int4> *host_boxes = nullptr, bool fill = true) {
+                           const lfdmi_rs_params *rs, bool fill = true) {
     if (!cat || cat->max_obj <= 0) return 0;
     if (!rs || rs->filter_index < 0 || rs->filter_index > 4) return fail(ctx, LFDMI_ERR_ARG, "removestars params");
     lfdmi_catalog dev;
@@ -1961,7 +1980,6 @@ static int run_removestars(lfdmi_ctx *ctx, float *frames_dev, int f0, int nc, in
         ctx->rs_hmax = 2 * std::max(rs->maxxy, rs->defaultxy); // a square's side: 2 dxy, dxy <= maxxy or the default
     }
     int4 *boxes = ctx->rs_boxes;
-    if (host_boxes) host_boxes->resize(need); // the blotted squares come back instead of the blotted frames
     {
         Span sp(ctx, KID_REMOVESTARS);
         k_rs_boxes<<<dim3((cat->max_obj + 255) / 256, nc), 256, 0, ctx->stream>>>(h, w, cat->max_obj, dev.count, dev.rowc, dev.colc, dev.psfmag,
@@ -1982,8 +2000,6 @@ static int run_removestars(lfdmi_ctx *ctx, float *frames_dev, int f0, int nc, in
             KCHK("k_rs_fill");
         }
     }
-    if (host_boxes)
-        HIPCHK(hipMemcpyAsync(host_boxes->data(), boxes, host_boxes->size() * sizeof(int4), hipMemcpyDeviceToHost, ctx->stream));
     return 0;
 }
 
@@ -2033,13 +2049,6 @@ extern "C" int lfdmi_remove_stars(lfdmi_ctx *ctx, float *img, int n, int h, int 
 // Whole-pass entry points launch the general run kernels only once the context has met a frame the per-frame
 // LDS kernels could not take; a chunk that meets the first such frame is run again with them.
 #define GENERAL_QUIET_CHUNKS 8
-static bool general_again(lfdmi_ctx *c, bool on, const int *flags, int n);
-struct GeneralGuard {
-    lfdmi_ctx *c;
-    explicit GeneralGuard(lfdmi_ctx *ctx) : c(ctx) { c->general_on = !c->frame_ccl || c->general_seen; }
-    ~GeneralGuard() { c->general_on = true; }
-    bool again(const int *flags, int n) { return general_again(c, c->general_on, flags, n); }
-};
 // on: the chunk ran with the general run kernels; true: run it again with them
 static bool general_again(lfdmi_ctx *c, bool on, const int *flags, int n) {
     bool need = false;
@@ -2059,8 +2068,25 @@ static bool general_again(lfdmi_ctx *c, bool on, const int *flags, int n) {
     return true;
 }
 
-// results[s * rstride + i]: frame i at Hough scale s (rhos == nullptr: one scale, p->houghMethod)
-struct KeepEqu { lfdmi_ctx *c; bool old; KeepEqu(lfdmi_ctx *c_, bool v) : c(c_), old(c_->keep_equ) { c->keep_equ = v; } ~KeepEqu() { c->keep_equ = old; } };
+// a chunk about to be enqueued: what it runs with (ctx->general_on follows it), for the verdict on it once its flags and
+// records have landed -- at once (synchronous calls) or at lfdmi_end_oldest (calls in flight)
+static CallChunk chunk_start(lfdmi_ctx *ctx, int c0, int nc) {
+    ctx->general_on = !ctx->frame_ccl || ctx->general_seen;
+    return CallChunk{c0, nc, ctx->general_on, ctx->scan_fused, ctx->n_cap_growths};
+}
+
+// true: run the chunk again.  The look-back scan gave up on a frame (three launches from now on: see scan_gave_up), else a frame
+// overflowed tables that have grown since the chunk was enqueued or that grow now (may_grow), else a frame needs the general run
+// kernels.  rec[s * rstride + i]: frame i's record at Hough scale s.
+static bool chunk_again(lfdmi_ctx *ctx, const CallChunk &ch, const int *flags, const lfdmi_result *rec, size_t rstride, int n_scales,
+                        bool may_grow) {
+    if (scan_gave_up(ctx, flags, ch.nc, ch.scan_fused)) return true;
+    bool over = false;
+    for (int s = 0; s < n_scales; s++)
+        for (int i = 0; i < ch.nc; i++) over = over || rec[s * rstride + i].status == LFDMI_ERR_CAPACITY;
+    if (over && (ctx->n_cap_growths > ch.growths || (may_grow && grow_caps(ctx, rec, ch.nc, rstride, n_scales)))) return true;
+    return general_again(ctx, ch.general_on, flags, ch.nc);
+}
 
 // one chunk of a pass, enqueued: its records (rec_h[s * hstride + i]), flags and (hl != nullptr) line sets are copied to the
 // host in stream order
@@ -2124,45 +2150,49 @@ static int finish_pass_frames(lfdmi_ctx *ctx, const void *img, int dtype, int c0
     return 0;
 }
 
-static int pass_api(lfdmi_ctx *ctx, const void *img, int dtype, int n, int h, int w, int flip, int prep_mode, bool dim,
-                    const lfdmi_params *p, int n_scales, const double *rhos, lfdmi_result *results, size_t rstride, float *lines_equ,
-                    float *lines_box, int loc) {
+// what every pass call (lfdmi_process_* and lfdmi_process_multiscale_begin) does first: its checks, then the workspace that takes
+// it (*ws; rhos == nullptr: p->houghMethod); in this one, the 8-bit stage images for lfdmi_get_stage are kept unless switched
+// off (batches)
+static int pass_prologue(lfdmi_ctx *ctx, const void *img, int dtype, int n, int h, int w, bool dim, const lfdmi_params *p, int n_scales,
+                         const double *rhos, const lfdmi_result *results, lfdmi_ctx **ws) {
     RET(check_shape(ctx, n, h, w));
     RET(check_params(ctx, p, dim));
     if (!img || !results || dtype < 0 || dtype > 2) return fail(ctx, LFDMI_ERR_ARG, "bad argument");
     if (n_scales < 1 || n_scales > LFDMI_MAX_SCALES) return fail(ctx, LFDMI_ERR_ARG, "n_scales out of range");
     if (dtype == LFDMI_U8 && dim) return fail(ctx, LFDMI_ERR_DTYPE, "dim pass needs a float image (numpy refuses uint8 += float)");
-    const double rho1 = p->houghMethod;
-    if (!rhos) rhos = &rho1;
-    for (int s = 0; s < n_scales; s++)
-        if (!hough_fits(ctx, h, w, rhos[s], LFD_PI / 180)) { // finer than this workspace's accumulators: the worst-case one takes the call
-            lfdmi_ctx *sp = get_spill(ctx);
-            if (!sp || !hough_fits(sp, h, w, rhos[s], LFD_PI / 180)) return fail(ctx, LFDMI_ERR_CAPACITY, "Hough accumulator larger than the workspace (rho < 1 px)");
-            int rc = pass_api(sp, img, dtype, n, h, w, flip, prep_mode, dim, p, n_scales, rhos, results, rstride, lines_equ, lines_box, loc);
-            if (rc) ctx->err = sp->err;
-            return rc;
-        }
+    RET(call_workspace(ctx, h, w, rhos ? rhos : &p->houghMethod, n_scales, LFD_PI / 180, ws));
+    if (*ws == ctx) ctx->keep_equ = ctx->stages_valid = ctx->stage_mode != 0;
+    return 0;
+}
+
+// results[s * rstride + i]: frame i at Hough scale s (rhos == nullptr: one scale, p->houghMethod)
+static int pass_api(lfdmi_ctx *ctx, const void *img, int dtype, int n, int h, int w, int flip, int prep_mode, bool dim,
+                    const lfdmi_params *p, int n_scales, const double *rhos, lfdmi_result *results, size_t rstride, float *lines_equ,
+                    float *lines_box, int loc) {
+    lfdmi_ctx *ws;
+    RET(pass_prologue(ctx, img, dtype, n, h, w, dim, p, n_scales, rhos, results, &ws));
+    if (!rhos) rhos = &p->houghMethod;
+    if (ws != ctx) {
+        int rc = pass_api(ws, img, dtype, n, h, w, flip, prep_mode, dim, p, n_scales, rhos, results, rstride, lines_equ, lines_box, loc);
+        if (rc) ctx->err = ws->err;
+        return rc;
+    }
     size_t N = (size_t)h * w, es = dtype_size(dtype);
     int K = p->nlinesInSet;
     const size_t G = (size_t)ctx->G;
-    KeepEqu keep_guard(ctx, ctx->stage_mode != 0); // the 8-bit stage images for lfdmi_get_stage unless switched off (batches)
-    ctx->stages_valid = ctx->keep_equ;
     std::vector<lfdmi_result> host(G * n_scales);
     std::vector<float> hl(G * 2 * K * 2);
     std::vector<int> flags(G);
-    ctx->cur_pass = 0;
     for (int c0 = 0; c0 < n; c0 += ctx->G) {
         int nc = n - c0 < ctx->G ? n - c0 : ctx->G;
         const void *d;
         RET(in_ptr(ctx, img, (size_t)c0 * N * es, (size_t)nc * N * es, loc, &d));
-        GeneralGuard gg(ctx);
-        int grow_tries = 0;
-        for (;;) { // (again, with the general run kernels, if a frame turned out to need them)
+        for (int grow_tries = 0;;) { // (again after the scan's give-up, table growth -- at most four times -- or with the general run kernels)
+            const CallChunk ch = chunk_start(ctx, c0, nc);
             RET(enqueue_pass_chunk(ctx, d, dtype, nc, h, w, flip, prep_mode, dim, p, n_scales, rhos, host.data(), G, flags.data(), hl.data()));
             HIPCHK(hipStreamSynchronize(ctx->stream));
-            if (scan_gave_up(ctx, flags.data(), nc)) continue; // (see lfdmi_detect_batch)
-            if (grow_tries < 4 && grow_caps(ctx, host.data(), nc, G, n_scales)) { grow_tries++; continue; } // tables enlarged: once more
-            if (!gg.again(flags.data(), nc)) break;
+            if (!chunk_again(ctx, ch, flags.data(), host.data(), G, n_scales, grow_tries < 4)) break;
+            grow_tries += ctx->n_cap_growths > ch.growths;
         }
         chunk_done(ctx);
         {
@@ -2467,8 +2497,8 @@ static int detect_impl(lfdmi_ctx *ctx, void *frames_v, int dtype, int n, int h, 
 
 // the records of a finished chunk of lfdmi_detect_batch (frames c0 .. c0 + nc) into results: frames whose tables overflowed are
 // run again, alone, in the worst-case workspace (remove_stars has already blotted them -- device copy and caller's array -- so
-// without the catalogue, except big-endian frames: a read-only input, what the rerun uploads is not blotted); the rest are
-// dictified.  loc: LFDMI_HOST for pinned frames, as detect_impl treats them.
+// without the catalogue, except big-endian frames: a read-only input, what the rerun uploads is not blotted; pinned frames as
+// host frames); the rest are dictified.
 static int finish_detect_frames(lfdmi_ctx *ctx, float *frames, int dtype, int c0, int nc, int h, int w, const lfdmi_catalog *cat,
                                 const lfdmi_rs_params *rs, const lfdmi_params *bright, const lfdmi_params *dim, lfdmi_result *host,
                                 lfdmi_result *results, int loc, int cat_f0, std::thread *blotter) {
@@ -2480,7 +2510,7 @@ static int finish_detect_frames(lfdmi_ctx *ctx, float *frames, int dtype, int c0
             if (sp) {
                 if (blotter && blotter->joinable()) blotter->join(); // (a host frame is read again below: its blotting must be complete)
                 int rc = detect_impl(sp, frames + (size_t)(c0 + i) * N, dtype, 1, h, w, be ? cat : nullptr, be ? rs : nullptr, bright, dim,
-                                     &results[c0 + i], loc, cat_f0 + c0 + i);
+                                     &results[c0 + i], loc == LFDMI_HOST_PINNED ? LFDMI_HOST : loc, cat_f0 + c0 + i);
                 if (rc) { ctx->err = sp->err; return rc; }
                 ctx->n_spilled++;
                 continue;
@@ -2536,47 +2566,87 @@ struct FoldState { // (an error return in the middle of a chunk must not leave t
     }
 };
 
-static int detect_impl(lfdmi_ctx *ctx, void *frames_v, int dtype, int n, int h, int w, const lfdmi_catalog *cat,
-                       const lfdmi_rs_params *rs, const lfdmi_params *bright, const lfdmi_params *dim,
-                       lfdmi_result *results, int loc, int cat_f0) { // cat_f0: catalogue entry of frame 0 (a frame run again alone)
+// what every detect call (lfdmi_detect_batch / _raw / _begin) does first: its checks, then the workspace that takes it (*ws).
+// Only then, in this one, are big-endian frames already on the device (decoded there: lfdmi_bz2_*) swapped in place, once for the
+// whole batch -- a chunk that is run again must not be swapped again -- and native from here on (*dtype); the worst-case
+// workspace, when it takes the call, swaps them itself.  Last, the stage images the call keeps and its dim pass's front end.
+static int detect_prologue(lfdmi_ctx *ctx, const char *fn, void *frames, int *dtype, int n, int h, int w, const lfdmi_catalog *cat,
+                           const lfdmi_rs_params *rs, const lfdmi_params *bright, const lfdmi_params *dim, const lfdmi_result *results,
+                           int loc, lfdmi_ctx **ws, bool *dual, bool *delta) {
     RET(check_shape(ctx, n, h, w));
     RET(check_params(ctx, bright, false));
     RET(check_params(ctx, dim, true));
-    float *frames = (float *)frames_v;
     if (!frames || !results) return fail(ctx, LFDMI_ERR_ARG, "NULL argument");
-    if (dtype != LFDMI_F32 && dtype != LFDMI_F32_BE) return fail(ctx, LFDMI_ERR_DTYPE, "lfdmi_detect_batch_raw: frames must be LFDMI_F32 or LFDMI_F32_BE");
+    if (*dtype != LFDMI_F32 && *dtype != LFDMI_F32_BE) return fail(ctx, LFDMI_ERR_DTYPE, std::string(fn) + ": frames must be LFDMI_F32 or LFDMI_F32_BE");
     if (loc != LFDMI_HOST && loc != LFDMI_DEVICE && loc != LFDMI_HOST_PINNED) return fail(ctx, LFDMI_ERR_ARG, "bad loc");
-    if (dtype == LFDMI_F32_BE && loc == LFDMI_DEVICE) {
-        // big-endian frames already on the device (decoded there: lfdmi_bz2_*): swapped in place, once -- a chunk that is run again
-        // (table growth, general path) must not be swapped again -- and native from here on
-        HIPCHK(hipSetDevice(ctx->device));
+    if (cat && cat->max_obj > 0 && (!rs || rs->filter_index < 0 || rs->filter_index > 4)) return fail(ctx, LFDMI_ERR_ARG, "removestars params");
+    const double rhos[2] = {bright->houghMethod, dim->houghMethod};
+    RET(call_workspace(ctx, h, w, rhos, 2, LFD_PI / 180, ws));
+    if (*ws != ctx) return 0;
+    if (*dtype == LFDMI_F32_BE && loc == LFDMI_DEVICE) {
         RET(run_bswap(ctx, frames, (size_t)n * h * w * 4));
-        dtype = LFDMI_F32;
+        *dtype = LFDMI_F32;
     }
-    const bool be = dtype == LFDMI_F32_BE;
-    const bool pinned = loc == LFDMI_HOST_PINNED;
-    if (pinned) loc = LFDMI_HOST; // (everything below but the upload treats them as host frames)
-    if (!hough_fits(ctx, h, w, bright->houghMethod, LFD_PI / 180) || !hough_fits(ctx, h, w, dim->houghMethod, LFD_PI / 180)) {
-        lfdmi_ctx *sp = get_spill(ctx); // rho finer than this workspace's accumulators: the worst-case one takes the call
-        if (!sp || !hough_fits(sp, h, w, bright->houghMethod, LFD_PI / 180) || !hough_fits(sp, h, w, dim->houghMethod, LFD_PI / 180))
-            return fail(ctx, LFDMI_ERR_CAPACITY, "Hough accumulator larger than the workspace (rho < 1 px)");
-        int rc = detect_impl(sp, frames, dtype, n, h, w, cat, rs, bright, dim, results, pinned ? LFDMI_HOST_PINNED : loc, cat_f0);
-        if (rc) ctx->err = sp->err;
+    ctx->keep_equ = ctx->stages_valid = ctx->stage_mode == 1; // (before the front-end choice, which depends on it)
+    dim_front_end(ctx, w, dim, dual, delta);
+    return 0;
+}
+
+// remove_stars' squares go back to the host, where the caller's array is blotted with them: a host catalogue for native frames on
+// the host (pageable or pinned).  Raw big-endian frames are a file's data unit, a read-only input: only the device copy is
+// blotted -- no squares come back, no mid-call synchronisation, no host threads.
+static bool blot_on_host(const lfdmi_catalog *cat, bool on_host, int dtype) {
+    return cat && on_host && cat->loc == LFDMI_HOST && dtype != LFDMI_F32_BE;
+}
+
+// the front matter of one detect chunk on its device copy d (frames c0 .. c0 + nc; on_host: the caller's frames are on the host,
+// pageable or pinned): a staged big-endian copy is swapped, remove_stars is enqueued, and for blot_on_host its squares are copied
+// to squares[nc x max_obj] in stream order.
+static int enqueue_detect_front(lfdmi_ctx *ctx, float *frames, const void *d, int dtype, bool on_host, int c0, int nc, int h, int w,
+                                const lfdmi_catalog *cat, const lfdmi_rs_params *rs, int cat_f0, bool delta, int4 *squares) {
+    const size_t N = (size_t)h * w;
+    const bool be = dtype == LFDMI_F32_BE, host_blot = blot_on_host(cat, on_host, dtype);
+    if (be) RET(run_bswap(ctx, (void *)d, (size_t)nc * N * 4));
+    // The bit-plane sweep can mask remove_stars' squares as it loads the values (k_prep_hist<.., RS>), so nothing waits for the
+    // zero fill: a host frame's device copy is never filled at all (the caller's array is blotted by host threads, a big-endian
+    // frame is read-only), a device-resident frame -- which the caller does get back blotted -- is filled on a side stream
+    // beside the latency-bound stages of the bright pass (rs_fill_point).  Frames whose blotted copy travels back over PCIe
+    // (catalogue on the device, frames on the host) keep the fill in front.
+    const bool copy_back = cat && on_host && !host_blot && !be;
+    ctx->rs_fold = cat && cat->max_obj > 0 && ctx->rs_fold_on && delta && w <= RS_MAXW && !copy_back;
+    ctx->rs_fill_frames = nullptr;
+    if (!cat) return 0;
+    RET(run_removestars(ctx, (float *)d, cat_f0 + c0, nc, h, w, cat, rs, !ctx->rs_fold));
+    if (ctx->rs_fold && !on_host) { ctx->rs_fill_frames = (float *)d; ctx->rs_fill_part = 0; ctx->rs_fill_nc = nc; ctx->rs_fill_h = h; ctx->rs_fill_w = w; }
+    if (copy_back) RET(out_copy(ctx, frames, (size_t)c0 * N * 4, d, (size_t)nc * N * 4, LFDMI_HOST));
+    if (host_blot && cat->max_obj > 0)
+        HIPCHK(hipMemcpyAsync(squares, ctx->rs_boxes, (size_t)nc * cat->max_obj * sizeof(int4), hipMemcpyDeviceToHost, ctx->stream));
+    return 0;
+}
+
+static int detect_impl(lfdmi_ctx *ctx, void *frames_v, int dtype, int n, int h, int w, const lfdmi_catalog *cat,
+                       const lfdmi_rs_params *rs, const lfdmi_params *bright, const lfdmi_params *dim,
+                       lfdmi_result *results, int loc, int cat_f0) { // cat_f0: catalogue entry of frame 0 (a frame run again alone)
+    float *frames = (float *)frames_v;
+    lfdmi_ctx *ws;
+    bool dual, delta;
+    RET(detect_prologue(ctx, "lfdmi_detect_batch_raw", frames, &dtype, n, h, w, cat, rs, bright, dim, results, loc, &ws, &dual, &delta));
+    if (ws != ctx) {
+        int rc = detect_impl(ws, frames, dtype, n, h, w, cat, rs, bright, dim, results, loc, cat_f0);
+        if (rc) ctx->err = ws->err;
         return rc;
     }
+    const bool pinned = loc == LFDMI_HOST_PINNED, on_host = loc != LFDMI_DEVICE;
+    const bool host_blot = blot_on_host(cat, on_host, dtype);
     size_t N = (size_t)h * w;
     int *const flags = (int *)ctx->res_host;
     lfdmi_result *const host = (lfdmi_result *)((char *)ctx->res_host + (size_t)ctx->G * sizeof(int));
     std::vector<int4> boxes;
-    KeepEqu keep_guard(ctx, ctx->stage_mode == 1);
-    ctx->stages_valid = ctx->keep_equ;
-    bool dual, delta;
-    dim_front_end(ctx, w, dim, &dual, &delta);
     // Host frames: chunks of up to ~feed_chunk_bytes (and at most G frames) go through the pinned double buffer
     // (feed_* above), chunk k+1 uploading while chunk k is processed.  Device frames (LFDMI_FEED_MB=0, tiny batches):
     // chunks of G frames, used in place / staged by the runtime.
     int per = ctx->G;
-    const bool feed = !pinned && loc == LFDMI_HOST && ctx->feed_chunk_bytes > 0 && (size_t)n * N * 4 >= (64u << 20);
+    const bool feed = loc == LFDMI_HOST && ctx->feed_chunk_bytes > 0 && (size_t)n * N * 4 >= (64u << 20);
     if (feed || pinned) {
         per = feed_chunk_frames(ctx, n, N, pinned);
         RET(feed_prepare(ctx, (size_t)std::min(per, n) * N * 4, feed));
@@ -2612,49 +2682,29 @@ static int detect_impl(lfdmi_ctx *ctx, void *frames_v, int dtype, int n, int h, 
                 RET(pinned_upload(ctx, (const char *)frames + (size_t)(c0 + per) * N * 4, (size_t)std::min(per, n - c0 - per) * N * 4, kc + 1));
             HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->feed_up[kc & 1], 0));
         } else RET(in_ptr(ctx, frames, (size_t)c0 * N * 4, (size_t)nc * N * 4, loc, &d));
-        if (be) RET(run_bswap(ctx, (void *)d, (size_t)nc * N * 4));
-        // (raw big-endian frames are a file's data unit, a read-only input: only the device copy is blotted -- no squares come
-        // back, no mid-call synchronisation, no host threads)
-        const bool host_blot = cat && loc == LFDMI_HOST && cat->loc == LFDMI_HOST && !be;
-        // The bit-plane sweep can mask remove_stars' squares as it loads the values (k_prep_hist<.., RS>), so nothing waits for the
-        // zero fill: a host frame's device copy is never filled at all (the caller's array is blotted by host threads, a big-endian
-        // frame is read-only), a device-resident frame -- which the caller does get back blotted -- is filled on a side stream
-        // beside the latency-bound stages of the bright pass (rs_fill_point).  Frames whose blotted copy travels back over PCIe
-        // (catalogue on the device, frames on the host) keep the fill in front.
-        const bool copy_back = cat && loc == LFDMI_HOST && !host_blot && !be;
-        ctx->rs_fold = cat && cat->max_obj > 0 && ctx->rs_fold_on && delta && w <= RS_MAXW && !copy_back;
-        ctx->rs_fill_frames = nullptr;
         FoldState fold_guard{ctx};
-        if (cat) {
-            RET(run_removestars(ctx, (float *)d, cat_f0 + c0, nc, h, w, cat, rs, host_blot ? &boxes : nullptr, !ctx->rs_fold));
-            if (ctx->rs_fold && loc == LFDMI_DEVICE) { ctx->rs_fill_frames = (float *)d; ctx->rs_fill_part = 0; ctx->rs_fill_nc = nc; ctx->rs_fill_h = h; ctx->rs_fill_w = w; }
-            if (copy_back) RET(out_copy(ctx, frames, (size_t)c0 * N * 4, d, (size_t)nc * N * 4, loc));
-            if (host_blot) {
-                double t0_ = feed && getenv("LFDMI_FEED_TRACE") ? feed_now() : 0;
-                HIPCHK(hipStreamSynchronize(ctx->stream)); // the squares are on the host; the passes are enqueued next
-                if (t0_ > 0) fprintf(stderr, "[feed] chunk %d: upload + remove_stars synced after %.2f ms (t=%.2f)\n", kc, feed_now() - t0_, feed_now());
-            }
+        if (host_blot) boxes.resize((size_t)nc * std::max(0, cat->max_obj));
+        RET(enqueue_detect_front(ctx, frames, d, dtype, on_host, c0, nc, h, w, cat, rs, cat_f0, delta, boxes.data()));
+        if (host_blot) {
+            double t0_ = feed && getenv("LFDMI_FEED_TRACE") ? feed_now() : 0;
+            HIPCHK(hipStreamSynchronize(ctx->stream)); // the squares are on the host; the passes are enqueued next
+            if (t0_ > 0) fprintf(stderr, "[feed] chunk %d: upload + remove_stars synced after %.2f ms (t=%.2f)\n", kc, feed_now() - t0_, feed_now());
         }
         bool blotted = false;
-        GeneralGuard gg(ctx);
-        int grow_tries = 0;
-        for (;;) { // (again, with the general run kernels, if a frame turned out to need them)
-        RET(enqueue_detect_passes(ctx, d, nc, h, w, bright, dim, dual, delta));
-        if (host_blot && !blotted) { // host threads zero-fill the caller's frames in the background (joined below / at the end)
-            if (blotter.joinable()) blotter.join();
-            blotter = std::thread([=, bx = boxes, cpus = ctx->feed_cpus] { blot_host_frames(frames + (size_t)c0 * N, nc, h, w, cat, cat_f0 + c0, bx.data(), cpus); });
-            blotted = true;
-        }
-        HIPCHK(hipMemcpyAsync(ctx->res_host, ctx->pass_flags, (size_t)ctx->G * sizeof(int) + (size_t)nc * sizeof(lfdmi_result), hipMemcpyDeviceToHost, ctx->stream));
-        { double t0_ = feed && getenv("LFDMI_FEED_TRACE") ? feed_now() : 0;
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        if (t0_ > 0) fprintf(stderr, "[feed] chunk %d (%d frames): passes synced after %.2f ms (t=%.2f)\n", kc, nc, feed_now() - t0_, feed_now()); }
-        { // the look-back scan gave up on a frame (the GPU is shared with another process: see k_scan_fused): three launches from
-          // now on, and this chunk once more (cheaper than the worst-case rerun of every frame that was flagged)
-            if (scan_gave_up(ctx, flags, nc)) continue;
-        }
-        if (grow_tries < 4 && grow_caps(ctx, host, nc)) { grow_tries++; continue; } // tables enlarged for this chunk's frames: once more
-        if (!gg.again(flags, nc)) break;
+        for (int grow_tries = 0;;) { // (again after the scan's give-up, table growth -- at most four times -- or with the general run kernels)
+            const CallChunk ch = chunk_start(ctx, c0, nc);
+            RET(enqueue_detect_passes(ctx, d, nc, h, w, bright, dim, dual, delta));
+            if (host_blot && !blotted) { // host threads zero-fill the caller's frames in the background (joined below / at the end)
+                if (blotter.joinable()) blotter.join();
+                blotter = std::thread([=, bx = boxes, cpus = ctx->feed_cpus] { blot_host_frames(frames + (size_t)c0 * N, nc, h, w, cat, cat_f0 + c0, bx.data(), cpus); });
+                blotted = true;
+            }
+            HIPCHK(hipMemcpyAsync(ctx->res_host, ctx->pass_flags, (size_t)ctx->G * sizeof(int) + (size_t)nc * sizeof(lfdmi_result), hipMemcpyDeviceToHost, ctx->stream));
+            double t0_ = feed && getenv("LFDMI_FEED_TRACE") ? feed_now() : 0;
+            HIPCHK(hipStreamSynchronize(ctx->stream));
+            if (t0_ > 0) fprintf(stderr, "[feed] chunk %d (%d frames): passes synced after %.2f ms (t=%.2f)\n", kc, nc, feed_now() - t0_, feed_now());
+            if (!chunk_again(ctx, ch, flags, host, 1, 1, grow_tries < 4)) break;
+            grow_tries += ctx->n_cap_growths > ch.growths;
         }
         chunk_done(ctx);
         {
@@ -2759,7 +2809,6 @@ struct BeginAbort {
     lfdmi_ctx *c;
     bool armed = true;
     ~BeginAbort() {
-        c->general_on = true;
         if (!armed) return;
         (void)hipStreamSynchronize(c->stream);
         for (hipStream_t st : {c->feed_copy, c->feed_copy2, c->side[0], c->side[1]})
@@ -2792,16 +2841,20 @@ extern "C" int lfdmi_detect_batch_begin(lfdmi_ctx *ctx, void *frames, int dtype,
     const size_t N = h > 0 && w > 0 ? (size_t)h * w : 0;
     RET(begin_check(ctx, frames, n > 0 ? (size_t)n * N * 4 : 0, loc, false));
     Internal internal(ctx);
-    RET(check_shape(ctx, n, h, w));
-    RET(check_params(ctx, bright, false));
-    RET(check_params(ctx, dim, true));
-    if (!frames || !results) return fail(ctx, LFDMI_ERR_ARG, "NULL argument");
-    if (dtype != LFDMI_F32 && dtype != LFDMI_F32_BE) return fail(ctx, LFDMI_ERR_DTYPE, "lfdmi_detect_batch_begin: frames must be LFDMI_F32 or LFDMI_F32_BE");
-    if (cat && cat->max_obj > 0 && (!rs || rs->filter_index < 0 || rs->filter_index > 4)) return fail(ctx, LFDMI_ERR_ARG, "removestars params");
+    lfdmi_ctx *ws;
+    bool dual, delta;
+    RET(detect_prologue(ctx, "lfdmi_detect_batch_begin", frames, &dtype, n, h, w, cat, rs, bright, dim, results, loc, &ws, &dual, &delta));
     PendingCall &pc = next_call(ctx);
     pc.kind = 0;
     pc.frames = frames; pc.frame_bytes = (size_t)n * N * 4;
-    pc.n = n; pc.h = h; pc.w = w; pc.loc = loc;
+    if (ws != ctx) { // the worst-case workspace takes the call, here and now
+        int rc = detect_impl(ws, frames, dtype, n, h, w, cat, rs, bright, dim, results, loc);
+        if (rc) { ctx->err = ws->err; return rc; }
+        pc.finished = true;
+        ctx->n_calls++;
+        return 0;
+    }
+    pc.dtype = dtype; pc.n = n; pc.h = h; pc.w = w; pc.loc = loc;
     pc.results = results;
     pc.has_cat = cat != nullptr; if (cat) pc.cat = *cat;
     pc.has_rs = rs != nullptr; if (rs) pc.rs = *rs;
@@ -2809,29 +2862,8 @@ extern "C" int lfdmi_detect_batch_begin(lfdmi_ctx *ctx, void *frames, int dtype,
     const lfdmi_catalog *cc = pc.has_cat ? &pc.cat : nullptr;
     const lfdmi_rs_params *rr = pc.has_rs ? &pc.rs : nullptr;
     const bool pinned = loc == LFDMI_HOST_PINNED;
-    if (dtype == LFDMI_F32_BE && !pinned) { // (as lfdmi_detect_batch_raw: device frames are swapped in place, once)
-        RET(run_bswap(ctx, frames, pc.frame_bytes));
-        dtype = LFDMI_F32;
-    }
-    pc.dtype = dtype;
-    pc.be = dtype == LFDMI_F32_BE;
-    if (!hough_fits(ctx, h, w, bright->houghMethod, LFD_PI / 180) || !hough_fits(ctx, h, w, dim->houghMethod, LFD_PI / 180)) {
-        // rho finer than this workspace's accumulators: the worst-case workspace takes the call, here and now
-        lfdmi_ctx *sp = get_spill(ctx);
-        if (!sp || !hough_fits(sp, h, w, bright->houghMethod, LFD_PI / 180) || !hough_fits(sp, h, w, dim->houghMethod, LFD_PI / 180))
-            return fail(ctx, LFDMI_ERR_CAPACITY, "Hough accumulator larger than the workspace (rho < 1 px)");
-        int rc = detect_impl(sp, frames, dtype, n, h, w, cc, rr, &pc.p1, &pc.p2, results, loc);
-        if (rc) { ctx->err = sp->err; return rc; }
-        pc.finished = true;
-        ctx->n_calls++;
-        return 0;
-    }
-    KeepEqu keep_guard(ctx, ctx->stage_mode == 1); // (before the front-end choice, which depends on it, as in detect_impl)
-    ctx->stages_valid = ctx->keep_equ;
-    bool dual, delta;
-    dim_front_end(ctx, w, &pc.p2, &dual, &delta);
     const int per = pinned ? feed_chunk_frames(ctx, n, N, true) : ctx->G;
-    pc.host_blot = cc && pinned && cc->loc == LFDMI_HOST && !pc.be;
+    pc.host_blot = blot_on_host(cc, pinned, dtype);
     const int max_obj = cc ? std::max(0, cc->max_obj) : 0;
     RET(call_area(ctx, pc, n, 1, pc.host_blot ? (size_t)n * max_obj : 0));
     if (pinned && n > 0) {
@@ -2853,24 +2885,12 @@ extern "C" int lfdmi_detect_batch_begin(lfdmi_ctx *ctx, void *frames, int dtype,
                 RET(async_upload(ctx, (const char *)frames + (size_t)(c0 + per) * N * 4, (size_t)std::min(per, n - c0 - per) * N * 4, kc + 1));
             HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->feed_up[kc & 1], 0));
         } else d = (const float *)frames + (size_t)c0 * N;
-        if (pc.be) RET(run_bswap(ctx, (void *)d, (size_t)nc * N * 4));
-        // remove_stars as in detect_impl, except that the squares a host catalogue gives pinned frames are copied into the call's
-        // area in stream order and the caller's array is blotted at the end
-        const bool copy_back = cc && pinned && !pc.host_blot && !pc.be;
-        ctx->rs_fold = cc && cc->max_obj > 0 && ctx->rs_fold_on && delta && w <= RS_MAXW && !copy_back;
-        ctx->rs_fill_frames = nullptr;
+        // (the squares a host catalogue gives pinned frames go to the call's area; the caller's array is blotted at the end)
         FoldState fold_guard{ctx};
-        if (cc) {
-            RET(run_removestars(ctx, (float *)d, c0, nc, h, w, cc, rr, nullptr, !ctx->rs_fold));
-            if (ctx->rs_fold && !pinned) { ctx->rs_fill_frames = (float *)d; ctx->rs_fill_part = 0; ctx->rs_fill_nc = nc; ctx->rs_fill_h = h; ctx->rs_fill_w = w; }
-            if (copy_back) RET(out_copy(ctx, frames, (size_t)c0 * N * 4, d, (size_t)nc * N * 4, LFDMI_HOST));
-            if (pc.host_blot && max_obj > 0)
-                HIPCHK(hipMemcpyAsync(pc.boxes_h + (size_t)c0 * max_obj, ctx->rs_boxes, (size_t)nc * max_obj * sizeof(int4), hipMemcpyDeviceToHost, ctx->stream));
-        }
-        CallChunk ch{c0, nc, !ctx->frame_ccl || ctx->general_seen, ctx->scan_fused, ctx->n_cap_growths};
-        ctx->general_on = ch.general_on;
+        RET(enqueue_detect_front(ctx, (float *)frames, d, dtype, pinned, c0, nc, h, w, cc, rr, 0, delta,
+                                 pc.host_blot ? pc.boxes_h + (size_t)c0 * max_obj : nullptr));
+        const CallChunk ch = chunk_start(ctx, c0, nc);
         RET(enqueue_detect_passes(ctx, d, nc, h, w, &pc.p1, &pc.p2, dual, delta));
-        ctx->general_on = true;
         if (pinned) { HIPCHK(hipEventRecord(ctx->feed_free[kc & 1], ctx->stream)); ctx->feed_free_set[kc & 1] = true; }
         HIPCHK(hipMemcpyAsync(pc.flags_h + c0, ctx->pass_flags, (size_t)nc * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipMemcpyAsync(pc.rec_h + c0, ctx->res_dev, (size_t)nc * sizeof(lfdmi_result), hipMemcpyDeviceToHost, ctx->stream));
@@ -2887,43 +2907,33 @@ extern "C" int lfdmi_process_multiscale_begin(lfdmi_ctx *ctx, const void *img, i
                                               lfdmi_result *results, int loc) {
     const size_t N = h > 0 && w > 0 ? (size_t)h * w : 0, es = dtype_size(dtype);
     RET(begin_check(ctx, img, n > 0 ? (size_t)n * N * es : 0, loc, true));
+    if (!rhos) return fail(ctx, LFDMI_ERR_ARG, "rhos NULL");
     Internal internal(ctx);
-    RET(check_shape(ctx, n, h, w));
-    RET(check_params(ctx, p, dim != 0));
-    if (!img || !results || !rhos || dtype < 0 || dtype > 2) return fail(ctx, LFDMI_ERR_ARG, "bad argument");
-    if (n_scales < 1 || n_scales > LFDMI_MAX_SCALES) return fail(ctx, LFDMI_ERR_ARG, "n_scales out of range");
-    if (dtype == LFDMI_U8 && dim) return fail(ctx, LFDMI_ERR_DTYPE, "dim pass needs a float image (numpy refuses uint8 += float)");
+    lfdmi_ctx *ws;
+    RET(pass_prologue(ctx, img, dtype, n, h, w, dim != 0, p, n_scales, rhos, results, &ws));
     PendingCall &pc = next_call(ctx);
     pc.kind = 1;
     pc.frames = (void *)img; pc.frame_bytes = (size_t)n * N * es;
+    pc.prep_mode = dim ? (after_bright ? LFDMI_PREP_BRIGHT_THEN_DIM : LFDMI_PREP_DIM) : LFDMI_PREP_BRIGHT;
+    if (ws != ctx) { // (as lfdmi_process_multiscale: the worst-case workspace, here and now)
+        int rc = pass_api(ws, img, dtype, n, h, w, flip, pc.prep_mode, dim != 0, p, n_scales, rhos, results, (size_t)n, nullptr, nullptr, loc);
+        if (rc) { ctx->err = ws->err; return rc; }
+        pc.finished = true;
+        ctx->n_calls++;
+        return 0;
+    }
     pc.dtype = dtype; pc.n = n; pc.h = h; pc.w = w; pc.loc = loc;
     pc.flip = flip; pc.dim = dim != 0; pc.n_scales = n_scales;
-    pc.prep_mode = dim ? (after_bright ? LFDMI_PREP_BRIGHT_THEN_DIM : LFDMI_PREP_DIM) : LFDMI_PREP_BRIGHT;
     for (int s = 0; s < n_scales; s++) pc.rhos[s] = rhos[s];
     pc.results = results;
     own_params(pc, p, nullptr);
-    for (int s = 0; s < n_scales; s++)
-        if (!hough_fits(ctx, h, w, rhos[s], LFD_PI / 180)) { // (as lfdmi_process_multiscale: the worst-case workspace, here and now)
-            lfdmi_ctx *sp = get_spill(ctx);
-            if (!sp || !hough_fits(sp, h, w, rhos[s], LFD_PI / 180)) return fail(ctx, LFDMI_ERR_CAPACITY, "Hough accumulator larger than the workspace (rho < 1 px)");
-            int rc = pass_api(sp, img, dtype, n, h, w, flip, pc.prep_mode, pc.dim, &pc.p1, n_scales, pc.rhos, results, (size_t)n, nullptr, nullptr, loc);
-            if (rc) { ctx->err = sp->err; return rc; }
-            pc.finished = true;
-            ctx->n_calls++;
-            return 0;
-        }
     RET(call_area(ctx, pc, n, n_scales, 0));
-    KeepEqu keep_guard(ctx, ctx->stage_mode != 0);
-    ctx->stages_valid = ctx->keep_equ;
-    ctx->cur_pass = 0;
     BeginAbort abort_guard{ctx};
     for (int c0 = 0; c0 < n; c0 += ctx->G) {
         const int nc = n - c0 < ctx->G ? n - c0 : ctx->G;
-        CallChunk ch{c0, nc, !ctx->frame_ccl || ctx->general_seen, ctx->scan_fused, ctx->n_cap_growths};
-        ctx->general_on = ch.general_on;
+        const CallChunk ch = chunk_start(ctx, c0, nc);
         RET(enqueue_pass_chunk(ctx, (const char *)img + (size_t)c0 * N * es, dtype, nc, h, w, flip, pc.prep_mode, pc.dim, &pc.p1, n_scales,
                                pc.rhos, pc.rec_h + c0, (size_t)n, pc.flags_h + c0, nullptr));
-        ctx->general_on = true;
         pc.chunks.push_back(ch);
     }
     HIPCHK(hipEventRecord(pc.done, ctx->stream));
@@ -2945,22 +2955,13 @@ static int finish_call(lfdmi_ctx *ctx, PendingCall &pc) {
     for (const CallChunk &ch : pc.chunks) {
         const int *flags = pc.flags_h + ch.c0;
         lfdmi_result *rec = pc.rec_h + ch.c0;
-        bool again = scan_gave_up(ctx, flags, ch.nc, ch.scan_fused);
-        if (!again) {
-            bool over = false;
-            for (int s = 0; s < n_scales; s++)
-                for (int i = 0; i < ch.nc; i++) over = over || rec[s * rstride + i].status == LFDMI_ERR_CAPACITY;
-            // (tables that have grown since the chunk was enqueued may hold it already)
-            again = over && (ctx->n_cap_growths > ch.growths || grow_caps(ctx, rec, ch.nc, rstride, n_scales));
-        }
-        if (!again) again = general_again(ctx, ch.general_on, flags, ch.nc);
-        ctx->general_on = true;
-        if (again) { // through the synchronous path, on a drained stream
+        if (chunk_again(ctx, ch, flags, rec, rstride, n_scales, true)) { // through the synchronous path, on a drained stream
             HIPCHK(hipStreamSynchronize(ctx->stream));
             if (pc.kind == 0) {
                 // device frames are swapped and blotted by now, pinned ones blotted (above, or by the copy back): no catalogue but
                 // for big-endian host frames, a read-only input
-                RET(detect_impl(ctx, (float *)pc.frames + (size_t)ch.c0 * N, pc.dtype, ch.nc, pc.h, pc.w, pc.be ? cc : nullptr, pc.be ? rr : nullptr,
+                const bool be = pc.dtype == LFDMI_F32_BE;
+                RET(detect_impl(ctx, (float *)pc.frames + (size_t)ch.c0 * N, pc.dtype, ch.nc, pc.h, pc.w, be ? cc : nullptr, be ? rr : nullptr,
                                 &pc.p1, &pc.p2, pc.results + ch.c0, pc.loc, ch.c0));
             } else {
                 RET(pass_api(ctx, (const char *)pc.frames + (size_t)ch.c0 * N * dtype_size(pc.dtype), pc.dtype, ch.nc, pc.h, pc.w, pc.flip, pc.prep_mode,
@@ -2970,8 +2971,8 @@ static int finish_call(lfdmi_ctx *ctx, PendingCall &pc) {
         }
         chunk_done(ctx);
         if (pc.kind == 0)
-            RET(finish_detect_frames(ctx, (float *)pc.frames, pc.dtype, ch.c0, ch.nc, pc.h, pc.w, cc, rr, &pc.p1, &pc.p2, rec, pc.results,
-                                     pc.loc == LFDMI_HOST_PINNED ? LFDMI_HOST : pc.loc, 0, nullptr));
+            RET(finish_detect_frames(ctx, (float *)pc.frames, pc.dtype, ch.c0, ch.nc, pc.h, pc.w, cc, rr, &pc.p1, &pc.p2, rec, pc.results, pc.loc, 0,
+                                     nullptr));
         else
             RET(finish_pass_frames(ctx, pc.frames, pc.dtype, ch.c0, ch.nc, pc.h, pc.w, pc.flip, pc.prep_mode, pc.dim, &pc.p1, pc.n_scales, pc.rhos,
                                    rec, rstride, nullptr, pc.results, rstride, nullptr, nullptr, pc.loc));
@@ -2989,10 +2990,7 @@ extern "C" int lfdmi_end_oldest(lfdmi_ctx *ctx) {
     HIPCHK(hipSetDevice(ctx->device));
     Internal internal(ctx);
     int rc = finish_call(ctx, pc);
-    if (rc) { // (the context stays usable: nothing of this call is left on the stream)
-        (void)hipStreamSynchronize(ctx->stream);
-        ctx->general_on = true;
-    }
+    if (rc) (void)hipStreamSynchronize(ctx->stream); // (the context stays usable: nothing of this call is left on the stream)
     return rc;
 }
 

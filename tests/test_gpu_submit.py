@@ -110,6 +110,28 @@ def test_submit_pinned_and_big_endian_frames(oracle):
         assert np.array_equal(swapped, blotted2)
 
 
+def test_refused_call_leaves_big_endian_device_frames_untouched():
+    """A call its checks refuse (here: rs.filter_index out of range with a catalogue of objects) does not swap big-endian
+    device frames in place: through detect_batch and detect_batch_begin they stay byte for byte as they were."""
+    import torch
+    from lfd_amd import _native
+    pb, pd, prs = params()
+    bad = _native.make_rs_params("r", **{k: v for k, v in prs.items() if k != "debug"})
+    bad.filter_index = 5
+    ((batch, packed, _, _),) = sdss_batches(1, 2, seed0=100)
+    assert packed["NOBSERVE"].shape[1] > 0
+    with _native.Context(0, 1489, 2048, 2) as ctx:
+        dbe = torch.from_numpy(batch.astype(">f4").view(np.uint8)).to("cuda:0")
+        before = dbe.cpu().numpy()
+        frames = _native.DeviceFrames(dbe.data_ptr(), batch.shape)
+        for call in (ctx.detect_batch, ctx.detect_batch_begin):
+            with pytest.raises(_native.NativeError) as e:
+                call(frames, pb, pd, to_dev(packed), bad)
+            assert e.value.code == _native.ERR_ARG, call.__name__
+            assert np.array_equal(dbe.cpu().numpy(), before), call.__name__
+        assert ctx.calls_in_flight() == 0
+
+
 @pytest.mark.parametrize("shape", [(4096, 4096), (1489, 2048)])
 def test_submit_multiscale_matches_process_multiscale(shape):
     import torch
