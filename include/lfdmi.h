@@ -483,6 +483,117 @@ int lfdmi_measure_trails(lfdmi_ctx *ctx, const void *frames, int dtype, int n, i
                          const lfdmi_catalog *cat, const lfdmi_rs_params *rs, const lfdmi_trail_params *p, lfdmi_trail *out,
                          float *profiles);
 
+/* ---- defocus fit ------------------------------------------------------------------------------------------------------------
+ * lfdmi_fit_defocus compares the profiles of lfdmi_measure_trails with a bank of model cross-sections of a trail, built on the
+ * device by lfdmi_defocus_bank_create, and reports the best model: the object's distance h, its size R and the seeing.  The
+ * model is the one of lfd/analysis/profiles (Bektesevic & Vinkovic et al., arXiv 1707.07223): object (x) defocus (x) seeing,
+ * plus the detector's pixel and the profile's bilinear sampling.  The reference's model functions return None in the tree
+ * this follows (defocusing.py:90, seeing.py:51, objectprofiles.py:151), so the expressions in their lambdas and docstrings
+ * are the definition, as below; tests/defocus_ref.py restates it in numpy.  Angles are in arcsec (RAD2ARCSEC = 206264.806247).
+ *
+ * 1. Components (continuous).
+ *    D, defocus (defocusing.py:49-101, Eq. 6), mirrors Ro, Ri in mm, theta_o = Ro / (h 1e6), theta_i = Ri / (h 1e6) rad:
+ *        D(x) = 2 / (pi (theta_o^2 - theta_i^2)) * (sqrt(theta_o^2 - x^2)_+ - [|x| < theta_i] sqrt(theta_i^2 - x^2)).
+ *      (The reference's step sign(theta_i - x) is one-sided, but its nan_to_num zeroes the inner term for every |x| >
+ *      theta_i, so D is symmetric.)
+ *    O, object: a point (delta), or a disk of radius R m with the 1-D profile 2 sqrt(rho^2 - x^2)_+ / (pi rho^2), where
+ *      rho = R / (2 h 1000) rad: the reference's angular size (objectprofiles.py:126), kept as it is (it is half the
+ *      angle R / (h 1000) the disk subtends).  R = 0 is the point.
+ *    S, seeing (seeing.py:29-57): sigma = 1.035 / 2.436 * FWHM; as written, both terms of 0.909 (G + 0.1 G) have the same
+ *      width, so S is one Gaussian exp(-x^2 / (2 sigma^2)) normalised to unit area.  The paper may intend a wider second
+ *      term; if someone pins it, it is a one-line change in k_def_kernel (and in the restatement).
+ *    B, the pixel: a box 1 px wide.  T, bilinear interpolation: the triangle 1 - |x| / 1 px.  B (x) T is the phase average of
+ *      measure_trails' bilinear samples.  The variance B (x) T adds along the trail's normal does not depend on the trail's
+ *      angle, but its shape does: this is an approximation (the recovery test in tests/test_gpu_defocus.py measures it).
+ *    The focus model (h = inf, height index n_h) has no D and a point object: S (x) B (x) T.  It is always in the bank.
+ * 2. Fine grid.  delta = prof_step * pixscale / ovs arcsec; F = ovs / prof_step fine steps per px; x_j = j delta.  Every
+ *    component is sampled in double at x_j and normalised to unit sum:
+ *        D_j = D(x_j), |j| <= floor(theta_o / delta);  O_j = the disk at x_j, |j| <= floor(rho / delta) (point: O_0 = 1);
+ *        S_j = exp(-x_j^2 / (2 sigma^2)), |j| <= floor(4 sigma / delta);
+ *        B_j = max(0, min(j + 1/2, F/2) - max(j - 1/2, -F/2)) (the box's overlap with fine cell j), |j| <= ceil(F/2 - 1/2);
+ *        T_j = 1 - |j| / F, |j| < F.
+ *    Discrete convolutions (a (x) b)_j = sum_i a_i b_(j-i), the sum over a's support in ascending i, in double:
+ *        OD = O (x) D;  KS = (S (x) B) (x) T;  M_q = sum_i OD_i KS_(q ovs - i)  (the model at bin q only).
+ *    Sums of normalisation are in ascending index order.
+ * 3. Columns.  The profile's bins are u_k = (k - K) prof_step px, k = 0 .. 2K (K = prof_half / prof_step).  With samp_q =
+ *    M at (q - K - S) prof_step px, q = 0 .. 2K + 2S (S = max_shift), the column of shift s in [-S, S] is the model centred
+ *    at s prof_step: t_k = samp_(k - s + S).  It is centred (t - mean(t), the mean over its 2K+1 bins) and scaled to unit
+ *    norm in double, then rounded to float32: t^_k.  Column index ((i_seeing n_h' + i_h) n_r + i_r) (2S+1) + (s + S) with
+ *    n_h' = n_h + 1 (the focus model is height index n_h; its n_r radius entries are all the point).
+ * 4. Validity.  A model is invalid, and never chosen, when (theta_o + rho) / pixscale + 4 sigma / pixscale + 1 + S prof_step
+ *    > prof_half - wing (px): its wings would reach the background bins of measure_trails.  An invalid model's columns are 0.
+ * 5. Grid record per model (what generic_sampler(returnType="grid") reports, samplers.py:150-162): dfwhm = the FWHM of OD,
+ *    ofwhm = the FWHM of samp at shift 0 (the bins u_k), both by measure_trails' calc_fwhm rule (first / last bin >= peak/2,
+ *    |x_right| + |x_left|, 0 when they coincide) in arcsec; depth = (peak - samp_(K+S)) / peak * 100.  NaN for a model whose
+ *    OD does not fit the profile (theta_o + rho > prof_half px); the focus model's dfwhm is 0.
+ * 6. Fit of one trail.  Fitted when its record has LFDMI_TRAIL_OK, its row no NaN and noise > 0 (otherwise status
+ *    LFDMI_DEFOCUS_NOT_MEASURED / _GAPS / _NO_NOISE and every double NaN).  v~ = (float)(v - mean(v)) (mean in double).
+ *    Allowed columns: valid, and of the trail's seeing slice when one is given (the seeing value nearest to it; a tie: the
+ *    lower).  Score c = v~ . t^, a float32 product on the matrix cores (an fmaf chain in ascending k).  The best column is
+ *    the arg-max of c over the allowed columns with c > 0 (a tie: the lowest index); none: LFDMI_DEFOCUS_NO_MODEL.
+ *    For it, in double, with t = samp at that shift (not normalised): a = sum (v - vbar)(t - tbar) / sum (t - tbar)^2,
+ *    b = vbar - a tbar, chi2 = sum (v - a t - b)^2 / noise^2, dof = 2K - 1.
+ *    chi2_by_height[i_h] = (|v~|^2 - m^2) / noise^2, m = max(0, the largest c of the allowed columns of that height) (|v~|^2
+ *    in double); NaN when the height has no allowed column.  chi2_min = the least of them; h_lo / h_hi = the least / largest
+ *    grid height with chi2_by_height <= chi2_min + delta_chi2 (h_hi = +inf when the focus model is among them, h_lo too when
+ *    it is the only one).  The bins are correlated (about 1 / prof_step of them per px), so chi2 is a relative measure and
+ *    delta_chi2 a relative threshold, not a confidence level.  The chosen model's h_km is +inf for the focus model.
+ * Recovery (tests/test_gpu_defocus.py: trails rendered as the model without B and T, 8 x 8 sub-pixel points, peak 2 sky sigma,
+ * ~2000 px long, three angles, then measure_trails and this fit with the default bank plus the true heights): h = 80, 100,
+ * 150 km came back within 0.9 % (on the true height or the next grid height) and in-focus trails as the focus model.  The
+ * interval [h_lo, h_hi] held the true height in 6 of 9 cases; in 3 (100 km at theta 0.35, 150 km at 1.2 and 2.4 rad) the fit
+ * sat on the neighbouring grid height and the interval was narrower than that 0.4-0.9 % step: the median and bilinear
+ * approximations bias h by more than delta_chi2 = 1 / prof_step allows.  The seeing came back within 0.13" in 8 of 9 cases
+ * and 0.28" low in one (150 km at theta 2.4 rad), where defocus and seeing widen the profile alike. */
+typedef struct {
+    double Ro, Ri;            /* mirrors' radii in mm (SDSS 1250, 585; LSST 4180, 2558) */
+    double pixscale;          /* arcsec per px: the trail params' */
+    double prof_half;         /* P px: the trail params' */
+    double prof_step;         /* px: the trail params' (ovs / prof_step need not be an integer) */
+    int32_t wing;             /* px: the trail params' */
+    int32_t ovs;              /* fine steps per profile bin (1 .. 64); default 8 */
+    int32_t max_shift;        /* S: shifts of +-S bins (0 .. 64); default 5 */
+    int32_t n_h, n_r, n_seeing; /* grid lengths (each >= 1; n_seeing (n_h + 1) n_r (2S+1) columns at most 2^26) */
+    const double *heights;    /* km, > 0, n_h of them; NULL in the defaults: 60 .. 300 km in 128 geometric steps */
+    const double *radii;      /* m, >= 0; defaults {0, 0.1, 0.5, 1, 2, 5, 10} */
+    const double *seeings;    /* FWHM arcsec, > 0; defaults 0.8 .. 2.2 in steps of 0.05 */
+    double delta_chi2;        /* interval threshold; default 1 / prof_step */
+} lfdmi_defocus_params;
+typedef struct {
+    double h_km;              /* +inf: the focus model */
+    double radius_m, sfwhm, dfwhm, ofwhm, depth;  /* sfwhm: the seeing FWHM; dfwhm, ofwhm arcsec, depth % (step 5) */
+    int32_t valid, pad;
+} lfdmi_defocus_model;
+enum { LFDMI_DEFOCUS_OK = 0, LFDMI_DEFOCUS_NOT_MEASURED = 1, LFDMI_DEFOCUS_GAPS = 2, LFDMI_DEFOCUS_NO_NOISE = 3,
+       LFDMI_DEFOCUS_NO_MODEL = 4 };
+typedef struct {
+    int32_t status;           /* LFDMI_DEFOCUS_* */
+    int32_t shift;            /* s of the chosen column, bins */
+    int32_t dof;
+    int32_t column;           /* the chosen column's index; -1 without a fit */
+    double h_km, radius_m, seeing_arcsec;
+    double amplitude, offset, chi2;
+    double h_lo, h_hi, chi2_focus;
+    double model_ofwhm, model_depth;
+} lfdmi_defocus_fit;
+typedef struct lfdmi_defocus_bank lfdmi_defocus_bank;
+/* the defaults (SDSS mirrors and trail params, the grids above: the pointers are the library's own constant arrays) */
+void lfdmi_default_defocus_params(lfdmi_defocus_params *out);
+/* builds the bank on ctx's device (kept in device memory until lfdmi_defocus_bank_destroy); the grids are copied */
+int lfdmi_defocus_bank_create(lfdmi_ctx *ctx, const lfdmi_defocus_params *p, lfdmi_defocus_bank **out);
+/* destroy may come before or after lfdmi_ctx_destroy of the bank's context (it does not touch the context); read and fit
+ * need the context alive */
+void lfdmi_defocus_bank_destroy(lfdmi_defocus_bank *bank);
+/* sizes of a bank: columns, models (n_seeing (n_h + 1) n_r), bins per column (2K + 1); any pointer may be NULL */
+int lfdmi_defocus_bank_dims(const lfdmi_defocus_bank *bank, int64_t *n_columns, int64_t *n_models, int32_t *n_bins);
+/* columns: n_columns x (2K + 1) float32 (host) or NULL; grid: n_models records (host) or NULL */
+int lfdmi_defocus_bank_read(const lfdmi_defocus_bank *bank, float *columns, lfdmi_defocus_model *grid);
+/* trails / profiles: n records and n x (2K + 1) float32 rows of lfdmi_measure_trails (host), with the trail params the bank
+ * was built for; seeing: n FWHM values in arcsec (NaN: free) or NULL; out: n records; chi2_by_height: n x (n_h + 1) or NULL.
+ * ctx must be the bank's.  The fit's workspace is allocated on the first call. */
+int lfdmi_fit_defocus(lfdmi_ctx *ctx, const lfdmi_defocus_bank *bank, const lfdmi_trail *trails, const float *profiles, int n,
+                      const float *seeing, lfdmi_defocus_fit *out, float *chi2_by_height);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,6 +36,8 @@ SYMBOLS = (
     "lfdmi_timing_slots", "lfdmi_timing_name",
     "lfdmi_detect_batch_begin", "lfdmi_process_multiscale_begin", "lfdmi_end_oldest", "lfdmi_calls_in_flight",
     "lfdmi_default_trail_params", "lfdmi_measure_trails",
+    "lfdmi_default_defocus_params", "lfdmi_defocus_bank_create", "lfdmi_defocus_bank_destroy", "lfdmi_defocus_bank_dims",
+    "lfdmi_defocus_bank_read", "lfdmi_fit_defocus",
 )
 
 
@@ -119,6 +121,25 @@ def trail_bins(p):
     return 2 * int(round(p.prof_half / p.prof_step)) + 1
 
 
+class DefocusParams(C.Structure):
+    """lfdmi_defocus_params (include/lfdmi.h: defocus fit)."""
+    _fields_ = [("Ro", C.c_double), ("Ri", C.c_double), ("pixscale", C.c_double), ("prof_half", C.c_double),
+                ("prof_step", C.c_double), ("wing", C.c_int32), ("ovs", C.c_int32), ("max_shift", C.c_int32),
+                ("n_h", C.c_int32), ("n_r", C.c_int32), ("n_seeing", C.c_int32), ("heights", C.POINTER(C.c_double)),
+                ("radii", C.POINTER(C.c_double)), ("seeings", C.POINTER(C.c_double)), ("delta_chi2", C.c_double)]
+
+
+# lfdmi_defocus_model: one record per model of a bank; lfdmi_defocus_fit: one per trail of lfdmi_fit_defocus
+DEFOCUS_MODEL_DTYPE = np.dtype([("h_km", "<f8"), ("radius_m", "<f8"), ("sfwhm", "<f8"), ("dfwhm", "<f8"), ("ofwhm", "<f8"),
+                                ("depth", "<f8"), ("valid", "<i4"), ("pad", "<i4")])
+DEFOCUS_DTYPE = np.dtype([("status", "<i4"), ("shift", "<i4"), ("dof", "<i4"), ("column", "<i4"),
+                          ("h_km", "<f8"), ("radius_m", "<f8"), ("seeing_arcsec", "<f8"),
+                          ("amplitude", "<f8"), ("offset", "<f8"), ("chi2", "<f8"),
+                          ("h_lo", "<f8"), ("h_hi", "<f8"), ("chi2_focus", "<f8"),
+                          ("model_ofwhm", "<f8"), ("model_depth", "<f8")])
+DEFOCUS_OK, DEFOCUS_NOT_MEASURED, DEFOCUS_GAPS, DEFOCUS_NO_NOISE, DEFOCUS_NO_MODEL = 0, 1, 2, 3, 4
+
+
 _lib = None
 
 
@@ -155,6 +176,15 @@ def lib():
         _lib.lfdmi_bz2_timings.argtypes = [C.c_void_p, C.c_void_p]
         _lib.lfdmi_bz2_frames.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(C.c_void_p)]
         _lib.lfdmi_bz2_reserve.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_uint64]
+        _lib.lfdmi_default_defocus_params.restype = None
+        _lib.lfdmi_default_defocus_params.argtypes = [C.c_void_p]
+        _lib.lfdmi_defocus_bank_create.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+        _lib.lfdmi_defocus_bank_destroy.restype = None
+        _lib.lfdmi_defocus_bank_destroy.argtypes = [C.c_void_p]
+        _lib.lfdmi_defocus_bank_dims.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.lfdmi_defocus_bank_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.lfdmi_fit_defocus.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]
     return _lib
 
 
@@ -403,6 +433,8 @@ class Context:
         if h:
             while getattr(self, "_inflight", None):          # (calls in flight end first: their results stay readable)
                 self._end_oldest()
+            for b in list(getattr(self, "_banks", ())):       # defocus banks of this context close with it
+                b.close()
             self._h = None
             self._lib.lfdmi_ctx_destroy(h)
 
@@ -794,6 +826,27 @@ class Context:
                                                  C.byref(c) if c is not None else None, C.byref(rs) if rs is not None else None,
                                                  C.byref(p), _ptr(out), _ptr(prof)))
         return out, prof
+
+    # -- defocus fit (lfdmi_fit_defocus) ---------------------------------------------------------------------------------------
+    def fit_defocus(self, bank, trails, profiles, seeing=None, chi2_by_height=False):
+        """Best defocus model of every trail (include/lfdmi.h: defocus fit).  bank: a ``defocus.DefocusBank`` of this context;
+        trails / profiles: what ``measure_trails`` returned (with the trail params the bank was built for); seeing: None or n
+        FWHM values in arcsec (NaN: free).  Returns a DEFOCUS_DTYPE array [n], and with chi2_by_height=True also the float32
+        [n, n_h + 1] chi2 per height (the last column: the focus model)."""
+        if not bank._b or bank.ctx is not self:
+            raise ValueError("fit_defocus needs an open bank of this context")
+        tr = np.ascontiguousarray(trails, TRAIL_DTYPE).reshape(-1)
+        n = len(tr)
+        prof = np.ascontiguousarray(profiles, np.float32)
+        if prof.shape != (n, bank.n_bins):
+            raise ValueError(f"profiles of shape {prof.shape}, the bank needs ({n}, {bank.n_bins})")
+        see = None
+        if seeing is not None:
+            see = np.ascontiguousarray(np.broadcast_to(np.asarray(seeing, np.float32), (n,)))
+        out = np.zeros(n, DEFOCUS_DTYPE)
+        cbh = np.empty((n, bank.n_h + 1), np.float32) if chi2_by_height else None
+        self._chk(self._lib.lfdmi_fit_defocus(self._h, bank._b, _ptr(tr), _ptr(prof), n, _ptr(see), _ptr(out), _ptr(cbh)))
+        return (out, cbh) if chi2_by_height else out
 
     def pinned_buffer(self, nbytes):
         """Page-locked host memory next to this context's GPU (lfdmi_host_alloc) as a ``PinnedBuffer``."""

@@ -246,3 +246,13 @@ class BatchDetector:
                 for c, (a, b) in zip(self.ctxs, bounds) if b > a]
         res = [f.result() for f in futs]
         return np.concatenate([r[0] for r in res]), np.concatenate([r[1] for r in res])
+
+    def fit_defocus(self, bank, trails, profiles, seeing=None, **kw):
+        """``Context.fit_defocus`` on the first lane's context (the bank's: build it with ``DefocusBank(bd.ctx, ...)``).  With
+        calls in flight it runs after them, as ``measure_trails`` does."""
+        for f in list(self._pending):
+            f.result()
+        self._pending = []
+        while self.ctx.calls_in_flight():
+            self.ctx._end_oldest()
+        return self.ctx.fit_defocus(bank, trails, profiles, seeing, **kw)

@@ -268,6 +268,9 @@ struct lfdmi_ctx {
                stage_c = 0;
         size_t bytes = 0;
     } trail;
+    // lfdmi_fit_defocus' workspace (defocus.hip), allocated by its first call; defocus_free releases it
+    void *defocus = nullptr;
+    void (*defocus_free)(lfdmi_ctx *) = nullptr;
 };
 
 static int fail(lfdmi_ctx *c, int code, const std::string &msg) {
@@ -728,6 +731,7 @@ extern "C" void lfdmi_ctx_destroy(lfdmi_ctx *ctx) {
     if (ctx->rs_sboxes) hipFree(ctx->rs_sboxes);
     if (ctx->rs_rowstart) hipFree(ctx->rs_rowstart);
     if (ctx->cat_dev) hipFree(ctx->cat_dev);
+    if (ctx->defocus_free) ctx->defocus_free(ctx);
     for (void *p : {ctx->trail.st, ctx->trail.segm, ctx->trail.sA, ctx->trail.sC, ctx->trail.sSig, ctx->trail.planes, ctx->trail.boxes,
                     ctx->trail.prof, ctx->trail.cnt, ctx->trail.rec, ctx->trail.stage})
         if (p) hipFree(p);
@@ -3145,6 +3149,22 @@ extern "C" int lfdmi_get_stage(lfdmi_ctx *ctx, int slot, int which, int h, int w
     } else return fail(ctx, LFDMI_ERR_ARG, "unknown stage");
     RET(out_copy(ctx, dst, 0, src, N, loc));
     return sync(ctx, 1);
+}
+
+// ---- the context as defocus.hip sees it (host side, not exported) -----------------------------------------------------------
+#define LFD_HIDDEN __attribute__((visibility("hidden")))
+LFD_HIDDEN int ctx_begin(lfdmi_ctx *ctx) { // an entry point's start: not while calls are in flight; the ctx's device, no stale error
+    RET(idle(ctx));
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, LFDMI_ERR_HIP, "hipSetDevice");
+    (void)hipGetLastError();
+    return 0;
+}
+LFD_HIDDEN int ctx_fail(lfdmi_ctx *ctx, int code, const std::string &msg) { return fail(ctx, code, msg); }
+LFD_HIDDEN hipStream_t ctx_stream(lfdmi_ctx *ctx) { return ctx->stream; }
+LFD_HIDDEN int ctx_device(lfdmi_ctx *ctx) { return ctx->device; }
+LFD_HIDDEN void **ctx_defocus(lfdmi_ctx *ctx, void (*release)(lfdmi_ctx *)) {
+    if (release) ctx->defocus_free = release;
+    return &ctx->defocus;
 }
 
 // ---- C-ABI: trail profiles (include/lfdmi.h, k_trail.h) ---------------------------------------------------------------------

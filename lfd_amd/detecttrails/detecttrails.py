@@ -135,8 +135,57 @@ def _write_profile(profiles, errors, key, meas, debug):
         if isinstance(meas, Exception):
             raise meas
         profiles.write(profile_row(key, *meas))
+        if isinstance(profiles, _DefocusTee):
+            profiles.add(key, *meas)
     except Exception as e:  # noqa: BLE001
         _log_error(errors, key, e, debug)
+
+
+_BANKS = {}   # (device, params) -> (Context, DefocusBank): the defocus bank is built once per process
+
+
+def defocus_bank(defocus_params=None, trail_params=None):
+    """The process's ``DefocusBank`` for these grid / instrument params (``defocus_params``: heights, radii, seeings,
+    instrument, ovs, max_shift, delta_chi2) and trail params, on its own small context of the device the shared context uses."""
+    from .. import defocus
+    from .processfield import _device_index
+    dp, tp = dict(defocus_params or {}), dict(trail_params or {})
+    key = (_device_index(), repr(sorted((k, _np.asarray(v).tolist()) for k, v in dp.items())), repr(sorted(tp.items())))
+    if key not in _BANKS:
+        ctx = _native.Context(key[0], 64, 64, 1)
+        try:
+            _BANKS[key] = (ctx, defocus.DefocusBank(ctx, **dp, **tp))
+        except Exception:
+            ctx.close()
+            raise
+    return _BANKS[key]
+
+
+class _DefocusTee:
+    """profiles.txt with defocus.txt beside it: every profiles row written is also fitted (include/lfdmi.h: defocus fit); the
+    rows added since the last ``flush`` are fitted in one call and their defocus rows written in the same order."""
+
+    def __init__(self, profiles, out, defocus_params, trail_params):
+        self.profiles, self.out = profiles, out
+        self.defocus_params, self.trail_params = defocus_params, trail_params
+        self.pending = []
+
+    def write(self, text):
+        self.profiles.write(text)
+
+    def add(self, key, trail, profile):
+        self.pending.append((key, trail, profile))
+
+    def flush(self):
+        from .. import defocus
+        if self.pending:
+            ctx, bank = defocus_bank(self.defocus_params, self.trail_params)
+            trails = _np.array([t for _, t, _ in self.pending], _native.TRAIL_DTYPE)
+            fit = ctx.fit_defocus(bank, trails, _np.stack([p for _, _, p in self.pending]))
+            self.out.write("".join(defocus.format_row(k, f) + "\n" for (k, _, _), f in zip(self.pending, fit)))
+            self.pending = []
+        self.profiles.flush()
+        self.out.flush()
 
 
 def _load_frame(run, camcol, filter, field):
@@ -424,6 +473,12 @@ class DetectTrails:
     trail profiles) and appends its ``profile_row`` to ``profiles`` (default ``<savepath>/profiles.txt``), one row per
     results.txt row, in the same order; ``trail_params`` (dict) replaces fields of lfdmi_trail_params.  Rank files, resume
     and ``Jobs`` merging treat profiles.txt as they treat results.txt.
+    ``defocus=True`` (default off; implies ``trail_profiles``) also fits every profiles row against the defocus bank
+    (``lfd_amd.defocus``; include/lfdmi.h: defocus fit) and writes one row per results.txt row to ``defocus_file`` (default
+    ``<savepath>/defocus.txt``): ``run camcol filter field status h_km h_lo h_hi radius_m seeing_arcsec shift amplitude offset
+    chi2 dof chi2_focus model_ofwhm model_depth``.  ``defocus_params`` (dict): heights, radii, seeings, instrument, ovs,
+    max_shift, delta_chi2.  The bank is built once per process; rank files, resume and ``Jobs`` treat defocus.txt like
+    profiles.txt.
     """
 
     _FILTERS = ('u', 'g', 'r', 'i', 'z')
@@ -435,11 +490,17 @@ class DetectTrails:
         self.params_bright, self.params_dim, self.params_removestars = default_params()
         self.results = kwargs.get("results", os.path.join(save, "results.txt"))
         self.errors = kwargs.get("errors", os.path.join(save, "errors.txt"))
-        self.trail_profiles = bool(kwargs.get("trail_profiles", False))
+        self.defocus = bool(kwargs.get("defocus", False))
+        self.defocus_file = kwargs.get("defocus_file", os.path.join(save, "defocus.txt"))
+        self.defocus_params = dict(kwargs.get("defocus_params") or {})
+        self.trail_profiles = bool(kwargs.get("trail_profiles", False)) or self.defocus
         self.profiles = kwargs.get("profiles", os.path.join(save, "profiles.txt"))
         self.trail_params = dict(kwargs.get("trail_params") or {})
         if self.trail_profiles:
             _native.make_trail_params(**self.trail_params)      # (unknown names raise here, not per frame)
+        if self.defocus:
+            from .. import defocus
+            defocus.make_params(**self.defocus_params, **self.trail_params)   # (likewise)
         for name in ("params_bright", "params_dim", "params_removestars"):
             if name in kwargs:
                 setattr(self, name, kwargs[name])
@@ -587,7 +648,10 @@ class DetectTrails:
         import contextlib
         with open(self.results + suffix, "a") as results, open(self.errors + suffix, "a") as errors, \
                 open(progress_path, "w" if fresh else "a") as progress, \
-                (open(self.profiles + suffix, "a") if self.trail_profiles else contextlib.nullcontext()) as profiles:
+                (open(self.profiles + suffix, "a") if self.trail_profiles else contextlib.nullcontext()) as profiles, \
+                (open(self.defocus_file + suffix, "a") if self.defocus else contextlib.nullcontext()) as defocus_out:
+            if self.defocus:
+                profiles = _DefocusTee(profiles, defocus_out, self.defocus_params, self.trail_params)
             prof_kw = {"profiles": profiles, "trail_params": self.trail_params} if self.trail_profiles else {}
             if fresh:
                 progress.write(header + "\n")
