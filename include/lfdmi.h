@@ -594,6 +594,77 @@ int lfdmi_defocus_bank_read(const lfdmi_defocus_bank *bank, float *columns, lfdm
 int lfdmi_fit_defocus(lfdmi_ctx *ctx, const lfdmi_defocus_bank *bank, const lfdmi_trail *trails, const float *profiles, int n,
                       const float *seeing, lfdmi_defocus_fit *out, float *chi2_by_height);
 
+/* ---- sky normalisation ------------------------------------------------------------------------------------------------------
+ * Every other entry point assumes an SDSS frame-*.fits: sky subtracted, pixels in nanomaggies, sky sigma 0.02 - 0.05 (the
+ * units minFlux / addFlux are written in).  lfdmi_sky_normalize makes a frame that still carries its sky (a pedestal, a
+ * gradient, a raw exposure in ADU, an SDSS fpC file) look like that: it estimates the sky and its noise on a mesh, subtracts
+ * the sky and scales the noise to target_sigma.  The reference has no such step.  The procedure below is the definition;
+ * tests/sky_ref.py restates it in numpy and the device matches it bit for bit: every statistic is an exact selection, so no
+ * result depends on evaluation order.  Notation: frame x of H x W float32, buffer rows (not flipped).  The lower median of m
+ * values is rank floor((m-1)/2) in ascending order, as in lfdmi_measure_trails.  In the statistics a pixel -0 counts as +0.
+ *
+ * 1. Mesh.  ny = ceil(H / cell), nx = ceil(W / cell); cell (j, i) covers rows [j cell, min((j+1) cell, H)) and columns
+ *    [i cell, min((i+1) cell, W)): the last row and column of cells may be partial.  A cell's area is its own pixel count.
+ * 2. Cell statistic.  S_0 = the cell's finite pixels.  For t = 0 .. n_clip: med_t = lower median of S_t; mad_t = lower median of
+ *    |v - med_t| over S_t (one float32 subtraction per element); if t < n_clip: S_(t+1) = {v in S_t : lo <= (double)v <= hi} with
+ *    d = k_clip * 1.4826 * (double)mad_t, lo = (double)med_t - d, hi = (double)med_t + d (double, left to right).
+ *    b = med_(n_clip), s = (float)(1.4826 * (double)mad_(n_clip)).  A cell is EMPTY when 8 |S_0| < area; its b, s are not used.
+ * 3. Fill.  An empty cell takes, for b and s separately, the lower median of the non-empty cells among its up-to-8 neighbours
+ *    (their step-2 values, not filled ones); without such a neighbour, the frame value of step 5.
+ * 4. Filter (filter = 3; 1: none).  Each value becomes the lower median of the filled mesh over its 3 x 3 neighbourhood clipped
+ *    to the mesh, written to a second mesh (never in place); the same for the s mesh.
+ * 5. Frame values.  sky / sigma = lower median of b / s over the non-empty cells (step-2 values); gain = (float)(target_sigma /
+ *    (double)sigma) in mode LFDMI_SKY_NORMALISE, 1 in mode LFDMI_SKY_SUBTRACT.  status: LFDMI_SKY_OK; LFDMI_SKY_NO_SKY: no
+ *    non-empty cell (the output is the input with non-finite pixels set to 0; sky, sigma and the meshes are NaN, gain 1);
+ *    LFDMI_SKY_NO_NOISE: NORMALISE and sigma == 0 (the sky is subtracted, gain 1).
+ * 6. Background at a pixel, from the filtered b mesh m.  Cell centres cy_j = (r0 + r1 - 1) * 0.5 over the cell's own rows
+ *    [r0, r1), cx_i likewise.  For row y: j = the last cell with cy_j <= y (0 when y < cy_0), j' = min(j + 1, ny - 1),
+ *    ty = (float)((y - cy_j) / (cy_j' - cy_j)) (double division) when j' != j and y >= cy_j, else 0: constant outside the
+ *    outermost centres.  i, i', tx likewise along the columns.  Then in float32, each operation rounded, no FMA:
+ *        top = m[j][i] + tx*(m[j][i'] - m[j][i]);  bot = m[j'][i] + tx*(m[j'][i'] - m[j'][i]);  bkg = top + ty*(bot - top)
+ * 7. Output.  out = (x - bkg) * gain in float32 (two rounded operations); a non-finite x gives 0.
+ * Units afterwards: value = (flux - sky) * gain, so flux = value / gain + sky(pixel); trail profiles and defocus fits of a
+ * normalised frame are in these units. */
+enum { LFDMI_SKY_SUBTRACT = 0, LFDMI_SKY_NORMALISE = 1 };
+enum { LFDMI_SKY_OK = 0, LFDMI_SKY_NO_SKY = 1, LFDMI_SKY_NO_NOISE = 2 };
+typedef struct {
+    int32_t cell;         /* mesh cell edge in px (16 .. 256); default 64 */
+    int32_t n_clip;       /* clipping rounds (0 .. 8); default 3 */
+    int32_t filter;       /* 3: 3 x 3 median of the mesh (default); 1: none */
+    int32_t mode;         /* LFDMI_SKY_NORMALISE (default) or LFDMI_SKY_SUBTRACT */
+    double k_clip;        /* clip at +- k_clip sigma (> 0); default 3 */
+    double target_sigma;  /* sky sigma after NORMALISE (> 0); default 0.025: the sky sigma of lfd_amd/synth.make_frame, the recipe
+                             the detection thresholds and the benchmark are quoted on */
+} lfdmi_sky_params;
+typedef struct {
+    int32_t status;       /* LFDMI_SKY_* */
+    int32_t ny, nx;       /* the mesh */
+    int32_t n_empty;      /* empty cells (step 2) */
+    double sky, sigma, gain;
+} lfdmi_sky_frame;
+typedef struct lfdmi_sky lfdmi_sky;
+void lfdmi_default_sky_params(lfdmi_sky_params *out);
+/* A handle for frames of exactly h x w on ctx's device: it owns the meshes, the tables of step 6, page-locked staging for host
+ * frames and a device output buffer of max_frames frames.  p NULL: the defaults.  Bad arguments: LFDMI_ERR_ARG.  Destroy may
+ * come before or after lfdmi_ctx_destroy of its context (it does not touch the context); normalize needs the context alive. */
+int lfdmi_sky_create(lfdmi_ctx *ctx, int h, int w, int max_frames, const lfdmi_sky_params *p, lfdmi_sky **out);
+void lfdmi_sky_destroy(lfdmi_sky *sky);
+/* the mesh and the device bytes the handle holds; any pointer may be NULL */
+int lfdmi_sky_dims(const lfdmi_sky *sky, int32_t *ny, int32_t *nx, int64_t *bytes);
+/* the handle's device output buffer (max_frames x h x w float32) */
+void *lfdmi_sky_frames(lfdmi_sky *sky);
+/* frames: n frames, LFDMI_F32 or LFDMI_F32_BE, loc LFDMI_HOST / LFDMI_HOST_PINNED / LFDMI_DEVICE; only read (unless out == frames).
+ * out (native float32, out_loc where it lives): a caller's buffer of n frames, host or device; or, for LFDMI_F32 device frames,
+ * the frames themselves (in place: the statistics of a chunk are complete before any pixel of it is written); or NULL: the
+ * handle's own device buffer (n <= max_frames), valid until the handle's next call and fit for lfdmi_detect_batch_raw(...,
+ * LFDMI_F32, ..., LFDMI_DEVICE) and lfdmi_measure_trails.  rec: n records (host).  mesh_sky / mesh_sigma: n x ny x nx float32
+ * each (host), the filtered meshes of step 4; either may be NULL.  n > max_frames runs in chunks of max_frames.  The call
+ * refuses while calls are in flight (LFDMI_ERR_ARG), runs on the context's stream and waits for it once, at its end; copies
+ * to pageable host memory (records, meshes, a LFDMI_HOST output) are staged by the runtime as they are queued, so the chunks
+ * of a call overlap only with device or page-locked outputs. */
+int lfdmi_sky_normalize(lfdmi_ctx *ctx, lfdmi_sky *sky, const void *frames, int dtype, int n, int loc, void *out, int out_loc,
+                        lfdmi_sky_frame *rec, float *mesh_sky, float *mesh_sigma);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,7 @@ SYMBOLS = (
     "lfdmi_default_trail_params", "lfdmi_measure_trails",
     "lfdmi_default_defocus_params", "lfdmi_defocus_bank_create", "lfdmi_defocus_bank_destroy", "lfdmi_defocus_bank_dims",
     "lfdmi_defocus_bank_read", "lfdmi_fit_defocus",
+    "lfdmi_default_sky_params", "lfdmi_sky_create", "lfdmi_sky_destroy", "lfdmi_sky_dims", "lfdmi_sky_frames", "lfdmi_sky_normalize",
 )
 
 
@@ -140,6 +141,38 @@ DEFOCUS_DTYPE = np.dtype([("status", "<i4"), ("shift", "<i4"), ("dof", "<i4"), (
 DEFOCUS_OK, DEFOCUS_NOT_MEASURED, DEFOCUS_GAPS, DEFOCUS_NO_NOISE, DEFOCUS_NO_MODEL = 0, 1, 2, 3, 4
 
 
+class SkyParamsStruct(C.Structure):
+    """lfdmi_sky_params (include/lfdmi.h: sky normalisation)."""
+    _fields_ = [("cell", C.c_int32), ("n_clip", C.c_int32), ("filter", C.c_int32), ("mode", C.c_int32),
+                ("k_clip", C.c_double), ("target_sigma", C.c_double)]
+
+
+class SkyFrame(C.Structure):
+    """lfdmi_sky_frame: one record per frame of lfdmi_sky_normalize."""
+    _fields_ = [("status", C.c_int32), ("ny", C.c_int32), ("nx", C.c_int32), ("n_empty", C.c_int32),
+                ("sky", C.c_double), ("sigma", C.c_double), ("gain", C.c_double)]
+
+
+SKY_DTYPE = np.dtype([("status", "<i4"), ("ny", "<i4"), ("nx", "<i4"), ("n_empty", "<i4"),
+                      ("sky", "<f8"), ("sigma", "<f8"), ("gain", "<f8")])
+SKY_SUBTRACT, SKY_NORMALISE = 0, 1
+SKY_OK, SKY_NO_SKY, SKY_NO_NOISE = 0, 1, 2
+
+
+def make_sky_params(**params):
+    """lfdmi_default_sky_params with the given fields replaced (unknown names raise; mode also as "subtract" / "normalise")."""
+    p = SkyParamsStruct()
+    lib().lfdmi_default_sky_params(C.byref(p))
+    names = {k for k, _ in SkyParamsStruct._fields_}
+    for k, v in params.items():
+        if k not in names:
+            raise TypeError(f"unknown sky parameter {k!r}")
+        if k == "mode" and isinstance(v, str):
+            v = {"subtract": SKY_SUBTRACT, "normalise": SKY_NORMALISE, "normalize": SKY_NORMALISE}[v.lower()]
+        setattr(p, k, v)
+    return p
+
+
 _lib = None
 
 
@@ -185,6 +218,16 @@ def lib():
         _lib.lfdmi_defocus_bank_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.lfdmi_fit_defocus.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                            C.c_void_p]
+        _lib.lfdmi_default_sky_params.restype = None
+        _lib.lfdmi_default_sky_params.argtypes = [C.c_void_p]
+        _lib.lfdmi_sky_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
+        _lib.lfdmi_sky_destroy.restype = None
+        _lib.lfdmi_sky_destroy.argtypes = [C.c_void_p]
+        _lib.lfdmi_sky_dims.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.lfdmi_sky_frames.restype = C.c_void_p
+        _lib.lfdmi_sky_frames.argtypes = [C.c_void_p]
+        _lib.lfdmi_sky_normalize.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]
     return _lib
 
 
@@ -292,6 +335,19 @@ class DeviceFrames:
 
     def slice(self, a, b):
         return DeviceFrames(self.address_of(a), (int(b) - int(a), self.shape[1], self.shape[2]))
+
+
+class NativeDeviceFrames(DeviceFrames):
+    """n native float32 frames in device memory that belongs to a ``Sky`` handle (its normalised output): taken as LFDMI_F32
+    device frames by ``detect_batch``, ``process_multiscale`` and ``measure_trails``."""
+    native = True
+    dtype = "float32"
+
+    def is_contiguous(self):
+        return True
+
+    def slice(self, a, b):
+        return NativeDeviceFrames(self.address_of(a), (int(b) - int(a), self.shape[1], self.shape[2]))
 
 
 class Bz2Decoder:
@@ -435,6 +491,8 @@ class Context:
                 self._end_oldest()
             for b in list(getattr(self, "_banks", ())):       # defocus banks of this context close with it
                 b.close()
+            for k in list(getattr(self, "_skies", ())):       # and so do its sky handles
+                k.close()
             self._h = None
             self._lib.lfdmi_ctx_destroy(h)
 
@@ -732,7 +790,7 @@ class Context:
         ``_batch``, which copies a non-contiguous array (``contiguous``: refused instead)."""
         if isinstance(frames, DeviceFrames):
             n, h, w = frames.shape
-            code = F32 if native_device else F32_BE
+            code = F32 if (native_device or getattr(frames, "native", False)) else F32_BE
         elif not _is_dev(frames) and isinstance(frames, np.ndarray) and frames.dtype == np.dtype(">f4"):
             if not frames.flags.c_contiguous:
                 raise ValueError("big-endian frames must be C-contiguous")
@@ -863,3 +921,78 @@ class Context:
         out = np.empty((h, w), np.uint8)
         self._chk(self._lib.lfdmi_get_stage(self._h, int(slot), int(which), int(h), int(w), _ptr(out), HOST))
         return out
+
+
+class Sky:
+    """lfdmi_sky: the sky normalisation of frames of ``shape`` on ``ctx``'s device (include/lfdmi.h: sky normalisation).  The
+    handle owns the meshes and a device buffer of ``max_frames`` normalised frames; ``Context.close()`` closes it first."""
+
+    def __init__(self, ctx, shape, max_frames=None, **params):
+        self._s = C.c_void_p()
+        self._lib = lib()
+        self.ctx = ctx
+        if not getattr(ctx, "_h", None):
+            raise ValueError("the context is closed")
+        self.shape = (int(shape[0]), int(shape[1]))
+        self.max_frames = int(ctx.max_inflight if max_frames is None else max_frames)
+        self.params = make_sky_params(**params)
+        ctx._chk(self._lib.lfdmi_sky_create(ctx._h, self.shape[0], self.shape[1], self.max_frames, C.byref(self.params),
+                                            C.byref(self._s)))
+        import weakref
+        ctx.__dict__.setdefault("_skies", weakref.WeakSet()).add(self)
+        ny, nx, nb = C.c_int32(), C.c_int32(), C.c_int64()
+        self._lib.lfdmi_sky_dims(self._s, C.byref(ny), C.byref(nx), C.byref(nb))
+        self.ny, self.nx, self.bytes = ny.value, nx.value, nb.value
+
+    def close(self):
+        if getattr(self, "_s", None):
+            self._lib.lfdmi_sky_destroy(self._s)
+            self._s = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def frames(self, n=None):
+        """The handle's device buffer as ``DeviceFrames`` (``NativeDeviceFrames``: native float32)."""
+        if not self._s:
+            raise ValueError("the sky handle is closed")
+        n = self.max_frames if n is None else int(n)
+        return NativeDeviceFrames(self._lib.lfdmi_sky_frames(self._s), (n, *self.shape))
+
+    def normalize(self, frames, out=None, meshes=False, pinned=False):
+        """Normalise ``frames`` ('<f4' / '>f4' numpy, torch CUDA float32, ``DeviceFrames`` holding big-endian data).  out: None =
+        the handle's device buffer (``frames(n)``; n <= max_frames), "inplace" for torch CUDA float32 frames, or a float32 numpy
+        array / torch CUDA tensor of the frames' shape.  Returns the SKY_DTYPE records [n], and with meshes=True also the
+        filtered sky and sigma meshes, float32 [n, ny, nx] each."""
+        if not self._s or not getattr(self.ctx, "_h", None):
+            raise ValueError("the sky handle is closed")
+        ctx = self.ctx
+        frames, code, n, h, w, loc = ctx._frames(frames, pinned, "Sky.normalize")
+        if (h, w) != self.shape:
+            raise NativeError(ERR_ARG, f"Sky.normalize: frames of {h} x {w}, the handle was made for {self.shape[0]} x {self.shape[1]}")
+        if isinstance(out, str):
+            if out != "inplace":
+                raise ValueError("out: None, 'inplace' or an array")
+            out = frames
+        out_loc = HOST
+        if out is not None:
+            if not _is_dev(out) and not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous):
+                raise TypeError("out: a C-contiguous float32 numpy array or a torch CUDA tensor")
+            if int(np.prod(tuple(out.shape))) != n * h * w:
+                raise ValueError("out does not have the frames' size")
+            out_loc = DEVICE if _is_dev(out) else HOST
+        rec = np.zeros(n, SKY_DTYPE)
+        mb = np.empty((n, self.ny, self.nx), np.float32) if meshes else None
+        ms = np.empty((n, self.ny, self.nx), np.float32) if meshes else None
+        ctx._chk(self._lib.lfdmi_sky_normalize(ctx._h, self._s, _ptr(frames), code, n, loc, _ptr(out), out_loc, _ptr(rec), _ptr(mb),
+                                               _ptr(ms)))
+        return (rec, mb, ms) if meshes else rec

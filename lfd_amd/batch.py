@@ -62,7 +62,11 @@ class BatchDetector:
     """
 
     def __init__(self, device=0, shape=(1489, 2048), inflight=32, stream=None, lanes=1, caps=None, stage_images=False,
-                 calls_in_flight=1):
+                 calls_in_flight=1, sky=None):
+        """sky: None, or a dict of lfdmi_sky_params fields ({} = the defaults): ``detect`` / ``submit`` / ``multiscale`` then
+        first normalise the frames into a ``Sky`` handle's device buffer (include/lfdmi.h: sky normalisation) and work on that
+        buffer, ``measure_trails`` measures it, and ``last_sky`` holds the records of the last call.  Needs lanes == 1 and
+        calls_in_flight == 1."""
         from concurrent.futures import ThreadPoolExecutor
         self.lanes = max(1, int(lanes))
         self.calls_in_flight = max(1, int(calls_in_flight))
@@ -92,6 +96,40 @@ class BatchDetector:
         self._last_start = 0.0
         self._spacing = 0.001
         self.shape = shape
+        self.sky, self.last_sky, self._sky_src = None, None, None
+        if sky is not None:
+            if self.lanes != 1 or self.calls_in_flight != 1:
+                raise ValueError("sky= needs lanes == 1 and calls_in_flight == 1")
+            from .sky import as_params
+            self.sky = _native.Sky(self.ctx, shape, max_frames=per, **as_params(sky))
+
+    # ---- sky normalisation in front of every call (sky=...) ------------------------------------------------------------------
+    def _drain(self):
+        for f in list(self._pending):
+            f.result()
+        self._pending = []
+        while self.ctx.calls_in_flight():
+            self.ctx._end_oldest()
+
+    def _normalized(self, frames, a, b, pinned=False):
+        """frames[a:b] normalised into the handle's buffer -> (NativeDeviceFrames, records)"""
+        self._drain()                                        # (the buffer is the pending calls' input)
+        part = frames.slice(a, b) if isinstance(frames, _native.DeviceFrames) else frames[a:b]
+        rec = self.sky.normalize(part, pinned=pinned)
+        return self.sky.frames(b - a), rec
+
+    def _sky_chunks(self, frames, call):
+        """call(buffer, a, b) on every max_frames chunk of the normalised frames; the sky records go to ``last_sky``"""
+        n = frames.shape[0]
+        outs, recs = [], []
+        for a in range(0, n, self.sky.max_frames):
+            b = min(n, a + self.sky.max_frames)
+            buf, rec = self._normalized(frames, a, b)
+            recs.append(rec)
+            outs.append(call(buf, a, b))
+        self.last_sky = np.concatenate(recs)
+        self._sky_src = frames if n <= self.sky.max_frames else None
+        return outs
 
     def close(self):
         if self.pool is not None:
@@ -108,6 +146,8 @@ class BatchDetector:
     # call k + 1 is already queued behind it, and the GPU goes from one to the other without waiting for the host.  The calls
     # still run one after the other on the GPU and their results are what the synchronous call returns.
     def _in_turn(self, method, args):
+        if self.sky is not None:
+            raise RuntimeError("detect_async / multiscale_async are not routed through sky=: use detect / submit")
         if self._turn_pool is None:
             raise RuntimeError("BatchDetector(calls_in_flight=1): use detect / multiscale")
         i = self._turn
@@ -157,10 +197,22 @@ class BatchDetector:
     def submit(self, frames, params_bright, params_dim, catalogs=None, rs=None, pinned=False):
         """``detect`` without waiting: returns a ``Pending`` (``.result()`` = ``detect``'s records).  Frames are device-resident
         (or ``PinnedBuffer`` memory with ``pinned=True``) and, with the catalogue, must stay untouched until the call has ended."""
+        if self.sky is not None:
+            if frames.shape[0] > self.sky.max_frames:
+                raise ValueError("submit with sky=: at most `inflight` frames per call (the handle's buffer)")
+            buf, self.last_sky = self._normalized(frames, 0, frames.shape[0], pinned=pinned)
+            self._sky_src = frames
+            return self._submit_ctx().detect_batch_begin(buf, params_bright, params_dim, catalogs, rs)
         return self._submit_ctx().detect_batch_begin(frames, params_bright, params_dim, catalogs, rs, pinned=pinned)
 
     def submit_multiscale(self, frames, params, rhos, dim=True, flip=True, after_bright=False):
         """``multiscale`` without waiting (device-resident frames): a ``Pending`` whose ``.result()`` is its records."""
+        if self.sky is not None:
+            if frames.shape[0] > self.sky.max_frames:
+                raise ValueError("submit_multiscale with sky=: at most `inflight` frames per call (the handle's buffer)")
+            buf, self.last_sky = self._normalized(frames, 0, frames.shape[0])
+            self._sky_src = frames
+            return self._submit_ctx().process_multiscale_begin(buf, params, rhos, dim=dim, flip=flip, after_bright=after_bright)
         return self._submit_ctx().process_multiscale_begin(frames, params, rhos, dim=dim, flip=flip, after_bright=after_bright)
 
     def enable_timing(self, on=True):
@@ -205,6 +257,9 @@ class BatchDetector:
 
     def multiscale(self, frames, params, rhos, dim=True, flip=True, after_bright=False):
         """One pass (dim or bright) with HoughLines at every rho of ``rhos`` over the batch: records [len(rhos), n]."""
+        if self.sky is not None:
+            return np.concatenate(self._sky_chunks(frames, lambda buf, a, b: self.ctx.process_multiscale(
+                buf, params, rhos, dim=dim, flip=flip, after_bright=after_bright)), axis=1)
         if self.lanes == 1:
             if self._turn_pool is not None and self._busy():
                 return self.multiscale_async(frames, params, rhos, dim, flip, after_bright).result()
@@ -219,6 +274,9 @@ class BatchDetector:
         """frames: (n, h, w) float32, numpy (staged through the library) or a torch CUDA tensor
         (used in place; must be complete on the device before the call when lanes > 1).
         catalogs: dict from synth.pack_catalogs (numpy or torch CUDA tensors)."""
+        if self.sky is not None:
+            return np.concatenate(self._sky_chunks(frames, lambda buf, a, b: self.ctx.detect_batch(
+                buf, params_bright, params_dim, self._slice_cat(catalogs, a, b), rs)))
         if self.lanes == 1:
             if self._turn_pool is not None and self._busy():
                 return self.detect_async(frames, params_bright, params_dim, catalogs, rs).result()
@@ -232,7 +290,22 @@ class BatchDetector:
 
     def measure_trails(self, frames, records, catalogs=None, rs=None, **params):
         """``Context.measure_trails`` over the batch (trail profiles of the frames whose record has found != 0), sharded like
-        ``detect``.  With calls in flight it runs after them: the calls that produced ``records`` have ended by then."""
+        ``detect``.  With calls in flight it runs after them: the calls that produced ``records`` have ended by then.
+        With ``sky=`` the normalised frames are measured.  If ``frames`` is the very object the last detect / submit call was
+        given (identity, not equality) and it fitted the handle's buffer, that buffer is measured as the call left it;
+        any other array -- an equal copy included -- is normalised again, chunk by chunk, which gives the same values.  An
+        array changed in place between the two calls must not be passed as the same object."""
+        if self.sky is not None:
+            # the frames the records describe are the normalised ones: the handle's buffer when it still holds them (the last
+            # call's frames, blotted by remove_stars as detect left them), otherwise normalised again chunk by chunk
+            self._drain()
+            if frames is self._sky_src:
+                return self.ctx.measure_trails(self.sky.frames(frames.shape[0]), records, catalogs, rs, **params)
+            keep = self.last_sky
+            res = self._sky_chunks(frames, lambda buf, a, b: self.ctx.measure_trails(buf, records[a:b], self._slice_cat(catalogs, a, b),
+                                                                                   rs, **params))
+            self.last_sky, self._sky_src = keep, None
+            return np.concatenate([r[0] for r in res]), np.concatenate([r[1] for r in res])
         if self.lanes == 1:
             for f in list(self._pending):
                 f.result()

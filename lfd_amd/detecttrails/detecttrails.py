@@ -188,6 +188,50 @@ class _DefocusTee:
         self.out.flush()
 
 
+class _SkyStage:
+    """The sky normalisation in front of detection for ``DetectTrails(normalize=True)`` (include/lfdmi.h: sky normalisation):
+    a ``Sky`` handle per (context, shape), kept while it is large enough, and the sky.txt rows."""
+
+    def __init__(self, out, params):
+        from ..sky import as_params
+        self.out, self.params, self._handles = out, as_params(params), {}
+
+    def _handle(self, ctx, shape, n):
+        key = (id(ctx), tuple(shape))
+        h = self._handles.get(key)
+        if h is None or h.ctx is not ctx or not h._s or h.max_frames < n:
+            if h is not None:
+                h.close()
+            h = self._handles[key] = _native.Sky(ctx, shape, max_frames=n, **self.params)
+        return h
+
+    def batch(self, ctx, frames, shape, n, pinned=False):
+        """n frames (pinned big-endian slots, or ``DeviceFrames``) -> (the handle's device buffer, sky records)"""
+        h = self._handle(ctx, shape, n)
+        rec = h.normalize(frames, pinned=pinned)
+        return h.frames(n), rec
+
+    def one(self, img):
+        """one host frame -> (normalised float32 copy, its sky record)"""
+        img = _np.ascontiguousarray(img, _np.float32)
+        out = _np.empty_like(img)
+        with use_context(*img.shape) as ctx:
+            rec = self._handle(ctx, img.shape, 1).normalize(img, out=out)[0]
+        return out, rec
+
+    def row(self, key, rec):
+        from ..sky import format_row
+        self.out.write(format_row(key, rec) + "\n")
+
+    def flush(self):
+        self.out.flush()
+
+    def close(self):
+        for h in self._handles.values():
+            h.close()
+        self._handles = {}
+
+
 def _load_frame(run, camcol, filter, field):
     """Frame image (float32, C-contiguous), results-row head, photoObj columns; raises like the
     reference when neither the .fits nor the .fits.bz2 exists (detecttrails.py:81-87)."""
@@ -214,15 +258,19 @@ def _log_error(errors, ids, exc, debug):
 
 
 def process_field(results, errors, run, camcol, filter, field, params_bright, params_dim,
-                  params_removestars, profiles=None, trail_params=None):
+                  params_removestars, profiles=None, trail_params=None, sky=None):
     """One frame end to end (reference: detecttrails.py:30-143): locate the frame (or its .bz2),
     read image + header + photoObj, detect, append ``run camcol filter field tai crpix1 crpix2
     crval1 crval2 cd11 cd12 cd21 cd22 x1 y1 x2 y2`` to ``results``; every exception is logged
     to ``errors`` (ids, 3-frame traceback, message) and swallowed.  ``profiles``: a file the frame's trail profile row
-    (``profile_row``) is appended to when it has a detection."""
+    (``profile_row``) is appended to when it has a detection.  ``sky``: a ``_SkyStage``; the frame is normalised first and its
+    sky.txt row written (detection and profile then refer to the normalised frame)."""
     debug = params_bright.get("debug") or params_dim.get("debug")
     try:
         img, head, cat = _load_frame(run, camcol, filter, field)
+        if sky is not None:
+            img, srec = sky.one(img)
+            sky.row((run, camcol, filter, field), srec)
         detection, res, rec = process_frame_arrays(img, cat, filter, params_bright, params_dim,
                                                    params_removestars)
         if detection:
@@ -351,11 +399,14 @@ def _frame_shape(keys):
     return 1489, 2048
 
 
-def process_loaded(results, errors, loaded, params_bright, params_dim, params_removestars, profiles=None, trail_params=None):
+def process_loaded(results, errors, loaded, params_bright, params_dim, params_removestars, profiles=None, trail_params=None, sky=None):
     """process_fields_batched for a chunk the loader has read (``loader.Loaded``): the frames that sit in pinned memory go to
     the GPU as contiguous same-filter slices of that memory with the matching rows of the padded catalogue arrays (no copy
     of a frame on the host, no per-frame Python), the others take the per-frame path; rows and errors entries come out in
-    the caller's order, each frame under its own try (detecttrails.py:119-139)."""
+    the caller's order, each frame under its own try (detecttrails.py:119-139).  ``sky``: a
+    ``_SkyStage``: every slice is normalised into the handle's device buffer first (the pinned big-endian slots go in as they
+    are), detection and measurement run on that buffer, and one sky.txt row per normalised frame is written, in the caller's
+    order, ahead of the frame's results row."""
     import time
     from .loader import header_values
     trace = os.environ.get("LFD_LOADER_TRACE") == "1"
@@ -365,7 +416,14 @@ def process_loaded(results, errors, loaded, params_bright, params_dim, params_re
     n = len(loaded.keys)
     rows = [None] * n
     meas = [None] * n                                 # (trail record, profile) or the measurement's exception
+    srecs = [None] * n                                # sky records of the frames that were normalised
     tp = trail_params or {}
+
+    def normalised(i, img):
+        if sky is None:
+            return img
+        img, srecs[i] = sky.one(img)
+        return img
 
     def measure_one(i, img, cat, flt):
         if profiles is not None and rows[i]["found"]:
@@ -399,14 +457,23 @@ def process_loaded(results, errors, loaded, params_bright, params_dim, params_re
             rs = _rs_struct(flt, params_removestars)
             with use_context(h, w, inflight=min(256, len(idx))) as ctx:
                 t_g = time.perf_counter()
-                if loaded.device is not None:                 # decompressed on the GPU and still there
+                buf = None
+                if sky is not None:                           # the upload happens here; detection then reads the handle's buffer
+                    src = loaded.device.slice(a, b) if loaded.device is not None else loaded.buffer[a:b]
+                    buf, sr = sky.batch(ctx, src, (h, w), len(idx), pinned=loaded.device is None)
+                    for j, i in enumerate(idx):
+                        srecs[i] = sr[j]
+                    recs = ctx.detect_batch(buf, params_bright, params_dim, packed, rs)
+                elif loaded.device is not None:               # decompressed on the GPU and still there
                     recs = ctx.detect_batch(loaded.device.slice(a, b), params_bright, params_dim, packed, rs)
                 else:
                     recs = ctx.detect_batch(loaded.buffer[a:b], params_bright, params_dim, packed, rs, pinned=True)
                 t_gpu += time.perf_counter() - t_g
                 if profiles is not None:
                     try:                                      # device frames: swapped (and blotted) in place by the call above
-                        if loaded.device is not None:
+                        if buf is not None:
+                            tr, pr = ctx.measure_trails(buf, recs, packed, rs, **tp)
+                        elif loaded.device is not None:
                             tr, pr = ctx.measure_trails(loaded.device.slice(a, b), recs, packed, rs, native_device=True, **tp)
                         else:
                             tr, pr = ctx.measure_trails(loaded.buffer[a:b], recs, packed, rs, pinned=True, **tp)
@@ -422,7 +489,7 @@ def process_loaded(results, errors, loaded, params_bright, params_dim, params_re
                 try:
                     if loaded.device is not None:             # (the frames are wherever the failed call left them: no second source)
                         raise
-                    img = loaded.buffer[sl].astype(_np.float32)
+                    img = normalised(i, loaded.buffer[sl].astype(_np.float32))
                     rows[i] = process_frame_arrays(img, loaded.cat_of(i), flt, params_bright, params_dim, params_removestars)[2]
                     measure_one(i, img, loaded.cat_of(i), flt)
                 except Exception as e:  # noqa: BLE001
@@ -430,12 +497,15 @@ def process_loaded(results, errors, loaded, params_bright, params_dim, params_re
     for i in range(n):
         if rows[i] is None and loaded.array[i] is not None:      # not a plain float32 image of the chunk's shape, or an oversized catalogue
             try:
-                rows[i] = process_frame_arrays(loaded.array[i], loaded.cat_of(i), loaded.keys[i][2], params_bright, params_dim,
+                img = normalised(i, loaded.array[i])
+                rows[i] = process_frame_arrays(img, loaded.cat_of(i), loaded.keys[i][2], params_bright, params_dim,
                                                params_removestars)[2]
-                measure_one(i, loaded.array[i], loaded.cat_of(i), loaded.keys[i][2])
+                measure_one(i, img, loaded.cat_of(i), loaded.keys[i][2])
             except Exception as e:  # noqa: BLE001
                 rows[i] = e
     for i, key in enumerate(loaded.keys):
+        if sky is not None and srecs[i] is not None:
+            sky.row(key, srecs[i])
         try:
             rec = rows[i]
             if isinstance(rec, Exception):
@@ -479,6 +549,12 @@ class DetectTrails:
     chi2 dof chi2_focus model_ofwhm model_depth``.  ``defocus_params`` (dict): heights, radii, seeings, instrument, ovs,
     max_shift, delta_chi2.  The bank is built once per process; rank files, resume and ``Jobs`` treat defocus.txt like
     profiles.txt.
+    ``normalize=True`` (default off): every frame goes through the sky normalisation first (include/lfdmi.h: sky normalisation;
+    ``sky_params``: dict or ``lfd_amd.sky.SkyParams``) -- for frames that still carry their sky (fpC files, raw exposures).  The
+    loader's big-endian pinned slots are normalised into a device buffer and detected there.  ``sky_file`` (default
+    ``<savepath>/sky.txt``) gets one row per frame that loaded: ``run camcol filter field status sky sigma gain n_empty``,
+    written ahead of the chunk's progress marks; rank files, resume and ``Jobs`` treat it like results.txt.  Profiles and
+    defocus fits then refer to the normalised frame: flux = value / gain + sky.
     """
 
     _FILTERS = ('u', 'g', 'r', 'i', 'z')
@@ -496,6 +572,12 @@ class DetectTrails:
         self.trail_profiles = bool(kwargs.get("trail_profiles", False)) or self.defocus
         self.profiles = kwargs.get("profiles", os.path.join(save, "profiles.txt"))
         self.trail_params = dict(kwargs.get("trail_params") or {})
+        self.normalize = bool(kwargs.get("normalize", False))
+        self.sky_file = kwargs.get("sky_file", os.path.join(save, "sky.txt"))
+        from ..sky import as_params
+        self.sky_params = as_params(kwargs.get("sky_params"))
+        if self.normalize:
+            _native.make_sky_params(**self.sky_params)          # (unknown names raise here, not per frame)
         if self.trail_profiles:
             _native.make_trail_params(**self.trail_params)      # (unknown names raise here, not per frame)
         if self.defocus:
@@ -649,10 +731,14 @@ class DetectTrails:
         with open(self.results + suffix, "a") as results, open(self.errors + suffix, "a") as errors, \
                 open(progress_path, "w" if fresh else "a") as progress, \
                 (open(self.profiles + suffix, "a") if self.trail_profiles else contextlib.nullcontext()) as profiles, \
-                (open(self.defocus_file + suffix, "a") if self.defocus else contextlib.nullcontext()) as defocus_out:
+                (open(self.defocus_file + suffix, "a") if self.defocus else contextlib.nullcontext()) as defocus_out, \
+                (open(self.sky_file + suffix, "a") if self.normalize else contextlib.nullcontext()) as sky_out:
             if self.defocus:
                 profiles = _DefocusTee(profiles, defocus_out, self.defocus_params, self.trail_params)
             prof_kw = {"profiles": profiles, "trail_params": self.trail_params} if self.trail_profiles else {}
+            sky = _SkyStage(sky_out, self.sky_params) if self.normalize else None
+            if sky is not None:
+                prof_kw["sky"] = sky
             if fresh:
                 progress.write(header + "\n")
                 progress.flush()
@@ -662,6 +748,8 @@ class DetectTrails:
                 errors.flush()
                 if profiles is not None:
                     profiles.flush()
+                if sky is not None:
+                    sky.flush()
                 progress.write("".join("%s %s %s %s\n" % tuple(k) for k in done_keys))
                 progress.flush()
 
@@ -669,6 +757,8 @@ class DetectTrails:
                 for key in keys:
                     process_field(results, errors, *key, self.params_bright, self.params_dim, self.params_removestars, **prof_kw)
                     mark([key])
+                if sky is not None:
+                    sky.close()
                 self.last_stats["seconds"] = time.perf_counter() - t_start
                 return
             # a chunk = one GPU call: 64 frames keep the link and the GPU busy for plain files; a selection that exists only as
@@ -717,5 +807,7 @@ class DetectTrails:
                                   (i, 1e3 * (t1 - t0), 1e3 * (time.perf_counter() - t1)), flush=True)
             finally:
                 self.last_stats["bz2"] = dict(loader.bz2_stats)
+                if sky is not None:
+                    sky.close()
                 loader.close()
                 self.last_stats["seconds"] = time.perf_counter() - t_start
