@@ -665,6 +665,48 @@ void *lfdmi_sky_frames(lfdmi_sky *sky);
 int lfdmi_sky_normalize(lfdmi_ctx *ctx, lfdmi_sky *sky, const void *frames, int dtype, int n, int loc, void *out, int out_loc,
                         lfdmi_sky_frame *rec, float *mesh_sky, float *mesh_sigma);
 
+/* ---- trail injection --------------------------------------------------------------------------------------------------------
+ * lfdmi_inject_trails adds model trails of known line, extent, cross-section and brightness to frames, in place: the input of
+ * an efficiency measurement (inject, detect, count what comes back; lfd_amd/recovery.py).  The reference has no such step.  The
+ * procedure below is the definition; tests/inject_ref.py restates it in numpy and the device reproduces it bit for bit.
+ *
+ * 1. Coordinates are the detection records': x = column, y = row of the flipped frame, so (x, y) is buffer row H-1-y.  A trail's
+ *    line is x cos(theta) + y sin(theta) = rho, as lfdmi_result.rho / theta and lfdmi_measure_trails carry it.  c = cos(theta),
+ *    s = sin(theta) are taken once on the host (C library, double); the line is a foot point f = (rho c, rho s) and a direction
+ *    d = (-s, c).  The device evaluates no transcendental function.
+ * 2. Tables.  n_tables rows of table_len = 2M+1 float32 (row-major); node k of a row T sits at offset (k - M) table_step px from
+ *    the line: the cross-section as the sky shows it, before the pixel (the pixel integration is step 4).  T[2M+1] is read as T[2M].
+ * 3. Value at a point (px, py), for a trail (table T, rho, theta, t0, t1):
+ *        u = px c + py s - rho;   t = (px - f.x) d.x + (py - f.y) d.y        (double, left to right)
+ *    t < t0 or t > t1: 0 (a non-finite t0 / t1 means unbounded on that side).  Otherwise q = u / table_step + M (double);
+ *    q < 0 or q > 2M: 0.  Otherwise k = floor(q), a = (float)(q - k) and
+ *        value = T[k] + a (T[k+1] - T[k])                                    (float32, each operation rounded, no FMA).
+ * 4. Value added to pixel (x, y) by one trail: with ss = subsample and o_m = (m + 1/2) / ss - 1/2 (double), the point values at
+ *    (x + o_j, y + o_i) are summed in double, i = 0 .. ss-1 the outer and j = 0 .. ss-1 the inner loop, into acc;
+ *        add = (float)(amplitude acc / (ss ss))                             (double, left to right, then rounded once).
+ *    add != 0: pixel = pixel + add, one float32 addition.  add == 0: the pixel is not written (its bits stay, -0 and NaN
+ *    payloads included).
+ * 5. Several trails on one frame are applied in ascending index order, so the result is defined bit for bit where trails cross.
+ *
+ * The device culls 64 x 16 pixel tiles against every trail's band (|u| <= M table_step and t in [t0, t1], widened by the
+ * tile's half extent along the normal and along the line) and launches only over the surviving (frame, tile) pairs: the work
+ * follows the pixels the trails reach, not the frame, and a tile without a trail causes no global write. */
+#define LFDMI_INJECT_MAX_TABLE 4097   /* largest table_len (it is kept in LDS) */
+typedef struct {
+    int32_t frame;           /* 0 .. n-1 */
+    int32_t table;           /* 0 .. n_tables-1 */
+    double rho, theta;       /* the line (flipped frame); finite, |rho| <= 1e9 */
+    double t0, t1;           /* extent along d from f; non-finite: unbounded on that side */
+    double amplitude;        /* scale factor on the table; finite */
+} lfdmi_inject_trail;
+/* frames: n frames of h x w, LFDMI_F32 only (LFDMI_F32_BE is refused), loc LFDMI_DEVICE (modified in place), LFDMI_HOST or
+ * LFDMI_HOST_PINNED (the frames that carry a trail are uploaded, rendered and copied back).  trails: n_trails records (host);
+ * tables: n_tables x table_len float32 (host), table_len odd, 1 .. LFDMI_INJECT_MAX_TABLE; table_step > 0 px; subsample 1 .. 8.
+ * Bad arguments: LFDMI_ERR_ARG, and no pixel is touched.  The call refuses while calls are in flight, runs on the context's
+ * stream and waits for it once, at its end; its device memory is taken from the stream's pool and returned before that. */
+int lfdmi_inject_trails(lfdmi_ctx *ctx, void *frames, int dtype, int n, int h, int w, int loc, const lfdmi_inject_trail *trails,
+                        int n_trails, const float *tables, int n_tables, int table_len, double table_step, int subsample);
+
 #ifdef __cplusplus
 }
 #endif

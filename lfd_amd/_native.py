@@ -39,6 +39,7 @@ SYMBOLS = (
     "lfdmi_default_defocus_params", "lfdmi_defocus_bank_create", "lfdmi_defocus_bank_destroy", "lfdmi_defocus_bank_dims",
     "lfdmi_defocus_bank_read", "lfdmi_fit_defocus",
     "lfdmi_default_sky_params", "lfdmi_sky_create", "lfdmi_sky_destroy", "lfdmi_sky_dims", "lfdmi_sky_frames", "lfdmi_sky_normalize",
+    "lfdmi_inject_trails",
 )
 
 
@@ -173,6 +174,12 @@ def make_sky_params(**params):
     return p
 
 
+# lfdmi_inject_trail: one record per trail of lfdmi_inject_trails (include/lfdmi.h: trail injection)
+INJECT_DTYPE = np.dtype([("frame", "<i4"), ("table", "<i4"), ("rho", "<f8"), ("theta", "<f8"), ("t0", "<f8"), ("t1", "<f8"),
+                         ("amplitude", "<f8")])
+INJECT_MAX_TABLE = 4097
+
+
 _lib = None
 
 
@@ -228,6 +235,8 @@ def lib():
         _lib.lfdmi_sky_frames.argtypes = [C.c_void_p]
         _lib.lfdmi_sky_normalize.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                              C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.lfdmi_inject_trails.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                             C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int]
     return _lib
 
 
@@ -905,6 +914,26 @@ class Context:
         cbh = np.empty((n, bank.n_h + 1), np.float32) if chi2_by_height else None
         self._chk(self._lib.lfdmi_fit_defocus(self._h, bank._b, _ptr(tr), _ptr(prof), n, _ptr(see), _ptr(out), _ptr(cbh)))
         return (out, cbh) if chi2_by_height else out
+
+    # -- trail injection (lfdmi_inject_trails) ----------------------------------------------------------------------------------
+    def inject_trails(self, frames, trails, tables, table_step, subsample=4, pinned=False):
+        """Add model trails to ``frames`` in place (include/lfdmi.h: trail injection).  frames: float32 (n, h, w) or (h, w), a
+        torch CUDA tensor (rendered where it is), ``NativeDeviceFrames`` or a C-contiguous numpy array (the frames that carry a
+        trail are uploaded, rendered and copied back; ``pinned=True``: the array lives in ``PinnedBuffer`` memory); big-endian
+        frames are refused.  trails: INJECT_DTYPE records (or anything ``np.asarray`` turns into them); tables: float32
+        (n_tables, 2M+1) or one row, node k at (k - M) * table_step px from the line.  Returns ``frames``."""
+        if not _is_dev(frames) and not (isinstance(frames, np.ndarray) and frames.flags.c_contiguous and frames.flags.writeable):
+            raise ValueError("inject_trails needs a writable C-contiguous array (it is modified in place)")
+        fr, code, n, h, w, loc = self._frames(frames, pinned, "inject_trails")
+        tr = np.ascontiguousarray(trails, INJECT_DTYPE).reshape(-1)
+        tab = np.ascontiguousarray(tables, np.float32)
+        if tab.ndim == 1:
+            tab = tab[None]
+        if tab.ndim != 2:
+            raise ValueError("tables: (n_tables, 2M+1) float32")
+        self._chk(self._lib.lfdmi_inject_trails(self._h, _ptr(fr), code, n, h, w, loc, _ptr(tr), len(tr), _ptr(tab), tab.shape[0],
+                                                tab.shape[1], C.c_double(float(table_step)), int(subsample)))
+        return frames
 
     def pinned_buffer(self, nbytes):
         """Page-locked host memory next to this context's GPU (lfdmi_host_alloc) as a ``PinnedBuffer``."""

@@ -1,0 +1,276 @@
+"""Injection and recovery: add model trails of known line and brightness to frames, detect, and count what comes back -- the
+detector's efficiency as a function of the trail's peak (include/lfdmi.h: trail injection).
+
+    python -m lfd_amd.recovery --synth K0:N --peaks 0.05,0.1,0.2,5 --out DIR
+
+The plan (``draw_trails``), the matching (``match``) and the rows use integer RNG draws and IEEE + - * / sqrt only -- cos and sin
+come from ``cos_sin`` below, a fixed sequence of multiplications and additions -- so every machine draws the same plan and
+judges a detection the same way.
+"""
+import math
+
+import numpy as np
+
+from . import _native
+from . import inject as _inject
+
+PLAN_DTYPE = np.dtype([("frame", "<i4"), ("peak", "<f8"), ("rho", "<f8"), ("theta", "<f8"), ("t0", "<f8"), ("t1", "<f8")])
+ROW_DTYPE = np.dtype([("frame", "<i4"), ("peak", "<f8"), ("rho", "<f8"), ("theta", "<f8"), ("length", "<f8"), ("found", "<i4"),
+                      ("matched", "<i4"), ("d_rho", "<f8"), ("d_theta", "<f8"), ("fwhm", "<f8")])
+ROW_COLUMNS = ROW_DTYPE.names
+# The matching tolerance in Hough cells (1 degree, houghMethod px): the smallest of 1, 1.5, 2, 3 with which every trail of the
+# calibration set that the oracle detects is matched (injection and recovery).
+K_MATCH = 1.0
+THETA_STEPS = 4096
+
+_HALF_PI = math.pi / 2
+_SIN_C = [(-1.0) ** k / float(math.factorial(2 * k + 1)) for k in range(14)]
+_COS_C = [(-1.0) ** k / float(math.factorial(2 * k)) for k in range(14)]
+
+
+def cos_sin(theta):
+    """(cos, sin) of theta in [0, pi] (scalars or arrays) from the Taylor series about pi/2, 14 terms each in Horner form: the
+    truncation is below 1e-17, the rounding a few ulp, and the operations are the same on every machine."""
+    x = np.asarray(theta, np.float64) - _HALF_PI
+    x2 = x * x
+    sn = np.zeros_like(x2)
+    cs = np.zeros_like(x2)
+    for k in range(13, -1, -1):
+        sn = sn * x2 + _SIN_C[k]
+        cs = cs * x2 + _COS_C[k]
+    return -(sn * x), cs              # cos(theta) = -sin(theta - pi/2), sin(theta) = cos(theta - pi/2)
+
+
+def draw_trails(n_frames, shape, seed, peaks, length=None):
+    """One trail per frame through the frame's interior, as PLAN_DTYPE records: a point with integer coordinates in the middle
+    half of the frame, theta = j pi / THETA_STEPS (j an integer draw) rounded to float32 and widened, rho = the line through the
+    point.  peaks: frame i takes peaks[i % len(peaks)].  length None: the trail crosses the whole frame (t0 / t1 infinite);
+    otherwise it extends length / 2 px either side of the point."""
+    h, w = shape
+    rng = np.random.default_rng(np.random.PCG64(int(seed)))
+    x0 = (w // 4 + rng.integers(0, max(1, w // 2), n_frames)).astype(np.float64)
+    y0 = (h // 4 + rng.integers(0, max(1, h // 2), n_frames)).astype(np.float64)
+    j = rng.integers(0, THETA_STEPS, n_frames)
+    theta = (j.astype(np.float64) * (math.pi / THETA_STEPS)).astype(np.float32).astype(np.float64)
+    c, s = cos_sin(theta)
+    plan = np.zeros(n_frames, PLAN_DTYPE)
+    plan["frame"] = np.arange(n_frames)
+    plan["peak"] = [float(peaks[i % len(peaks)]) for i in range(n_frames)]
+    plan["rho"] = x0 * c + y0 * s
+    plan["theta"] = theta
+    if length is None:
+        plan["t0"], plan["t1"] = -np.inf, np.inf
+    else:
+        tm = (x0 - plan["rho"] * c) * -s + (y0 - plan["rho"] * s) * c
+        plan["t0"], plan["t1"] = tm - 0.5 * float(length), tm + 0.5 * float(length)
+    return plan
+
+
+def plan_checksum(plan):
+    """SHA-256 of the plan's bytes (tests/golden/inject_plan.json)"""
+    import hashlib
+    return hashlib.sha256(np.ascontiguousarray(plan, PLAN_DTYPE).tobytes()).hexdigest()
+
+
+def to_inject(plan, table=0):
+    """PLAN_DTYPE -> the INJECT_DTYPE records of ``Context.inject_trails``: amplitude = peak (tables of peak 1)"""
+    tr = np.zeros(len(plan), _native.INJECT_DTYPE)
+    for k in ("frame", "rho", "theta", "t0", "t1"):
+        tr[k] = plan[k]
+    tr["table"] = table
+    tr["amplitude"] = plan["peak"]
+    return tr
+
+
+def extent(rho, theta, t0, t1, shape):
+    """(ta, tb): the part of [t0, t1] on which the line's point f + t d lies inside the frame [0, W-1] x [0, H-1]; ta > tb when
+    there is none.  Scalars."""
+    h, w = shape
+    c, s = (float(v) for v in cos_sin(theta))
+    fx, fy, dx, dy = rho * c, rho * s, -s, c
+    ta = t0 if np.isfinite(t0) else -np.inf
+    tb = t1 if np.isfinite(t1) else np.inf
+    for f, d, top in ((fx, dx, w - 1.0), (fy, dy, h - 1.0)):
+        if d == 0.0:
+            if f < 0.0 or f > top:
+                return 1.0, 0.0
+            continue
+        a, b = (0.0 - f) / d, (top - f) / d
+        ta, tb = max(ta, min(a, b)), min(tb, max(a, b))
+    return ta, tb
+
+
+def match(records, trails, params_bright, params_dim, k=K_MATCH, shape=None):
+    """Is the detection record of a trail's frame the injected trail?  records: RESULT_DTYPE, one per frame; trails: PLAN_DTYPE
+    records with theta in [0, pi] (what ``draw_trails`` gives; ``cos_sin`` covers that range only); shape: the frames' (h, w).
+    A record matches when it has found != 0, |d_theta| <= k degrees and |d_rho| <= k * houghMethod of the pass that found it (found 1: params_bright, 2: params_dim): k Hough cells either way.
+    d_theta = theta_detected - theta_injected; d_rho = the distance of the injected extent's middle point from the detected
+    line, along the detected normal.  A detected line near theta = 0 / pi may carry the other orientation: (rho, theta) and
+    (-rho, theta -+ pi) are one line, so |d_theta| > pi/2 is folded by pi and d_rho changes sign with it.
+    Returns (matched bool, d_rho, d_theta, length); d_rho / d_theta are NaN where nothing was found."""
+    if shape is None:
+        raise ValueError("match needs the frames' shape")
+    n = len(trails)
+    if n and not ((trails["theta"] >= 0) & (trails["theta"] <= math.pi)).all():
+        raise ValueError("match needs trails with theta in [0, pi]")
+    matched = np.zeros(n, bool)
+    d_rho = np.full(n, np.nan)
+    d_theta = np.full(n, np.nan)
+    length = np.zeros(n)
+    for i, tr in enumerate(trails):
+        rho, theta = float(tr["rho"]), float(tr["theta"])
+        ta, tb = extent(rho, theta, float(tr["t0"]), float(tr["t1"]), shape)
+        length[i] = max(0.0, tb - ta)
+        rec = records[int(tr["frame"])]
+        found = int(rec["found"])
+        if found == 0 or not ta <= tb:
+            continue
+        c, s = (float(v) for v in cos_sin(theta))
+        tm = 0.5 * (ta + tb)
+        mx, my = rho * c + tm * -s, rho * s + tm * c
+        thd = float(rec["theta"])
+        cd, sd = (float(v) for v in cos_sin(thd))
+        dist = mx * cd + my * sd - float(rec["rho"])
+        dth = thd - theta
+        if dth > _HALF_PI:
+            dth, dist = dth - math.pi, -dist
+        elif dth < -_HALF_PI:
+            dth, dist = dth + math.pi, -dist
+        d_rho[i], d_theta[i] = dist, dth
+        cell = float((params_bright if found == 1 else params_dim)["houghMethod"])
+        matched[i] = abs(dth) <= k * (math.pi / 180) and abs(dist) <= k * cell
+    return matched, d_rho, d_theta, length
+
+
+def make_rows(records, trails, params_bright, params_dim, shape, k=K_MATCH, measured=None):
+    """One ROW_DTYPE row per injected trail from its frame's detection record (and, when given, the TRAIL_DTYPE records of
+    ``measure_trails``: fwhm of a measured trail, else NaN)."""
+    matched, d_rho, d_theta, length = match(records, trails, params_bright, params_dim, k=k, shape=shape)
+    rows = np.zeros(len(trails), ROW_DTYPE)
+    for key in ("frame", "peak", "rho", "theta"):
+        rows[key] = trails[key]
+    rows["length"] = length
+    rows["found"] = [int(records[int(t["frame"])]["found"]) for t in trails]
+    rows["matched"] = matched
+    rows["d_rho"], rows["d_theta"] = d_rho, d_theta
+    rows["fwhm"] = np.nan
+    if measured is not None:
+        for i, t in enumerate(trails):
+            m = measured[int(t["frame"])]
+            if int(m["status"]) == _native.TRAIL_OK:
+                rows["fwhm"][i] = float(m["fwhm"])
+    return rows
+
+
+def run(ctx, frames, cats, rs, trails, tables, table_step, params_bright=None, params_dim=None, subsample=4, profiles=False,
+        k=K_MATCH):
+    """Copy ``frames`` ((n, h, w) float32 numpy or torch CUDA), inject the plan ``trails`` (tables of peak 1: see
+    ``inject.normalise_peak``), run ``detect_batch`` and match: ROW_DTYPE rows, one per trail.  cats: the frames' catalogues
+    (a list of dicts, a packed dict or None) and rs their remove_stars parameters; profiles=True also runs ``measure_trails``
+    and fills fwhm."""
+    from .catalogs import pack_catalogs
+    from .detecttrails import default_params
+    pb, pd, _ = default_params()
+    pb = params_bright or pb
+    pd = params_dim or pd
+    work = frames.clone() if _native._is_dev(frames) else np.array(frames, np.float32, order="C")
+    n, h, w = work.shape
+    packed = pack_catalogs(list(cats)) if isinstance(cats, (list, tuple)) else cats
+    ctx.inject_trails(work, to_inject(trails), np.asarray(tables, np.float32), table_step, subsample=subsample)
+    recs = ctx.detect_batch(work, pb, pd, packed, rs if packed is not None else None)
+    measured = None
+    if profiles:
+        measured, _ = ctx.measure_trails(work, recs, packed, rs if packed is not None else None)
+    return make_rows(recs, trails, pb, pd, (h, w), k=k, measured=measured)
+
+
+def wilson(recovered, n, z=1.0):
+    """Wilson score interval of recovered / n at z standard deviations: (lo, hi); (nan, nan) for n = 0"""
+    if n == 0:
+        return float("nan"), float("nan")
+    p = recovered / n
+    den = 1.0 + z * z / n
+    mid = (p + z * z / (2.0 * n)) / den
+    half = z * math.sqrt(p * (1.0 - p) / n + z * z / (4.0 * n * n)) / den
+    return mid - half, mid + half
+
+
+def completeness(rows, edges, z=1.0):
+    """Per peak bin [edges[i], edges[i+1]): n, recovered (matched rows), efficiency and its Wilson interval at z sigmas"""
+    out = []
+    for lo, hi in zip(edges[:-1], edges[1:]):
+        sel = (rows["peak"] >= lo) & (rows["peak"] < hi)
+        n, r = int(sel.sum()), int(rows["matched"][sel].sum())
+        wl, wh = wilson(r, n, z)
+        out.append({"lo": float(lo), "hi": float(hi), "n": n, "recovered": r, "efficiency": r / n if n else float("nan"),
+                    "wilson_lo": wl, "wilson_hi": wh})
+    return out
+
+
+def write_recovery(path, rows):
+    """recovery.txt: a header line, then one row per injected trail (floats with repr, so that read_recovery returns them)"""
+    with open(path, "w") as f:
+        f.write(" ".join(ROW_COLUMNS) + "\n")
+        for r in rows:
+            f.write(" ".join(str(int(r[k])) if ROW_DTYPE[k].kind == "i" else repr(float(r[k])) for k in ROW_COLUMNS) + "\n")
+
+
+def read_recovery(path):
+    rows = []
+    with open(path) as f:
+        for ln in f:
+            parts = ln.split()
+            if not parts or parts[0] == ROW_COLUMNS[0]:
+                continue
+            rows.append(tuple(int(v) if ROW_DTYPE[k].kind == "i" else float(v) for k, v in zip(ROW_COLUMNS, parts)))
+    return np.array(rows, ROW_DTYPE)
+
+
+def peak_edges(peaks):
+    """bin edges that put every distinct peak into a bin of its own"""
+    p = sorted(set(float(v) for v in peaks))
+    mids = [0.5 * (a + b) for a, b in zip(p[:-1], p[1:])]
+    return [0.0] + mids + [math.inf]
+
+
+def format_table(table):
+    lines = ["%10s %10s %6s %9s %10s %9s %9s" % ("peak_lo", "peak_hi", "n", "recovered", "efficiency", "wilson_lo", "wilson_hi")]
+    for b in table:
+        lines.append("%10.4g %10.4g %6d %9d %10.4f %9.4f %9.4f" % (b["lo"], b["hi"], b["n"], b["recovered"], b["efficiency"],
+                                                                  b["wilson_lo"], b["wilson_hi"]))
+    return "\n".join(lines)
+
+
+def main(argv=None):
+    import argparse
+    import os
+    from . import synth
+    from .detecttrails import default_params
+    ap = argparse.ArgumentParser(description="inject model trails into synthetic frames, detect, print the completeness table")
+    ap.add_argument("--synth", required=True, metavar="K0:N", help="synthetic frames K0 .. K0+N-1 (those without a streak of their own)")
+    ap.add_argument("--peaks", required=True, help="comma-separated trail peaks in frame units")
+    ap.add_argument("--out", required=True, help="directory for recovery.txt")
+    ap.add_argument("--sigma", type=float, default=2.0, help="Gaussian cross-section sigma in px")
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--profiles", action="store_true", help="also measure the recovered trails' fwhm")
+    a = ap.parse_args(argv)
+    k0, n = (int(v) for v in a.synth.split(":"))
+    peaks = [float(v) for v in a.peaks.split(",")]
+    frames, cats, truths = synth.make_frames(k0, n, with_truth=True)
+    keep = [i for i, t in enumerate(truths) if t["streak"] == "none"]
+    if not keep:
+        raise SystemExit("no frame without a streak of its own in that range")
+    frames, cats = np.ascontiguousarray(frames[keep]), [cats[i] for i in keep]
+    pb, pd, prs = default_params()
+    rs = _native.make_rs_params("r", **{k: v for k, v in prs.items() if k != "debug"})
+    table, step = _inject.gaussian_table(a.sigma)
+    plan = draw_trails(len(keep), frames.shape[1:], a.seed, peaks)
+    with _native.Context(0, frames.shape[1], frames.shape[2], 16) as ctx:
+        rows = run(ctx, frames, cats, rs, plan, _inject.normalise_peak(table), step, pb, pd, profiles=a.profiles)
+    os.makedirs(a.out, exist_ok=True)
+    write_recovery(os.path.join(a.out, "recovery.txt"), rows)
+    print(format_table(completeness(rows, peak_edges(peaks))))
+
+
+if __name__ == "__main__":
+    main()
