@@ -20,6 +20,7 @@ import numpy as _np
 
 from .. import _native
 from . import fitslite, sdssfiles
+from .loader import card_value, header_end, header_values
 from .processfield import get_context, use_context, setup_debug, check_theta, dictify_hough  # noqa: F401
 from .removestars import read_photoObj_arrays
 
@@ -53,6 +54,20 @@ def _rs_struct(filter, params_removestars):
     return _native.make_rs_params(filter, **p)
 
 
+def _detection(rec, shape):
+    """One frame's detection record -> ``(detection, res_dict_or_None, record)``; a frame that failed on the device raises what
+    the reference would have raised (detecttrails.py:126-131)."""
+    status = int(rec["status"])
+    if status == _native.ERR_NOLINES:
+        raise TypeError("'NoneType' object is not subscriptable")  # HoughLines gave None
+    if status:
+        raise _native.NativeError(status, "frame failed on the device")
+    if rec["found"]:
+        # coordinates the way the reference computes them: numpy float32 scalars
+        return True, dictify_hough(shape, (_np.float32(rec["rho"]), _np.float32(rec["theta"]))), rec
+    return False, None, rec
+
+
 def process_frame_arrays(img, cat, filter, params_bright, params_dim, params_removestars):
     """The hot part of process_field (detecttrails.py:119-131) on arrays.
 
@@ -61,29 +76,11 @@ def process_frame_arrays(img, cat, filter, params_bright, params_dim, params_rem
     """
     if img.dtype != _np.float32 or not img.flags.c_contiguous:
         raise TypeError("process_frame_arrays needs a C-contiguous float32 frame")
-    packed = rs = None
-    if cat is not None and len(cat["NOBSERVE"]):
-        from .removestars import _check_finite
-        _check_finite(cat)
-        n = len(cat["NOBSERVE"])
-        packed = {"count": _np.array([n], _np.int32)}
-        for key in ("ROWC", "COLC", "PSFMAG", "PETROTH90"):
-            packed[key] = _np.ascontiguousarray(cat[key], _np.float32).reshape(1, n, 5)
-        for key in ("NOBSERVE", "NDETECT"):
-            packed[key] = _np.ascontiguousarray(cat[key], _np.int32).reshape(1, n)
-        rs = _rs_struct(filter, params_removestars)
+    packed = _pack_one(cat)
+    rs = _rs_struct(filter, params_removestars) if packed is not None else None
     with use_context(*img.shape) as ctx:
         rec = ctx.detect_batch(img, params_bright, params_dim, packed, rs)[0]
-    status = int(rec["status"])
-    if status == _native.ERR_NOLINES:
-        raise TypeError("'NoneType' object is not subscriptable")  # HoughLines gave None
-    if status:
-        raise _native.NativeError(status, "frame failed on the device")
-    if rec["found"]:
-        # coordinates the way the reference computes them: numpy float32 scalars
-        res = dictify_hough(img.shape, (_np.float32(rec["rho"]), _np.float32(rec["theta"])))
-        return True, res, rec
-    return False, None, rec
+    return _detection(rec, img.shape)
 
 
 def _pack_one(cat):
@@ -129,18 +126,6 @@ def profile_row(key, trail, profile):
     return " ".join([" ".join(str(x) for x in key)] + vals) + "\n"
 
 
-def _write_profile(profiles, errors, key, meas, debug):
-    """the frame's profiles row, or its errors entry when the measurement raised (results.txt is written before, untouched)"""
-    try:
-        if isinstance(meas, Exception):
-            raise meas
-        profiles.write(profile_row(key, *meas))
-        if isinstance(profiles, _DefocusTee):
-            profiles.add(key, *meas)
-    except Exception as e:  # noqa: BLE001
-        _log_error(errors, key, e, debug)
-
-
 _BANKS = {}   # (device, params) -> (Context, DefocusBank): the defocus bank is built once per process
 
 
@@ -162,19 +147,19 @@ def defocus_bank(defocus_params=None, trail_params=None):
 
 
 class _DefocusTee:
-    """profiles.txt with defocus.txt beside it: every profiles row written is also fitted (include/lfdmi.h: defocus fit); the
-    rows added since the last ``flush`` are fitted in one call and their defocus rows written in the same order."""
+    """What the drivers write trail profiles to.  ``add`` appends the frame's ``profile_row`` to profiles.txt; with ``out``
+    (defocus.txt beside it) every row is also fitted (include/lfdmi.h: defocus fit): the rows added since the last ``flush``
+    are fitted in one call and their defocus rows written in the same order."""
 
     def __init__(self, profiles, out, defocus_params, trail_params):
         self.profiles, self.out = profiles, out
         self.defocus_params, self.trail_params = defocus_params, trail_params
         self.pending = []
 
-    def write(self, text):
-        self.profiles.write(text)
-
     def add(self, key, trail, profile):
-        self.pending.append((key, trail, profile))
+        self.profiles.write(profile_row(key, trail, profile))
+        if self.out is not None:
+            self.pending.append((key, trail, profile))
 
     def flush(self):
         from .. import defocus
@@ -185,7 +170,8 @@ class _DefocusTee:
             self.out.write("".join(defocus.format_row(k, f) + "\n" for (k, _, _), f in zip(self.pending, fit)))
             self.pending = []
         self.profiles.flush()
-        self.out.flush()
+        if self.out is not None:
+            self.out.flush()
 
 
 class _SkyStage:
@@ -257,112 +243,6 @@ def _log_error(errors, ids, exc, debug):
     errors.write(str(exc) + "\n\n")
 
 
-def process_field(results, errors, run, camcol, filter, field, params_bright, params_dim,
-                  params_removestars, profiles=None, trail_params=None, sky=None):
-    """One frame end to end (reference: detecttrails.py:30-143): locate the frame (or its .bz2),
-    read image + header + photoObj, detect, append ``run camcol filter field tai crpix1 crpix2
-    crval1 crval2 cd11 cd12 cd21 cd22 x1 y1 x2 y2`` to ``results``; every exception is logged
-    to ``errors`` (ids, 3-frame traceback, message) and swallowed.  ``profiles``: a file the frame's trail profile row
-    (``profile_row``) is appended to when it has a detection.  ``sky``: a ``_SkyStage``; the frame is normalised first and its
-    sky.txt row written (detection and profile then refer to the normalised frame)."""
-    debug = params_bright.get("debug") or params_dim.get("debug")
-    try:
-        img, head, cat = _load_frame(run, camcol, filter, field)
-        if sky is not None:
-            img, srec = sky.one(img)
-            sky.row((run, camcol, filter, field), srec)
-        detection, res, rec = process_frame_arrays(img, cat, filter, params_bright, params_dim,
-                                                   params_removestars)
-        if detection:
-            results.write(f"{head} {res['x1']} {res['y1']} {res['x2']} {res['y2']}\n")
-    except Exception as e:  # noqa: BLE001 - the reference swallows everything per frame
-        _log_error(errors, (run, camcol, filter, field), e, debug)
-        return
-    if detection and profiles is not None:
-        try:
-            meas = measure_trail(img, rec, cat, filter, params_removestars, **(trail_params or {}))
-        except Exception as e:  # noqa: BLE001
-            meas = e
-        _write_profile(profiles, errors, (run, camcol, filter, field), meas, debug)
-
-
-def process_fields_batched(results, errors, ids, params_bright, params_dim, params_removestars, loaded=None, profiles=None,
-                           trail_params=None):
-    """Same outcome as calling process_field for every (run, camcol, filter, field) in ``ids``, in order -- the same
-    results rows, the same errors entries, a bad frame costs only itself (detecttrails.py:119-139) -- but all frames
-    that load go through ONE lfdmi_detect_batch call per (filter, shape) group (frames with different filters use
-    different magnitude caps).  ``loaded``: what ``_load_many(ids)`` returned, if the caller read the files already."""
-    from .removestars import _check_finite
-    if loaded is None:
-        loaded = _load_many(ids)
-    rows = {}
-    meas = {}                                         # key -> (trail record, profile) or the measurement's exception
-    tp = trail_params or {}
-    debug = params_bright.get("debug") or params_dim.get("debug")
-    groups = {}
-    for item in loaded:
-        if len(item) != 4:
-            continue                                  # did not load: its exception is logged below
-        key, img, _, cat = item
-        try:
-            if cat is not None and len(cat["NOBSERVE"]):
-                _check_finite(cat)                    # math.ceil(nan) in the reference: this frame's error alone
-        except Exception as e:  # noqa: BLE001
-            rows[key] = e
-            continue
-        groups.setdefault((key[2], img.shape), []).append(item)
-    from ..catalogs import pack_catalogs
-    for (flt, shape), group in groups.items():
-        try:
-            frames = _np.stack([it[1] for it in group])
-            packed = pack_catalogs([it[3] for it in group])
-            rs = _rs_struct(flt, params_removestars)
-            with use_context(*shape, inflight=min(32, len(group))) as ctx:
-                recs = ctx.detect_batch(frames, params_bright, params_dim, packed, rs)
-                if profiles is not None:
-                    try:
-                        tr, pr = ctx.measure_trails(frames, recs, packed, rs, **tp)
-                        for j, it in enumerate(group):
-                            meas[it[0]] = (tr[j], pr[j])
-                    except Exception as e:  # noqa: BLE001 - the group's measurement failed: each detected frame logs it
-                        for it in group:
-                            meas[it[0]] = e
-            for it, rec in zip(group, recs):
-                rows[it[0]] = rec
-        except Exception:  # noqa: BLE001 - a call-level failure: every frame of the group on its own, under its own try
-            for it in group:
-                try:
-                    rows[it[0]] = process_frame_arrays(it[1], it[3], flt, params_bright, params_dim, params_removestars)[2]
-                    if profiles is not None and rows[it[0]]["found"]:
-                        try:
-                            meas[it[0]] = measure_trail(it[1], rows[it[0]], it[3], flt, params_removestars, **tp)
-                        except Exception as e:  # noqa: BLE001
-                            meas[it[0]] = e
-                except Exception as e:  # noqa: BLE001
-                    rows[it[0]] = e
-    for item in loaded:
-        key = item[0]
-        try:
-            if len(item) == 2:
-                raise item[1]
-            rec = rows[key]
-            if isinstance(rec, Exception):
-                raise rec
-            status = int(rec["status"])
-            if status == _native.ERR_NOLINES:
-                raise TypeError("'NoneType' object is not subscriptable")
-            if status:
-                raise _native.NativeError(status, "frame failed on the device")
-            if rec["found"]:
-                res = dictify_hough(item[1].shape, (_np.float32(rec["rho"]), _np.float32(rec["theta"])))
-                results.write(f"{item[2]} {res['x1']} {res['y1']} {res['x2']} {res['y2']}\n")
-        except Exception as e:  # noqa: BLE001
-            _log_error(errors, key, e, debug)
-            continue
-        if profiles is not None and rec["found"]:
-            _write_profile(profiles, errors, key, meas.get(key, RuntimeError("no trail measurement")), debug)
-
-
 def _load_many(ids):
     """[(key, img, head, cat) or (key, exception)] for every key, in order (FITS / bz2 decoding: host work that
     DetectTrails.process overlaps with the GPU passes of the previous chunk)."""
@@ -378,7 +258,6 @@ def _load_many(ids):
 def _frame_shape(keys):
     """(h, w) of the first frame of the selection that can be opened (SDSS frames are all 1489 x 2048; a selection none of
     whose files exists gets the SDSS shape and one errors entry per frame)."""
-    from .loader import card_value, header_end
     for key in keys[:64]:
         run, camcol, flt, field = key
         try:
@@ -399,6 +278,160 @@ def _frame_shape(keys):
     return 1489, 2048
 
 
+class _Chunk:
+    """What one driver call runs with -- the output files, the three parameter dictionaries, the profiles sink (``add(key, trail,
+    profile)``) with its trail params, the ``_SkyStage`` -- and the per-frame slots of its ``n`` frames: ``rows[i]`` the
+    detection record, what ``process_frame_arrays`` returned, or the exception that is the frame's errors entry; ``meas[i]``
+    (trail record, profile) or the measurement's exception; ``srecs[i]`` the sky record if the frame was normalised.  A new
+    per-frame product gets a slot here, a step in ``_run_group`` and ``_run_frame``, and its row in ``_emit``."""
+
+    def __init__(self, n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky):
+        self.results, self.errors, self.profiles, self.sky = results, errors, profiles, sky
+        self.params_bright, self.params_dim, self.params_removestars = params_bright, params_dim, params_removestars
+        self.trail_params = trail_params or {}
+        self.debug = params_bright.get("debug") or params_dim.get("debug")
+        self.rows, self.meas, self.srecs = [None] * n, [None] * n, [None] * n
+        self.gpu_s = 0.0                              # inside the sky + detect calls of the groups that went through
+
+
+def _run_frame(c, i, filter, frame):
+    """Frame i on its own, under its own try: ``frame()`` -> (float32 img, cat); sky normalisation if on, detection, and the
+    trail measurement of a detected frame."""
+    try:
+        img, cat = frame()
+        if c.sky is not None:
+            img, c.srecs[i] = c.sky.one(img)
+        c.rows[i] = process_frame_arrays(img, cat, filter, c.params_bright, c.params_dim, c.params_removestars)
+        if c.profiles is not None and c.rows[i][0]:
+            try:
+                c.meas[i] = measure_trail(img, c.rows[i][2], cat, filter, c.params_removestars, **c.trail_params)
+            except Exception as e:  # noqa: BLE001
+                c.meas[i] = e
+    except Exception as e:  # noqa: BLE001 - the reference swallows everything per frame
+        c.rows[i] = e
+
+
+def _run_group(c, idx, filter, shape, inflight, source, second, detect_kw=None, measure_kw=None):
+    """The frames ``idx`` of one filter and shape in ONE lfdmi_detect_batch call (frames with different filters use different
+    magnitude caps).  ``source()`` -> (frames, padded catalogue arrays); ``detect_kw`` / ``measure_kw`` say where those frames
+    are (``pinned``, ``native_device``).  With sky on the frames are normalised into the handle's device buffer first (the upload
+    happens there) and detection and measurement read that buffer.  A measurement that fails is the error of every detected
+    frame of the group.  A call-level failure: every frame on its own (``_run_frame``) from ``second(i)`` -> (img, cat);
+    ``second`` None: the frames are wherever the failed call left them, and each of them logs the call's exception."""
+    import time
+    detect_kw, measure_kw = detect_kw or {}, measure_kw or {}
+    try:
+        frames, packed = source()
+        rs = _rs_struct(filter, c.params_removestars)
+        with use_context(*shape, inflight=inflight) as ctx:
+            t0 = time.perf_counter()
+            if c.sky is not None:
+                frames, srecs = c.sky.batch(ctx, frames, shape, len(idx), pinned=detect_kw.get("pinned", False))
+                for j, i in enumerate(idx):
+                    c.srecs[i] = srecs[j]
+                detect_kw = measure_kw = {}
+            recs = ctx.detect_batch(frames, c.params_bright, c.params_dim, packed, rs, **detect_kw)
+            c.gpu_s += time.perf_counter() - t0
+            if c.profiles is not None:
+                try:
+                    trails, profs = ctx.measure_trails(frames, recs, packed, rs, **measure_kw, **c.trail_params)
+                    for j, i in enumerate(idx):
+                        c.meas[i] = (trails[j], profs[j])
+                except Exception as e:  # noqa: BLE001
+                    for i in idx:
+                        c.meas[i] = e
+        for i, rec in zip(idx, recs):
+            c.rows[i] = rec
+    except Exception as e:  # noqa: BLE001
+        failed = e
+    else:
+        return
+    for i in idx:                                     # (outside the handler: a frame's own exception is not chained to the call's)
+        if second is None:
+            c.rows[i] = failed
+        else:
+            _run_frame(c, i, filter, lambda: second(i))
+
+
+def _emit(c, i, key, head, shape):
+    """Frame i's text, from its slots: the sky row if it was normalised; the results row (``head``: its first 13 columns, or
+    the header to take them from) or the errors entry; then the profiles row or the measurement's errors entry."""
+    if c.srecs[i] is not None:
+        c.sky.row(key, c.srecs[i])
+    try:
+        row = c.rows[i]
+        if isinstance(row, Exception):
+            raise row
+        detection, res, _ = row if isinstance(row, tuple) else _detection(row, shape)
+        if detection:
+            if not isinstance(head, str):
+                head = " ".join(str(x) for x in (*key, *header_values(head, _HEADER_KEYS)))
+            c.results.write(f"{head} {res['x1']} {res['y1']} {res['x2']} {res['y2']}\n")
+    except Exception as e:  # noqa: BLE001
+        _log_error(c.errors, key, e, c.debug)
+        return
+    if not detection or c.profiles is None:
+        return
+    try:                                              # (results.txt is written before, untouched)
+        meas = c.meas[i] if c.meas[i] is not None else RuntimeError("no trail measurement")
+        if isinstance(meas, Exception):
+            raise meas
+        c.profiles.add(key, *meas)
+    except Exception as e:  # noqa: BLE001
+        _log_error(c.errors, key, e, c.debug)
+
+
+def process_field(results, errors, run, camcol, filter, field, params_bright, params_dim,
+                  params_removestars, profiles=None, trail_params=None, sky=None):
+    """One frame end to end (reference: detecttrails.py:30-143): locate the frame (or its .bz2),
+    read image + header + photoObj, detect, append ``run camcol filter field tai crpix1 crpix2
+    crval1 crval2 cd11 cd12 cd21 cd22 x1 y1 x2 y2`` to ``results``; every exception is logged
+    to ``errors`` (ids, 3-frame traceback, message) and swallowed.  ``profiles``: the sink (``add(key, trail, profile)``) the
+    frame's trail profile goes to when it has a detection.  ``sky``: a ``_SkyStage``; the frame is normalised first and its
+    sky.txt row written (detection and profile then refer to the normalised frame)."""
+    c = _Chunk(1, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky)
+    head = None
+    try:
+        img, head, cat = _load_frame(run, camcol, filter, field)
+    except Exception as e:  # noqa: BLE001
+        c.rows[0] = e
+    else:
+        _run_frame(c, 0, filter, lambda: (img, cat))
+    _emit(c, 0, (run, camcol, filter, field), head, None)
+
+
+def process_fields_batched(results, errors, ids, params_bright, params_dim, params_removestars, loaded=None, profiles=None,
+                           trail_params=None):
+    """Same outcome as calling process_field for every (run, camcol, filter, field) in ``ids``, in order -- the same
+    results rows, the same errors entries, a bad frame costs only itself (detecttrails.py:119-139) -- but all frames
+    that load go through ONE lfdmi_detect_batch call per (filter, shape) group.  ``loaded``: what ``_load_many(ids)``
+    returned, if the caller read the files already."""
+    from ..catalogs import pack_catalogs
+    from .removestars import _check_finite
+    if loaded is None:
+        loaded = _load_many(ids)
+    c = _Chunk(len(loaded), results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, None)
+    groups = {}
+    for i, item in enumerate(loaded):
+        if len(item) != 4:
+            c.rows[i] = item[1]                       # did not load
+            continue
+        key, img, _, cat = item
+        try:
+            if cat is not None and len(cat["NOBSERVE"]):
+                _check_finite(cat)                    # math.ceil(nan) in the reference: this frame's error alone
+        except Exception as e:  # noqa: BLE001
+            c.rows[i] = e
+            continue
+        groups.setdefault((key[2], img.shape), []).append(i)
+    for (flt, shape), idx in groups.items():
+        _run_group(c, idx, flt, shape, min(32, len(idx)),
+                   lambda: (_np.stack([loaded[i][1] for i in idx]), pack_catalogs([loaded[i][3] for i in idx])),
+                   lambda i: (loaded[i][1], loaded[i][3]))
+    for i, item in enumerate(loaded):
+        _emit(c, i, item[0], *((item[2], item[1].shape) if len(item) == 4 else (None, None)))
+
+
 def process_loaded(results, errors, loaded, params_bright, params_dim, params_removestars, profiles=None, trail_params=None, sky=None):
     """process_fields_batched for a chunk the loader has read (``loader.Loaded``): the frames that sit in pinned memory go to
     the GPU as contiguous same-filter slices of that memory with the matching rows of the padded catalogue arrays (no copy
@@ -408,33 +441,13 @@ def process_loaded(results, errors, loaded, params_bright, params_dim, params_re
     are), detection and measurement run on that buffer, and one sky.txt row per normalised frame is written, in the caller's
     order, ahead of the frame's results row."""
     import time
-    from .loader import header_values
-    trace = os.environ.get("LFD_LOADER_TRACE") == "1"
     t_in = time.perf_counter()
-    t_gpu = 0.0
-    debug = params_bright.get("debug") or params_dim.get("debug")
     n = len(loaded.keys)
-    rows = [None] * n
-    meas = [None] * n                                 # (trail record, profile) or the measurement's exception
-    srecs = [None] * n                                # sky records of the frames that were normalised
-    tp = trail_params or {}
-
-    def normalised(i, img):
-        if sky is None:
-            return img
-        img, srecs[i] = sky.one(img)
-        return img
-
-    def measure_one(i, img, cat, flt):
-        if profiles is not None and rows[i]["found"]:
-            try:
-                meas[i] = measure_trail(img, rows[i], cat, flt, params_removestars, **tp)
-            except Exception as e:  # noqa: BLE001
-                meas[i] = e
+    c = _Chunk(n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky)
     by_slot = {}
     for i in range(n):
         if loaded.error[i] is not None:
-            rows[i] = loaded.error[i]
+            c.rows[i] = loaded.error[i]
         elif loaded.slot[i] >= 0:
             by_slot[loaded.slot[i]] = i
     # maximal runs of neighbouring slots with one filter
@@ -444,90 +457,31 @@ def process_loaded(results, errors, loaded, params_bright, params_dim, params_re
         if j == len(slots) or slots[j] != slots[j - 1] + 1 or loaded.keys[by_slot[slots[j]]][2] != loaded.keys[by_slot[slots[start]]][2]:
             runs.append(slots[start:j])
             start = j
-    h, w = loaded.shape if getattr(loaded, "shape", None) else (loaded.buffer.shape[1:] if loaded.buffer is not None else (0, 0))
+    shape = loaded.shape if getattr(loaded, "shape", None) else (loaded.buffer.shape[1:] if loaded.buffer is not None else (0, 0))
+    if loaded.device is not None:                     # decompressed on the GPU and still there; swapped (and blotted) in place by
+        frames_of, second, where = loaded.device.slice, None, ({}, {"native_device": True})      # the detect call: no second source
+    else:
+        frames_of, where = lambda a, b: loaded.buffer[a:b], ({"pinned": True}, {"pinned": True})
+        second = lambda i: (loaded.buffer[loaded.slot[i]].astype(_np.float32), loaded.cat_of(i))  # noqa: E731
     for run_slots in runs:
-        idx = [by_slot[sl] for sl in run_slots]
-        flt = loaded.keys[idx[0]][2]
         a, b = run_slots[0], run_slots[-1] + 1
-        try:
+
+        def source():
             cats = loaded.cats
             m = max(1, int(cats["count"][a:b].max()))
             packed = {k: _np.ascontiguousarray(v[a:b, :m]) for k, v in cats.items() if k != "count"}
             packed["count"] = cats["count"][a:b]
-            rs = _rs_struct(flt, params_removestars)
-            with use_context(h, w, inflight=min(256, len(idx))) as ctx:
-                t_g = time.perf_counter()
-                buf = None
-                if sky is not None:                           # the upload happens here; detection then reads the handle's buffer
-                    src = loaded.device.slice(a, b) if loaded.device is not None else loaded.buffer[a:b]
-                    buf, sr = sky.batch(ctx, src, (h, w), len(idx), pinned=loaded.device is None)
-                    for j, i in enumerate(idx):
-                        srecs[i] = sr[j]
-                    recs = ctx.detect_batch(buf, params_bright, params_dim, packed, rs)
-                elif loaded.device is not None:               # decompressed on the GPU and still there
-                    recs = ctx.detect_batch(loaded.device.slice(a, b), params_bright, params_dim, packed, rs)
-                else:
-                    recs = ctx.detect_batch(loaded.buffer[a:b], params_bright, params_dim, packed, rs, pinned=True)
-                t_gpu += time.perf_counter() - t_g
-                if profiles is not None:
-                    try:                                      # device frames: swapped (and blotted) in place by the call above
-                        if buf is not None:
-                            tr, pr = ctx.measure_trails(buf, recs, packed, rs, **tp)
-                        elif loaded.device is not None:
-                            tr, pr = ctx.measure_trails(loaded.device.slice(a, b), recs, packed, rs, native_device=True, **tp)
-                        else:
-                            tr, pr = ctx.measure_trails(loaded.buffer[a:b], recs, packed, rs, pinned=True, **tp)
-                        for j, i in enumerate(idx):
-                            meas[i] = (tr[j], pr[j])
-                    except Exception as e:  # noqa: BLE001 - the slice's measurement failed: each detected frame logs it
-                        for i in idx:
-                            meas[i] = e
-            for i, rec in zip(idx, recs):
-                rows[i] = rec
-        except Exception:  # noqa: BLE001 - a call-level failure: every frame of the slice on its own, under its own try
-            for sl, i in zip(run_slots, idx):
-                try:
-                    if loaded.device is not None:             # (the frames are wherever the failed call left them: no second source)
-                        raise
-                    img = normalised(i, loaded.buffer[sl].astype(_np.float32))
-                    rows[i] = process_frame_arrays(img, loaded.cat_of(i), flt, params_bright, params_dim, params_removestars)[2]
-                    measure_one(i, img, loaded.cat_of(i), flt)
-                except Exception as e:  # noqa: BLE001
-                    rows[i] = e
+            return frames_of(a, b), packed
+        idx = [by_slot[sl] for sl in run_slots]
+        _run_group(c, idx, loaded.keys[idx[0]][2], shape, min(256, len(idx)), source, second, *where)
     for i in range(n):
-        if rows[i] is None and loaded.array[i] is not None:      # not a plain float32 image of the chunk's shape, or an oversized catalogue
-            try:
-                img = normalised(i, loaded.array[i])
-                rows[i] = process_frame_arrays(img, loaded.cat_of(i), loaded.keys[i][2], params_bright, params_dim,
-                                               params_removestars)[2]
-                measure_one(i, img, loaded.cat_of(i), loaded.keys[i][2])
-            except Exception as e:  # noqa: BLE001
-                rows[i] = e
+        if c.rows[i] is None and loaded.array[i] is not None:    # not a plain float32 image of the chunk's shape, or an oversized catalogue
+            _run_frame(c, i, loaded.keys[i][2], lambda: (loaded.array[i], loaded.cat_of(i)))
     for i, key in enumerate(loaded.keys):
-        if sky is not None and srecs[i] is not None:
-            sky.row(key, srecs[i])
-        try:
-            rec = rows[i]
-            if isinstance(rec, Exception):
-                raise rec
-            status = int(rec["status"])
-            if status == _native.ERR_NOLINES:
-                raise TypeError("'NoneType' object is not subscriptable")
-            if status:
-                raise _native.NativeError(status, "frame failed on the device")
-            if rec["found"]:
-                shape = loaded.array[i].shape if loaded.array[i] is not None else (h, w)
-                res = dictify_hough(shape, (_np.float32(rec["rho"]), _np.float32(rec["theta"])))
-                head = " ".join(str(x) for x in (*key, *header_values(loaded.hdr[i], _HEADER_KEYS)))
-                results.write(f"{head} {res['x1']} {res['y1']} {res['x2']} {res['y2']}\n")
-        except Exception as e:  # noqa: BLE001
-            _log_error(errors, key, e, debug)
-            continue
-        if profiles is not None and rec["found"]:
-            _write_profile(profiles, errors, key, meas[i] if meas[i] is not None else RuntimeError("no trail measurement"), debug)
-    if trace:
+        _emit(c, i, key, loaded.hdr[i], shape)
+    if os.environ.get("LFD_LOADER_TRACE") == "1":
         print("[loader]   process_loaded: %.1f ms in all, %.1f ms inside lfdmi_detect_batch_raw" %
-              (1e3 * (time.perf_counter() - t_in), 1e3 * t_gpu), flush=True)
+              (1e3 * (time.perf_counter() - t_in), 1e3 * c.gpu_s), flush=True)
 
 
 class DetectTrails:
@@ -733,7 +687,7 @@ class DetectTrails:
                 (open(self.profiles + suffix, "a") if self.trail_profiles else contextlib.nullcontext()) as profiles, \
                 (open(self.defocus_file + suffix, "a") if self.defocus else contextlib.nullcontext()) as defocus_out, \
                 (open(self.sky_file + suffix, "a") if self.normalize else contextlib.nullcontext()) as sky_out:
-            if self.defocus:
+            if self.trail_profiles:
                 profiles = _DefocusTee(profiles, defocus_out, self.defocus_params, self.trail_params)
             prof_kw = {"profiles": profiles, "trail_params": self.trail_params} if self.trail_profiles else {}
             sky = _SkyStage(sky_out, self.sky_params) if self.normalize else None

@@ -93,6 +93,7 @@ class Loaded:
         self.hdr = [None] * n
         self.cat = [None] * n
         self.buffer = None                                   # [slots, h, w] '>f4' view of the pinned memory
+        self.cats = None                                     # padded catalogue arrays of the buffer's slots + "count"
         self.shape = None                                    # (h, w) of the chunk's frames
         self.device = None                                   # or: _native.DeviceFrames (the same slots in device memory: frames that
                                                              # were decompressed on the GPU and stayed there; ``buffer`` is then unused)
@@ -101,7 +102,6 @@ class Loaded:
     def frame_host(self, slot):
         """Slot ``slot`` as a host array, wherever the chunk's frames are."""
         return self.buffer[slot] if self.device is None else self.fetch(slot)
-        self.cats = None                                     # padded catalogue arrays of the buffer's slots + "count"
 
     def cat_of(self, i):
         """photoObj columns of key i as a dict of arrays (what the per-frame path takes)."""
