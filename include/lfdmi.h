@@ -538,6 +538,10 @@ int lfdmi_measure_trails(lfdmi_ctx *ctx, const void *frames, int dtype, int n, i
  *    grid height with chi2_by_height <= chi2_min + delta_chi2 (h_hi = +inf when the focus model is among them, h_lo too when
  *    it is the only one).  The bins are correlated (about 1 / prof_step of them per px), so chi2 is a relative measure and
  *    delta_chi2 a relative threshold, not a confidence level.  The chosen model's h_km is +inf for the focus model.
+ *    Degenerate rows.  A constant row has v~ = 0 and every score 0: LFDMI_DEFOCUS_NO_MODEL, chi2_by_height 0 at every height
+ *    with an allowed column.  A row that holds +Inf or -Inf is not a gap: its mean is not finite, v~ holds NaN, and no score
+ *    compares above 0: LFDMI_DEFOCUS_NO_MODEL, chi2_by_height NaN at every height.  Neither changes the result of any other
+ *    row of the call: a row's result depends on that row, the bank and its seeing alone, not on its position or its neighbours.
  * Recovery (tests/test_gpu_defocus.py: trails rendered as the model without B and T, 8 x 8 sub-pixel points, peak 2 sky sigma,
  * ~2000 px long, three angles, then measure_trails and this fit with the default bank plus the true heights): h = 80, 100,
  * 150 km came back within 0.9 % (on the true height or the next grid height) and in-focus trails as the focus model.  The
@@ -553,7 +557,8 @@ typedef struct {
     int32_t wing;             /* px: the trail params' */
     int32_t ovs;              /* fine steps per profile bin (1 .. 64); default 8 */
     int32_t max_shift;        /* S: shifts of +-S bins (0 .. 64); default 5 */
-    int32_t n_h, n_r, n_seeing; /* grid lengths (each >= 1; n_seeing (n_h + 1) n_r (2S+1) columns at most 2^26) */
+    int32_t n_h, n_r, n_seeing; /* grid lengths (each >= 1; n_h <= 4096, n_r <= 64, n_seeing <= 1024; the bank's n_seeing (n_h + 1)
+                                 * n_r (2S+1) columns: fewer than 2^31, and columns x padded bins x 4 bytes at most 64 GB) */
     const double *heights;    /* km, > 0, n_h of them; NULL in the defaults: 60 .. 300 km in 128 geometric steps */
     const double *radii;      /* m, >= 0; defaults {0, 0.1, 0.5, 1, 2, 5, 10} */
     const double *seeings;    /* FWHM arcsec, > 0; defaults 0.8 .. 2.2 in steps of 0.05 */

@@ -149,3 +149,78 @@ def test_defocus_rows_round_trip(tmp_path):
             a, b = row[k], r[k].item()
             assert a == b or (math.isnan(a) and math.isnan(b)), k
     assert "-3 " in open(path).read().splitlines()[1] and "0.3333333333333333" in open(path).read()
+
+
+# ---- the inputs of tests/test_gpu_defocus_shapes.py: their conditions hold by the restatement alone --------------------------
+import defocus_cases as DC  # noqa: E402
+
+NON_DECISIVE_CAP = 0.25
+
+
+@pytest.mark.parametrize("name", list(DC.GEOMS))
+def test_shape_geometries_meet_their_conditions(name):
+    """the tile property each geometry is there for, a valid and an invalid model in every bank, and at most a quarter of the
+    fitted rows non-decisive (a row is decisive when the acceptance rule leaves the device one column to return)"""
+    rb, trails, prof = DC.fit_inputs(name)
+    facts = DC.tile_facts(rb)
+    for k, v in DC.GEOMS[name]["expect"].items():
+        assert facts[k] == v, (k, facts[k], v)
+    assert DC.PROPERTIES[name](facts), facts
+    assert 0 < facts["n_valid"] < facts["n_models"]
+    share, J = DC.non_decisive_share(rb, trails, prof)
+    band = int((~J["must_ok"] & ~J["must_none"]).sum())
+    print(f"{name}: non-decisive share {share:.3f}, rows where either status is accepted {band}, NO_MODEL required "
+          f"{int(J['must_none'].sum())} of {len(prof)}")
+    assert share <= NON_DECISIVE_CAP
+    assert J["must_ok"].sum() >= len(prof) // 2
+
+
+def test_largest_geometry_is_largest_by_groups_and_padded_bins():
+    facts = {n: DC.tile_facts(DC.restated(n)) for n in DC.GEOMS}
+    assert all(facts[DC.LARGEST][k] >= f[k] for f in facts.values() for k in ("n_groups", "nbp"))
+
+
+def test_row_test_inputs_meet_the_cap():
+    rb = DC.restated("two_k_steps")
+    for n, seed in ((127, 134), (128, 135), (129, 136), (4096, 4103), (300, 21), (128, 31)):
+        share, _ = DC.non_decisive_share(rb, *DC.make_rows(rb, n, seed)[:2])
+        assert share <= NON_DECISIVE_CAP, (n, share)
+    for seeings in ([1.0, 2.0], [2.0, 1.0], [1.0, 1.0, 2.0]):
+        rv = DC.restate(DC.variant("two_k_steps", seeings=seeings))
+        share, _ = DC.non_decisive_share(rv, *DC.make_rows(rv, 200, 41)[:2])
+        assert share <= NON_DECISIVE_CAP, (seeings, share)
+
+
+def test_tie_rows_are_decisive_and_name_the_lowest_copy():
+    for name, (ge, rb, trails, prof, want) in DC.tie_cases().items():
+        J = R.judge(rb, trails, prof)
+        assert J["decisive"].all() and J["must_ok"].all(), name
+        assert np.array_equal(J["want"], want), name
+        dup = np.bincount(rb.cls[rb.vcol])
+        assert dup.max() >= 2, name     # the bank does hold bit-identical valid columns
+
+
+def test_seeing_slice_rule():
+    assert [R.seeing_slice([1.0, 2.0], s) for s in (0.9, 1.5, 1.6, np.nan)] == [0, 0, 1, None]
+    assert R.seeing_slice([2.0, 1.0], 1.5) == 1 and R.seeing_slice([1.0, 1.0, 2.0], 1.1) == 0
+
+
+def test_score_bound_covers_float32_dot_products_in_any_order():
+    """the derived bound against float32 sums in ascending, descending, pairwise and random order, and against the rounded v~"""
+    rng = np.random.default_rng(0)
+    rb = DC.restated("fractional_F")
+    trails, prof, _ = DC.make_rows(rb, 40, 9)
+    vt = R.centre(prof, rounded=True)
+    assert np.array_equal(vt, vt.astype(np.float32)) and not np.array_equal(vt, R.centre(prof))
+    e = R.score_bound(rb.nbp, vt)
+    cols = np.flatnonzero(rb.vcol)[::7]
+    exact = vt @ rb.c64[cols].T
+    worst = 0.0
+    for order in (np.arange(rb.nb), np.arange(rb.nb)[::-1], rng.permutation(rb.nb)):
+        acc = np.zeros(exact.shape, np.float32)
+        for k in order:
+            acc = (acc + (vt[:, k, None].astype(np.float32) * rb.c32[cols][None, :, k]).astype(np.float32)).astype(np.float32)
+        worst = max(worst, float((np.abs(acc - exact) / e[:, None]).max()))
+    pair = (vt.astype(np.float32)[:, None, :] * rb.c32[cols][None]).sum(axis=2, dtype=np.float32)
+    worst = max(worst, float((np.abs(pair - exact) / e[:, None]).max()))
+    assert 0 < worst <= 1.0, worst
