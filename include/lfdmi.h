@@ -712,6 +712,68 @@ typedef struct {
 int lfdmi_inject_trails(lfdmi_ctx *ctx, void *frames, int dtype, int n, int h, int w, int loc, const lfdmi_inject_trail *trails,
                         int n_trails, const float *tables, int n_tables, int table_len, double table_step, int subsample);
 
+/* ---- faint-trail search -----------------------------------------------------------------------------------------------------
+ * The detector finds a trail whose pixels survive the 8-bit conversion; lfdmi_radon_search finds one that is faint in every
+ * pixel but long: it sums the frame along every line of a dyadic family (the fast Radon transform of Goetz and Druckmueller /
+ * Brady) and reports the line of largest signal-to-noise.  The reference has no such step.  The procedure below is the
+ * definition; tests/radon_ref.py restates it in numpy and the device matches it bit for bit: every value of the transform is
+ * one float32 sum of two values of the level before, so no result depends on how the device orders or fuses the levels.
+ *
+ * 1. Pixels.  Coordinates are the detection records': x = column, y = row of the flipped frame, so (x, y) is buffer row H-1-y.
+ *    A pixel is valid when it is finite, not +-0 (what remove_stars blotted) and |x| <= clip (above: a star, a saturated
+ *    column).  v = x where valid, else +0; m = 1 where valid, else 0.
+ * 2. Binning by b = bin.  Hb = ceil(H / b), Wb = ceil(W / b); V[j][i] = the float32 sum of v over rows j b .. j b + b-1 and
+ *    columns i b .. i b + b-1 that exist: rows ascending, within a row columns ascending, one sequential accumulator starting
+ *    at +0.  M[j][i] = the integer sum of m over the same pixels.
+ * 3. Orientations q = 0 .. 3, each a working array Q of R rows and C columns (and the same of M):
+ *        q = 0: Q[r][c] = V[r][c], R = Hb, C = Wb          q = 1: Q[r][c] = V[Hb-1-r][c]
+ *        q = 2: Q[r][c] = V[c][r], R = Wb, C = Hb          q = 3: Q[r][c] = V[c][Wb-1-r]
+ *    P = the smallest power of two >= C; columns C .. P-1 are +0.
+ * 4. Transform.  F_1[c][y][0] = Q[y][c].  For strip width n = 1, 2, .. P/2, strip j and s = 0 .. 2n-1:
+ *        F_2n[j][y][s] = F_n[2j][y][s>>1] + F_n[2j+1][y + ((s+1)>>1)][s>>1]          (one float32 addition)
+ *    y runs over [-(P-1), R-1]; any row outside [0, R-1] of a level-1 strip reads +0.  S_q[y][s] = F_P[0][y][s]: the sum along the
+ *    dyadic line that enters column 0 at row y and rises s rows over P-1 columns.  N_q[y][s]: the same recursion on M, exact
+ *    in integers, at most C b b.
+ * 5. Score.  A line is a candidate when N >= min_len.  Its SNR is S / (sigma * sqrtf((float)N)): a float32 square root, product
+ *    and quotient, each correctly rounded.  The frame's line is the candidate of largest SNR; ties go to the lowest (q, s, y).
+ * 6. Record.  status LFDMI_RADON_OK, or LFDMI_RADON_NO_LINE without a candidate (then snr = 0, found = 0, every other field 0).
+ *    found = snr >= threshold (float32).  x1, y1, x2, y2, rho, theta (double, on the host): the line runs through the working
+ *    points (c = 0, r = y0) and (c = P-1, r = y0 + s); these map back through the orientation to binned (i, j) -- q = 0: (c, r),
+ *    1: (c, Hb-1-r), 2: (r, c), 3: (Wb-1-r, c) -- and to pixels as b i + (b-1)/2, b j + (b-1)/2 (points outside the frame are
+ *    not clipped).  theta = atan2(-(x2-x1), y2-y1) folded into [0, pi), rho = x1 cos(theta) + y1 sin(theta): the line is
+ *    x cos(theta) + y sin(theta) = rho, as in lfdmi_result. */
+enum { LFDMI_RADON_OK = 0, LFDMI_RADON_NO_LINE = 1 };
+typedef struct {
+    int32_t bin;          /* 1, 2 or 4; default 2 */
+    int32_t min_len;      /* valid pixels a candidate line needs (>= 1); default 256 */
+    float clip;           /* pixels above it in magnitude are not summed (> 0); default 0.125 = five sky sigma */
+    float threshold;      /* found = snr >= threshold; default 8: noise-only frames of 372 x 512 peak at 4.5 - 5.3 (bin 1), 4.2 - 4.9 (bin 2) */
+} lfdmi_radon_params;
+typedef struct {
+    int32_t status;       /* LFDMI_RADON_* */
+    int32_t found;
+    int32_t q, y0, s;     /* the line in working coordinates (steps 3, 4) */
+    int32_t n_pix;        /* N: valid pixels on it */
+    float sum, snr;       /* S and its score */
+    double x1, y1, x2, y2, rho, theta;
+} lfdmi_radon_result;
+typedef struct lfdmi_radon lfdmi_radon;
+void lfdmi_default_radon_params(lfdmi_radon_params *out);
+/* A handle for frames of exactly h x w on ctx's device: it owns V, M, two sets of planes ((R + P - 1) x P float32 sums and
+ * 16-bit counts per orientation) for max_frames frames and, once host frames have been given, an upload buffer.  p NULL: the
+ * defaults.  LFDMI_ERR_ARG: h or w below 2 bin, a line that could count more than 65535 pixels (max(Hb, Wb) b b: a line crosses every column of its orientation), parameters
+ * out of range.  Destroy may come before or after lfdmi_ctx_destroy of its context (it does not touch the context). */
+int lfdmi_radon_create(lfdmi_ctx *ctx, int h, int w, int max_frames, const lfdmi_radon_params *p, lfdmi_radon **out);
+void lfdmi_radon_destroy(lfdmi_radon *radon);
+/* P of orientations 0, 1 (p01) and 2, 3 (p23) and the device bytes the handle holds; any pointer may be NULL */
+int lfdmi_radon_dims(const lfdmi_radon *radon, int32_t *p01, int32_t *p23, int64_t *bytes);
+/* frames: n frames, LFDMI_F32 or LFDMI_F32_BE, loc LFDMI_HOST / LFDMI_HOST_PINNED / LFDMI_DEVICE; only read.  sigma: n float32
+ * (host), the sky sigma of each frame, > 0; NULL: 0.025 for every frame.  results: n records (host).  n > max_frames runs in
+ * chunks of max_frames.  The call refuses (LFDMI_ERR_ARG) while calls are in flight and on a sigma that is not positive, runs
+ * on the context's stream and waits for it once, at its end. */
+int lfdmi_radon_search(lfdmi_ctx *ctx, lfdmi_radon *radon, const void *frames, int dtype, int n, int loc, const float *sigma,
+                       lfdmi_radon_result *results);
+
 #ifdef __cplusplus
 }
 #endif

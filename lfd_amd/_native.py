@@ -40,6 +40,7 @@ SYMBOLS = (
     "lfdmi_defocus_bank_read", "lfdmi_fit_defocus",
     "lfdmi_default_sky_params", "lfdmi_sky_create", "lfdmi_sky_destroy", "lfdmi_sky_dims", "lfdmi_sky_frames", "lfdmi_sky_normalize",
     "lfdmi_inject_trails",
+    "lfdmi_default_radon_params", "lfdmi_radon_create", "lfdmi_radon_destroy", "lfdmi_radon_dims", "lfdmi_radon_search",
 )
 
 
@@ -180,6 +181,36 @@ INJECT_DTYPE = np.dtype([("frame", "<i4"), ("table", "<i4"), ("rho", "<f8"), ("t
 INJECT_MAX_TABLE = 4097
 
 
+class RadonParamsStruct(C.Structure):
+    """lfdmi_radon_params (include/lfdmi.h: faint-trail search)."""
+    _fields_ = [("bin", C.c_int32), ("min_len", C.c_int32), ("clip", C.c_float), ("threshold", C.c_float)]
+
+
+class RadonResult(C.Structure):
+    """lfdmi_radon_result: one record per frame of lfdmi_radon_search."""
+    _fields_ = [("status", C.c_int32), ("found", C.c_int32), ("q", C.c_int32), ("y0", C.c_int32), ("s", C.c_int32),
+                ("n_pix", C.c_int32), ("sum", C.c_float), ("snr", C.c_float),
+                ("x1", C.c_double), ("y1", C.c_double), ("x2", C.c_double), ("y2", C.c_double), ("rho", C.c_double), ("theta", C.c_double)]
+
+
+RADON_DTYPE = np.dtype([("status", "<i4"), ("found", "<i4"), ("q", "<i4"), ("y0", "<i4"), ("s", "<i4"), ("n_pix", "<i4"),
+                        ("sum", "<f4"), ("snr", "<f4"), ("x1", "<f8"), ("y1", "<f8"), ("x2", "<f8"), ("y2", "<f8"),
+                        ("rho", "<f8"), ("theta", "<f8")])
+RADON_OK, RADON_NO_LINE = 0, 1
+
+
+def make_radon_params(**params):
+    """lfdmi_default_radon_params with the given fields replaced (unknown names raise)."""
+    p = RadonParamsStruct()
+    lib().lfdmi_default_radon_params(C.byref(p))
+    names = {k for k, _ in RadonParamsStruct._fields_}
+    for k, v in params.items():
+        if k not in names:
+            raise TypeError(f"unknown radon parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
 _lib = None
 
 
@@ -237,6 +268,13 @@ def lib():
                                              C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.lfdmi_inject_trails.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                              C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int]
+        _lib.lfdmi_default_radon_params.restype = None
+        _lib.lfdmi_default_radon_params.argtypes = [C.c_void_p]
+        _lib.lfdmi_radon_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
+        _lib.lfdmi_radon_destroy.restype = None
+        _lib.lfdmi_radon_destroy.argtypes = [C.c_void_p]
+        _lib.lfdmi_radon_dims.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.lfdmi_radon_search.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     return _lib
 
 
@@ -500,7 +538,7 @@ class Context:
                 self._end_oldest()
             for b in list(getattr(self, "_banks", ())):       # defocus banks of this context close with it
                 b.close()
-            for k in list(getattr(self, "_skies", ())):       # and so do its sky handles
+            for k in list(getattr(self, "_skies", ())):       # and so do its sky and radon handles
                 k.close()
             self._h = None
             self._lib.lfdmi_ctx_destroy(h)
@@ -1025,3 +1063,62 @@ class Sky:
         ctx._chk(self._lib.lfdmi_sky_normalize(ctx._h, self._s, _ptr(frames), code, n, loc, _ptr(out), out_loc, _ptr(rec), _ptr(mb),
                                                _ptr(ms)))
         return (rec, mb, ms) if meshes else rec
+
+
+class Radon:
+    """lfdmi_radon: the faint-trail search of frames of ``shape`` on ``ctx``'s device (include/lfdmi.h: faint-trail search).
+    The handle owns the transform's planes for ``max_frames`` frames; ``Context.close()`` closes it first."""
+
+    def __init__(self, ctx, shape, max_frames=None, **params):
+        self._r = C.c_void_p()
+        self._lib = lib()
+        self.ctx = ctx
+        if not getattr(ctx, "_h", None):
+            raise ValueError("the context is closed")
+        self.shape = (int(shape[0]), int(shape[1]))
+        self.max_frames = int(ctx.max_inflight if max_frames is None else max_frames)
+        self.params = make_radon_params(**params)
+        ctx._chk(self._lib.lfdmi_radon_create(ctx._h, self.shape[0], self.shape[1], self.max_frames, C.byref(self.params),
+                                              C.byref(self._r)))
+        import weakref
+        ctx.__dict__.setdefault("_skies", weakref.WeakSet()).add(self)
+        self.p01, self.p23, self.bytes = self.dims()
+
+    def dims(self):
+        """(P of orientations 0 and 1, P of orientations 2 and 3, device bytes held)"""
+        a, b, nb = C.c_int32(), C.c_int32(), C.c_int64()
+        self.ctx._chk(self._lib.lfdmi_radon_dims(self._r, C.byref(a), C.byref(b), C.byref(nb)))
+        return a.value, b.value, nb.value
+
+    def close(self):
+        if getattr(self, "_r", None):
+            self._lib.lfdmi_radon_destroy(self._r)
+            self._r = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def search(self, frames, sigma=None, pinned=False, native_device=False):
+        """The line of largest signal-to-noise of every frame ('<f4' / '>f4' numpy, torch CUDA float32, ``DeviceFrames``), only
+        read.  sigma: None (0.025), a number or n values, the frames' sky sigma.  Returns RADON_DTYPE records [n]."""
+        if not self._r or not getattr(self.ctx, "_h", None):
+            raise ValueError("the radon handle is closed")
+        ctx = self.ctx
+        frames, code, n, h, w, loc = ctx._frames(frames, pinned, "Radon.search", native_device=native_device)
+        if (h, w) != self.shape:
+            raise NativeError(ERR_ARG, f"Radon.search: frames of {h} x {w}, the handle was made for {self.shape[0]} x {self.shape[1]}")
+        sg = None
+        if sigma is not None:
+            sg = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, np.float32), (n,)))
+        res = np.zeros(n, RADON_DTYPE)
+        ctx._chk(self._lib.lfdmi_radon_search(ctx._h, self._r, _ptr(frames), code, n, loc, _ptr(sg), _ptr(res)))
+        return res

@@ -218,6 +218,57 @@ class _SkyStage:
         self._handles = {}
 
 
+class _RadonStage:
+    """The faint-trail search behind detection for ``DetectTrails(radon=True)`` (include/lfdmi.h: faint-trail search): a
+    ``Radon`` handle per (context, shape), kept while it is large enough, and the radon.txt rows.  ``sigma``: the frames' sky
+    sigma (target_sigma of the sky normalisation when that ran, else 0.025)."""
+
+    def __init__(self, out, params, sigma):
+        from ..radon import as_params
+        self.out, self.params, self.sigma, self._handles = out, as_params(params), float(sigma), {}
+
+    def _handle(self, ctx, shape, n):
+        key = (id(ctx), tuple(shape))
+        h = self._handles.get(key)
+        if h is None or h.ctx is not ctx or not h._r or h.max_frames < n:
+            if h is not None:
+                h.close()
+            h = self._handles[key] = _native.Radon(ctx, shape, max_frames=n, **self.params)
+        return h
+
+    def batch(self, ctx, frames, shape, todo, **where):
+        """the frames ``todo`` (ascending positions in ``frames``), searched in runs of neighbours -> {position: record}"""
+        out, k = {}, 0
+        while k < len(todo):
+            m = k
+            while m + 1 < len(todo) and todo[m + 1] == todo[m] + 1:
+                m += 1
+            a, b = todo[k], todo[m] + 1
+            part = frames.slice(a, b) if isinstance(frames, _native.DeviceFrames) else frames[a:b]
+            recs = self._handle(ctx, shape, min(b - a, 16)).search(part, sigma=self.sigma, **where)
+            out.update(zip(range(a, b), recs))
+            k = m + 1
+        return out
+
+    def one(self, img):
+        """one host frame -> its record"""
+        img = _np.ascontiguousarray(img, _np.float32)
+        with use_context(*img.shape) as ctx:
+            return self._handle(ctx, img.shape, 1).search(img, sigma=self.sigma)[0]
+
+    def row(self, key, rec):
+        from ..radon import format_row
+        self.out.write(format_row(key, rec) + "\n")
+
+    def flush(self):
+        self.out.flush()
+
+    def close(self):
+        for h in self._handles.values():
+            h.close()
+        self._handles = {}
+
+
 def _load_frame(run, camcol, filter, field):
     """Frame image (float32, C-contiguous), results-row head, photoObj columns; raises like the
     reference when neither the .fits nor the .fits.bz2 exists (detecttrails.py:81-87)."""
@@ -282,15 +333,16 @@ class _Chunk:
     """What one driver call runs with -- the output files, the three parameter dictionaries, the profiles sink (``add(key, trail,
     profile)``) with its trail params, the ``_SkyStage`` -- and the per-frame slots of its ``n`` frames: ``rows[i]`` the
     detection record, what ``process_frame_arrays`` returned, or the exception that is the frame's errors entry; ``meas[i]``
-    (trail record, profile) or the measurement's exception; ``srecs[i]`` the sky record if the frame was normalised.  A new
+    (trail record, profile) or the measurement's exception; ``srecs[i]`` the sky record if the frame was normalised;
+    ``rlines[i]`` the faint-trail record of a frame without a detection (``radon``: a ``_RadonStage``), or its exception.  A new
     per-frame product gets a slot here, a step in ``_run_group`` and ``_run_frame``, and its row in ``_emit``."""
 
-    def __init__(self, n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky):
-        self.results, self.errors, self.profiles, self.sky = results, errors, profiles, sky
+    def __init__(self, n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon=None):
+        self.results, self.errors, self.profiles, self.sky, self.radon = results, errors, profiles, sky, radon
         self.params_bright, self.params_dim, self.params_removestars = params_bright, params_dim, params_removestars
         self.trail_params = trail_params or {}
         self.debug = params_bright.get("debug") or params_dim.get("debug")
-        self.rows, self.meas, self.srecs = [None] * n, [None] * n, [None] * n
+        self.rows, self.meas, self.srecs, self.rlines = [None] * n, [None] * n, [None] * n, [None] * n
         self.gpu_s = 0.0                              # inside the sky + detect calls of the groups that went through
 
 
@@ -307,6 +359,11 @@ def _run_frame(c, i, filter, frame):
                 c.meas[i] = measure_trail(img, c.rows[i][2], cat, filter, c.params_removestars, **c.trail_params)
             except Exception as e:  # noqa: BLE001
                 c.meas[i] = e
+        if c.radon is not None and not c.rows[i][0]:
+            try:
+                c.rlines[i] = c.radon.one(img)
+            except Exception as e:  # noqa: BLE001
+                c.rlines[i] = e
     except Exception as e:  # noqa: BLE001 - the reference swallows everything per frame
         c.rows[i] = e
 
@@ -340,6 +397,14 @@ def _run_group(c, idx, filter, shape, inflight, source, second, detect_kw=None, 
                 except Exception as e:  # noqa: BLE001
                     for i in idx:
                         c.meas[i] = e
+            if c.radon is not None:                   # the frames without a detection, where the detect call left them
+                todo = [j for j, r in enumerate(recs) if not int(r["status"]) and not int(r["found"])]
+                try:
+                    for j, line in c.radon.batch(ctx, frames, shape, todo, **measure_kw).items():
+                        c.rlines[idx[j]] = line
+                except Exception as e:  # noqa: BLE001
+                    for j in todo:
+                        c.rlines[idx[j]] = e
         for i, rec in zip(idx, recs):
             c.rows[i] = rec
     except Exception as e:  # noqa: BLE001
@@ -370,6 +435,11 @@ def _emit(c, i, key, head, shape):
     except Exception as e:  # noqa: BLE001
         _log_error(c.errors, key, e, c.debug)
         return
+    line = c.rlines[i]
+    if isinstance(line, Exception):
+        _log_error(c.errors, key, line, c.debug)
+    elif line is not None and int(line["found"]):
+        c.radon.row(key, line)
     if not detection or c.profiles is None:
         return
     try:                                              # (results.txt is written before, untouched)
@@ -382,14 +452,15 @@ def _emit(c, i, key, head, shape):
 
 
 def process_field(results, errors, run, camcol, filter, field, params_bright, params_dim,
-                  params_removestars, profiles=None, trail_params=None, sky=None):
+                  params_removestars, profiles=None, trail_params=None, sky=None, radon=None):
     """One frame end to end (reference: detecttrails.py:30-143): locate the frame (or its .bz2),
     read image + header + photoObj, detect, append ``run camcol filter field tai crpix1 crpix2
     crval1 crval2 cd11 cd12 cd21 cd22 x1 y1 x2 y2`` to ``results``; every exception is logged
     to ``errors`` (ids, 3-frame traceback, message) and swallowed.  ``profiles``: the sink (``add(key, trail, profile)``) the
     frame's trail profile goes to when it has a detection.  ``sky``: a ``_SkyStage``; the frame is normalised first and its
-    sky.txt row written (detection and profile then refer to the normalised frame)."""
-    c = _Chunk(1, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky)
+    sky.txt row written (detection and profile then refer to the normalised frame).  ``radon``: a ``_RadonStage``; a frame
+    without a detection is searched for a faint trail and a line that is found gets its radon.txt row."""
+    c = _Chunk(1, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon)
     head = None
     try:
         img, head, cat = _load_frame(run, camcol, filter, field)
@@ -432,18 +503,20 @@ def process_fields_batched(results, errors, ids, params_bright, params_dim, para
         _emit(c, i, item[0], *((item[2], item[1].shape) if len(item) == 4 else (None, None)))
 
 
-def process_loaded(results, errors, loaded, params_bright, params_dim, params_removestars, profiles=None, trail_params=None, sky=None):
+def process_loaded(results, errors, loaded, params_bright, params_dim, params_removestars, profiles=None, trail_params=None, sky=None,
+                   radon=None):
     """process_fields_batched for a chunk the loader has read (``loader.Loaded``): the frames that sit in pinned memory go to
     the GPU as contiguous same-filter slices of that memory with the matching rows of the padded catalogue arrays (no copy
     of a frame on the host, no per-frame Python), the others take the per-frame path; rows and errors entries come out in
     the caller's order, each frame under its own try (detecttrails.py:119-139).  ``sky``: a
     ``_SkyStage``: every slice is normalised into the handle's device buffer first (the pinned big-endian slots go in as they
     are), detection and measurement run on that buffer, and one sky.txt row per normalised frame is written, in the caller's
-    order, ahead of the frame's results row."""
+    order, ahead of the frame's results row.  ``radon``: a ``_RadonStage``: after each slice's detection call its frames without
+    a detection are searched where that call left them, and the lines found get their radon.txt rows."""
     import time
     t_in = time.perf_counter()
     n = len(loaded.keys)
-    c = _Chunk(n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky)
+    c = _Chunk(n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon)
     by_slot = {}
     for i in range(n):
         if loaded.error[i] is not None:
@@ -509,6 +582,11 @@ class DetectTrails:
     ``<savepath>/sky.txt``) gets one row per frame that loaded: ``run camcol filter field status sky sigma gain n_empty``,
     written ahead of the chunk's progress marks; rank files, resume and ``Jobs`` treat it like results.txt.  Profiles and
     defocus fits then refer to the normalised frame: flux = value / gain + sky.
+    ``radon=True`` (default off): after each chunk's detection call the frames WITHOUT a detection are searched for a trail that
+    is faint in every pixel but long (include/lfdmi.h: faint-trail search; ``radon_params``: dict or
+    ``lfd_amd.radon.RadonParams``), with the sky sigma ``target_sigma`` under ``normalize=True`` and 0.025 otherwise.  A line
+    that is found gets a row in ``radon_file`` (default ``<savepath>/radon.txt``): ``run camcol filter field x1 y1 x2 y2 snr
+    n_pix``.  results.txt does not change with it.
     """
 
     _FILTERS = ('u', 'g', 'r', 'i', 'z')
@@ -532,6 +610,10 @@ class DetectTrails:
         self.sky_params = as_params(kwargs.get("sky_params"))
         if self.normalize:
             _native.make_sky_params(**self.sky_params)          # (unknown names raise here, not per frame)
+        self.radon = bool(kwargs.get("radon", False))
+        self.radon_file = kwargs.get("radon_file", os.path.join(save, "radon.txt"))
+        from ..radon import as_params as radon_as_params
+        self.radon_params = radon_as_params(kwargs.get("radon_params"))
         if self.trail_profiles:
             _native.make_trail_params(**self.trail_params)      # (unknown names raise here, not per frame)
         if self.defocus:
@@ -686,13 +768,18 @@ class DetectTrails:
                 open(progress_path, "w" if fresh else "a") as progress, \
                 (open(self.profiles + suffix, "a") if self.trail_profiles else contextlib.nullcontext()) as profiles, \
                 (open(self.defocus_file + suffix, "a") if self.defocus else contextlib.nullcontext()) as defocus_out, \
-                (open(self.sky_file + suffix, "a") if self.normalize else contextlib.nullcontext()) as sky_out:
+                (open(self.sky_file + suffix, "a") if self.normalize else contextlib.nullcontext()) as sky_out, \
+                (open(self.radon_file + suffix, "a") if self.radon else contextlib.nullcontext()) as radon_out:
             if self.trail_profiles:
                 profiles = _DefocusTee(profiles, defocus_out, self.defocus_params, self.trail_params)
             prof_kw = {"profiles": profiles, "trail_params": self.trail_params} if self.trail_profiles else {}
             sky = _SkyStage(sky_out, self.sky_params) if self.normalize else None
             if sky is not None:
                 prof_kw["sky"] = sky
+            radon = None
+            if self.radon:
+                sigma = _native.make_sky_params(**self.sky_params).target_sigma if self.normalize else 0.025
+                radon = prof_kw["radon"] = _RadonStage(radon_out, self.radon_params, sigma)
             if fresh:
                 progress.write(header + "\n")
                 progress.flush()
@@ -704,6 +791,8 @@ class DetectTrails:
                     profiles.flush()
                 if sky is not None:
                     sky.flush()
+                if radon is not None:
+                    radon.flush()
                 progress.write("".join("%s %s %s %s\n" % tuple(k) for k in done_keys))
                 progress.flush()
 
@@ -713,6 +802,8 @@ class DetectTrails:
                     mark([key])
                 if sky is not None:
                     sky.close()
+                if radon is not None:
+                    radon.close()
                 self.last_stats["seconds"] = time.perf_counter() - t_start
                 return
             # a chunk = one GPU call: 64 frames keep the link and the GPU busy for plain files; a selection that exists only as
@@ -763,5 +854,7 @@ class DetectTrails:
                 self.last_stats["bz2"] = dict(loader.bz2_stats)
                 if sky is not None:
                     sky.close()
+                if radon is not None:
+                    radon.close()
                 loader.close()
                 self.last_stats["seconds"] = time.perf_counter() - t_start

@@ -1,0 +1,119 @@
+"""Faint-trail search: the line of largest signal-to-noise of a whole frame by the dyadic fast Radon transform -- for trails
+that are faint in every pixel but long, which the detector cannot see (include/lfdmi.h: faint-trail search).  ``_native.Radon``
+is the device handle; this module holds the parameters, the host conversion of a working line to the frame (usable without a
+device), a one-call helper and the radon.txt format of ``DetectTrails(radon=True)``.
+"""
+import dataclasses
+import math
+
+import numpy as np
+
+from . import _native
+
+RADON_DTYPE = _native.RADON_DTYPE
+OK, NO_LINE = _native.RADON_OK, _native.RADON_NO_LINE
+DEFAULT_SIGMA = 0.025
+RADON_COLUMNS = ("run", "camcol", "filter", "field", "x1", "y1", "x2", "y2", "snr", "n_pix")
+
+
+@dataclasses.dataclass
+class RadonParams:
+    """lfdmi_radon_params with its defaults; ``validate`` applies the library's rules without a device."""
+    bin: int = 2
+    clip: float = 0.125
+    min_len: int = 256
+    threshold: float = 8.0
+
+    def as_dict(self):
+        return dataclasses.asdict(self)
+
+    def validate(self):
+        if self.bin not in (1, 2, 4):
+            raise ValueError("bin must be 1, 2 or 4")
+        if not (math.isfinite(self.clip) and self.clip > 0):
+            raise ValueError("clip must be positive")
+        if int(self.min_len) != self.min_len or self.min_len < 1:
+            raise ValueError("min_len must be an integer >= 1")
+        if math.isnan(self.threshold):
+            raise ValueError("threshold must be a number")
+        return self
+
+
+def default_params():
+    """lfdmi_default_radon_params as a RadonParams (read from the library: no GPU needed)."""
+    p = _native.make_radon_params()
+    return RadonParams(**{k: getattr(p, k) for k, _ in _native.RadonParamsStruct._fields_})
+
+
+def as_params(params):
+    """None / dict / RadonParams -> validated dict of lfdmi_radon_params fields"""
+    if params is None:
+        return {}
+    if isinstance(params, RadonParams):
+        return params.validate().as_dict()
+    unknown = set(params) - {f.name for f in dataclasses.fields(RadonParams)}
+    if unknown:
+        raise TypeError(f"unknown radon parameter {sorted(unknown)[0]!r}")
+    RadonParams(**params).validate()
+    return dict(params)
+
+
+def working_dims(shape, bin):
+    """(Hb, Wb, P of orientations 0 and 1, P of orientations 2 and 3)"""
+    h, w = int(shape[0]), int(shape[1])
+    hb, wb = -(-h // bin), -(-w // bin)
+    return hb, wb, 1 << max(0, (wb - 1).bit_length()), 1 << max(0, (hb - 1).bit_length())
+
+
+def line_of(q, y0, s, shape, bin):
+    """Step 6 of the definition: the working line (q, y0, s) of frames of ``shape`` searched at ``bin`` as (x1, y1, x2, y2, rho,
+    theta) in the detection records' coordinates (x = column, y = row of the flipped frame); theta in [0, pi) and
+    x cos(theta) + y sin(theta) = rho."""
+    if q not in (0, 1, 2, 3):
+        raise ValueError("q must be 0 .. 3")
+    if bin not in (1, 2, 4):
+        raise ValueError("bin must be 1, 2 or 4")
+    hb, wb, p01, p23 = working_dims(shape, bin)
+    P = p01 if q < 2 else p23
+    pts = []
+    for c, r in ((0, int(y0)), (P - 1, int(y0) + int(s))):
+        i, j = ((c, r), (c, hb - 1 - r), (r, c), (wb - 1 - r, c))[q]
+        pts.append((bin * i + (bin - 1) / 2.0, bin * j + (bin - 1) / 2.0))
+    (x1, y1), (x2, y2) = pts
+    theta = math.atan2(-(x2 - x1), y2 - y1)
+    if theta < 0.0:
+        theta += math.pi
+    if theta >= math.pi:
+        theta -= math.pi
+    return x1, y1, x2, y2, x1 * math.cos(theta) + y1 * math.sin(theta), theta
+
+
+def search_frames(ctx, frames, sigma=None, **params):
+    """Search (n, h, w) or (h, w) frames on ``ctx``: RADON_DTYPE records, one per frame.  For repeated calls keep a
+    ``_native.Radon`` handle instead: this one is created and destroyed per call."""
+    arr = frames if _native._is_dev(frames) or isinstance(frames, _native.DeviceFrames) else np.asarray(frames)
+    shp = tuple(arr.shape)
+    n, h, w = (1, *shp) if len(shp) == 2 else shp
+    with _native.Radon(ctx, (h, w), max_frames=max(1, min(n, ctx.max_inflight)), **as_params(params)) as r:
+        return r.search(arr, sigma=sigma)
+
+
+def format_row(meta, rec):
+    """One radon.txt row: meta = (run, camcol, filter, field); floats with repr."""
+    return " ".join(str(v) for v in (*meta, repr(float(rec["x1"])), repr(float(rec["y1"])), repr(float(rec["x2"])),
+                                      repr(float(rec["y2"])), repr(float(rec["snr"])), int(rec["n_pix"])))
+
+
+def read_radon(path):
+    """radon.txt (rows only, no header line) -> list of dicts keyed by RADON_COLUMNS."""
+    rows = []
+    with open(path) as f:
+        for ln in f:
+            parts = ln.split()
+            if not parts:
+                continue
+            r = {}
+            for k, v in zip(RADON_COLUMNS, parts):
+                r[k] = v if k == "filter" else int(v) if k in ("run", "camcol", "field", "n_pix") else float(v)
+            rows.append(r)
+    return rows

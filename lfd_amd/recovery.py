@@ -1,7 +1,7 @@
 """Injection and recovery: add model trails of known line and brightness to frames, detect, and count what comes back -- the
 detector's efficiency as a function of the trail's peak (include/lfdmi.h: trail injection).
 
-    python -m lfd_amd.recovery --synth K0:N --peaks 0.05,0.1,0.2,5 --out DIR
+    python -m lfd_amd.recovery --synth K0:N --peaks 0.05,0.1,0.2,5 --out DIR [--detector radon]
 
 The plan (``draw_trails``), the matching (``match``) and the rows use integer RNG draws and IEEE + - * / sqrt only -- cos and sin
 come from ``cos_sin`` below, a fixed sequence of multiplications and additions -- so every machine draws the same plan and
@@ -162,12 +162,25 @@ def make_rows(records, trails, params_bright, params_dim, shape, k=K_MATCH, meas
     return rows
 
 
+def radon_records(lines):
+    """RADON_DTYPE records -> RESULT_DTYPE records ``match`` can judge: found 1 (so that the cell is params_bright's
+    houghMethod) where the search found a line, with that line's rho and theta"""
+    recs = np.zeros(len(lines), _native.RESULT_DTYPE)
+    recs["found"] = lines["found"] != 0
+    recs["rho"], recs["theta"] = lines["rho"], lines["theta"]
+    return recs
+
+
 def run(ctx, frames, cats, rs, trails, tables, table_step, params_bright=None, params_dim=None, subsample=4, profiles=False,
-        k=K_MATCH):
+        k=K_MATCH, detector="hough", radon_params=None, sigma=None):
     """Copy ``frames`` ((n, h, w) float32 numpy or torch CUDA), inject the plan ``trails`` (tables of peak 1: see
     ``inject.normalise_peak``), run ``detect_batch`` and match: ROW_DTYPE rows, one per trail.  cats: the frames' catalogues
     (a list of dicts, a packed dict or None) and rs their remove_stars parameters; profiles=True also runs ``measure_trails``
-    and fills fwhm."""
+    and fills fwhm.  detector="radon": the stars are removed (``remove_stars``) and the faint-trail search
+    (include/lfdmi.h: faint-trail search; ``radon_params``, ``sigma``) takes the detector's place; its line is matched by the
+    same rule, with params_bright's houghMethod as the cell."""
+    if detector not in ("hough", "radon"):
+        raise ValueError("detector: 'hough' or 'radon'")
     from .catalogs import pack_catalogs
     from .detecttrails import default_params
     pb, pd, _ = default_params()
@@ -177,6 +190,13 @@ def run(ctx, frames, cats, rs, trails, tables, table_step, params_bright=None, p
     n, h, w = work.shape
     packed = pack_catalogs(list(cats)) if isinstance(cats, (list, tuple)) else cats
     ctx.inject_trails(work, to_inject(trails), np.asarray(tables, np.float32), table_step, subsample=subsample)
+    if detector == "radon":
+        from . import radon as _radon
+        if packed is not None:
+            ctx.remove_stars(work, packed, rs)
+        with _native.Radon(ctx, (h, w), max_frames=min(n, 16), **_radon.as_params(radon_params)) as search:
+            lines = search.search(work, sigma=sigma)
+        return make_rows(radon_records(lines), trails, pb, pd, (h, w), k=k)
     recs = ctx.detect_batch(work, pb, pd, packed, rs if packed is not None else None)
     measured = None
     if profiles:
@@ -253,6 +273,9 @@ def main(argv=None):
     ap.add_argument("--sigma", type=float, default=2.0, help="Gaussian cross-section sigma in px")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--profiles", action="store_true", help="also measure the recovered trails' fwhm")
+    ap.add_argument("--detector", choices=("hough", "radon"), default="hough",
+                    help="hough: the detector (default); radon: the faint-trail search in its place")
+    ap.add_argument("--bin", type=int, default=None, help="--detector radon: lfdmi_radon_params.bin")
     a = ap.parse_args(argv)
     k0, n = (int(v) for v in a.synth.split(":"))
     peaks = [float(v) for v in a.peaks.split(",")]
@@ -266,7 +289,8 @@ def main(argv=None):
     table, step = _inject.gaussian_table(a.sigma)
     plan = draw_trails(len(keep), frames.shape[1:], a.seed, peaks)
     with _native.Context(0, frames.shape[1], frames.shape[2], 16) as ctx:
-        rows = run(ctx, frames, cats, rs, plan, _inject.normalise_peak(table), step, pb, pd, profiles=a.profiles)
+        rows = run(ctx, frames, cats, rs, plan, _inject.normalise_peak(table), step, pb, pd, profiles=a.profiles,
+                   detector=a.detector, radon_params={"bin": a.bin} if a.bin else None)
     os.makedirs(a.out, exist_ok=True)
     write_recovery(os.path.join(a.out, "recovery.txt"), rows)
     print(format_table(completeness(rows, peak_edges(peaks))))

@@ -1,0 +1,116 @@
+"""Times lfdmi_radon_search on 256 device-resident SDSS frames at bin 1, 2 and 4: ms per call as the median of repeated calls
+between HIP events, beside the bytes each kernel has to move (the rows a level stores, read once and written once, sums and
+16-bit counts) and the floor those bytes give at the copy rate the project quotes (4.8 TB/s, DESIGN.md: sky normalisation).
+Writes profiles/radon_probe.json.
+
+    python tools/radon_probe.py [--reps 5] [--frames 256] [--max-frames 16] [--out FILE] [--trace]
+
+--trace  one more run per bin under `rocprofv3 --kernel-trace --stats` -> profiles/radon_probe_kernel_stats_bin<b>.csv
+Every GPU step is a child process under its own `timeout`.
+"""
+import argparse
+import glob
+import json
+import os
+import shutil
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+COPY_RATE = 4.8e12
+SHAPE = (1489, 2048)
+
+
+def kernel_bytes(shape, b):
+    """bytes per frame each kernel must move: {kernel: bytes}; a stored value is 6 bytes (float32 sum + 16-bit count)"""
+    from lfd_amd import radon
+    hb, wb, p01, p23 = radon.working_dims(shape, b)
+    out = {"k_radon_prep": 4 * shape[0] * shape[1] + 6 * hb * wb, "k_radon_first": 0, "k_radon_level": 0, "k_radon_level_last": 0,
+           "k_radon_finish": 0}
+    for R, P in ((hb, p01), (hb, p01), (wb, p23), (wb, p23)):
+        G = min(32, P // 2)
+        out["k_radon_first"] += 6 * hb * wb + 6 * (R + G - 1) * P
+        n = G
+        while 2 * n < P:
+            out["k_radon_level"] += 6 * (R + n - 1) * P + 6 * (R + 2 * n - 1) * P
+            n *= 2
+        out["k_radon_level_last"] += 6 * (R + n - 1) * P
+    return out
+
+
+def child(a):
+    import numpy as np
+    import torch
+    from lfd_amd import _native
+    h, w = SHAPE
+    g = torch.Generator(device="cuda").manual_seed(1)
+    frames = torch.randn((a.frames, h, w), generator=g, device="cuda", dtype=torch.float32) * 0.025
+    for b in ((a.bin,) if a.bin else (1, 2, 4)):
+        with _native.Context(0, h, w, 2) as ctx, _native.Radon(ctx, SHAPE, max_frames=a.max_frames, bin=b) as r:
+            rec = r.search(frames)                                  # warm-up: module load, first touch
+            ms = []
+            for _ in range(a.reps):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                rec = r.search(frames)
+                e1.record()
+                e1.synchronize()
+                ms.append(e0.elapsed_time(e1))
+            kb = kernel_bytes(SHAPE, b)
+            total = float(sum(kb.values())) * a.frames
+            med = float(np.median(ms))
+            print("RESULT " + json.dumps({
+                "bin": b, "frames": a.frames, "max_frames": a.max_frames, "shape": list(SHAPE), "P": [r.p01, r.p23],
+                "device_bytes_per_inflight_frame": r.bytes // a.max_frames, "ms_per_call": med, "ms_all": ms,
+                "ms_per_frame": med / a.frames, "bytes_per_frame_by_kernel": kb, "bytes_per_call": total,
+                "ms_floor_at_4.8_TBps": total / COPY_RATE * 1e3, "x_the_floor": med / (total / COPY_RATE * 1e3),
+                "snr_max": float(rec["snr"].max()), "found": int(rec["found"].sum())}), flush=True)
+
+
+def run_child(extra, timeout_s, prefix=()):
+    cmd = ["timeout", "-k", "10", str(timeout_s), *prefix, sys.executable, os.path.abspath(__file__), "--child", *extra]
+    p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
+    if p.returncode:
+        raise SystemExit("radon_probe: %s ended with status %d" % (" ".join(cmd), p.returncode))
+    return [json.loads(ln[7:]) for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--trace", action="store_true")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--frames", type=int, default=256)
+    ap.add_argument("--max-frames", type=int, default=16)
+    ap.add_argument("--bin", type=int, default=0)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "radon_probe.json"))
+    ap.add_argument("--child", action="store_true")
+    a = ap.parse_args()
+    if a.child:
+        child(a)
+        return
+    common = ["--frames", str(a.frames), "--max-frames", str(a.max_frames)]
+    doc = {"tool": "tools/radon_probe.py", "copy_rate_TBps": COPY_RATE / 1e12,
+           "runs": run_child(common + ["--reps", str(a.reps)], 500)}
+    for r in doc["runs"]:
+        print({k: r[k] for k in ("bin", "ms_per_call", "ms_floor_at_4.8_TBps", "x_the_floor")}, flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(doc, f, indent=1)
+    if a.trace:
+        for b in (1, 2, 4):
+            tmp = tempfile.mkdtemp(prefix="radon_probe_")
+            try:
+                run_child(["--frames", "32", "--max-frames", str(a.max_frames), "--reps", "1", "--bin", str(b)], 300,
+                          ["rocprofv3", "--kernel-trace", "--stats", "-d", tmp, "-o", "radon", "--output-format", "csv", "--"])
+                found = glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True)
+                if not found:
+                    raise SystemExit("radon_probe: rocprofv3 wrote no kernel_stats.csv")
+                shutil.copy(found[0], os.path.join(os.path.dirname(os.path.abspath(a.out)), "radon_probe_kernel_stats_bin%d.csv" % b))
+            finally:
+                shutil.rmtree(tmp, ignore_errors=True)
+
+
+if __name__ == "__main__":
+    main()
