@@ -741,8 +741,34 @@ int lfdmi_inject_trails(lfdmi_ctx *ctx, void *frames, int dtype, int n, int h, i
  *    points (c = 0, r = y0) and (c = P-1, r = y0 + s); these map back through the orientation to binned (i, j) -- q = 0: (c, r),
  *    1: (c, Hb-1-r), 2: (r, c), 3: (Wb-1-r, c) -- and to pixels as b i + (b-1)/2, b j + (b-1)/2 (points outside the frame are
  *    not clipped).  theta = atan2(-(x2-x1), y2-y1) folded into [0, pi), rho = x1 cos(theta) + y1 sin(theta): the line is
- *    x cos(theta) + y sin(theta) = rho, as in lfdmi_result. */
+ *    x cos(theta) + y sin(theta) = rho, as in lfdmi_result.
+ *
+ * lfdmi_radon_search_lines reports several lines per frame by peeling, and where along its line each trail starts and stops.
+ * The transform of a trail is a butterfly of neighbouring lines that share its pixels, so the next best entries of one
+ * transform would be the same trail again: the found line's band is blotted out of the binned frame and the frame is
+ * transformed again, until nothing reaches the threshold.  tests/radon_lines_ref.py restates steps 7 - 9.
+ * 7. Dyadic path.  d(c; s, P) is the row offset of line (y, s) in column c: d(0; 0, 1) = 0; for c < P/2 it is d(c; s>>1, P/2),
+ *    otherwise ((s+1)>>1) + d(c - P/2; s>>1, P/2) -- step 4's recursion unrolled.  The line (q, y0, s) is the cells
+ *    Q[y0 + d(c)][c], c = 0 .. C-1.
+ * 8. Rounds.  Round 0 is steps 1 - 6 on V_0 = V, M_0 = M; a frame's round-k record (step 6) is kept as line k.  The frame goes
+ *    on to round k+1 when that record is LFDMI_RADON_OK with found = 1 and k+1 < max_lines; otherwise it stops.  With
+ *    hw = ceil(peel_halfwidth / bin) cells, V_{k+1}, M_{k+1} are V_k, M_k with every cell set to +0 / 0 whose working
+ *    coordinates in orientation q are (r, c), 0 <= c < C, 0 <= r < R, |r - (y0 + d(c))| <= hw (mapped to V through step 3; the
+ *    band is the whole crossing, whatever step 9 finds); steps 3 - 6 then run on them.  n_lines = the number of records with
+ *    found = 1: records 0 .. n_lines-1, in peel order.  If n_lines < max_lines, record n_lines is the round that stopped the
+ *    frame (its best line below the threshold, or LFDMI_RADON_NO_LINE); later records are all zero.  Record 0 is bit for bit
+ *    what lfdmi_radon_search returns.
+ * 9. Extent, of every record with found = 1, on the arrays it was found in (before its own peel).  a_c = Q[y0 + d(c)][c]
+ *    where the row exists, else +0; m_c the same on M.  pre[0] = +0, pre[c+1] = pre[c] + a_c: one sequential float32
+ *    accumulator; cnt the same sum of m_c in integers.  For 0 <= c1 <= c2 <= C-1: A = pre[c2+1] - pre[c1] (one float32
+ *    subtraction), N = cnt[c2+1] - cnt[c1]; the interval is a candidate when N >= min_seg and its score is
+ *    A / (sigma * sqrtf((float)N)) with step 5's three roundings.  The segment is the candidate of largest score, ties to the
+ *    lowest (c1, c2); min_seg <= min_len, so a found line always has one.  ex1, ey1, ex2, ey2 (double, on the host) are the
+ *    working points (c1, y0 + d(c1)) and (c2, y0 + d(c2)) through step 6's mapping.  Nothing is decided on seg_snr: it is a
+ *    measurement, the maximum over about C * C / 2 intervals and therefore biased upward.  The device scores each of those
+ *    intervals: C * C / 2 scores per found line (C = 1024 / 745 for an SDSS frame at bin 2). */
 enum { LFDMI_RADON_OK = 0, LFDMI_RADON_NO_LINE = 1 };
+#define LFDMI_RADON_MAX_LINES 8
 typedef struct {
     int32_t bin;          /* 1, 2 or 4; default 2 */
     int32_t min_len;      /* valid pixels a candidate line needs (>= 1); default 256 */
@@ -773,6 +799,33 @@ int lfdmi_radon_dims(const lfdmi_radon *radon, int32_t *p01, int32_t *p23, int64
  * on the context's stream and waits for it once, at its end. */
 int lfdmi_radon_search(lfdmi_ctx *ctx, lfdmi_radon *radon, const void *frames, int dtype, int n, int loc, const float *sigma,
                        lfdmi_radon_result *results);
+typedef struct {
+    int32_t max_lines;        /* lines reported per frame at most, 1 .. LFDMI_RADON_MAX_LINES; default 4 */
+    int32_t peel_halfwidth;   /* half-width in pixels of the band blotted around a found line (>= 0); default 8 */
+    int32_t min_seg;          /* valid pixels a segment needs, 1 .. the handle's min_len; default 64 */
+} lfdmi_radon_lines_params;
+typedef struct {
+    int32_t status;       /* as in lfdmi_radon_result, down to theta */
+    int32_t found;
+    int32_t q, y0, s;
+    int32_t n_pix;
+    float sum, snr;
+    double x1, y1, x2, y2, rho, theta;
+    int32_t c1, c2;       /* the segment: working columns c1 .. c2 of the line (step 9); found = 0: this and the rest are 0 */
+    int32_t seg_n_pix;    /* N of the segment */
+    int32_t pad;
+    float seg_sum, seg_snr;   /* A and its score: a maximum over about C * C / 2 intervals, biased upward; nothing is decided on it */
+    double ex1, ey1, ex2, ey2;   /* the segment's end points, in the coordinates of x1 .. y2 */
+} lfdmi_radon_line;
+void lfdmi_default_radon_lines_params(lfdmi_radon_lines_params *out);
+/* lfdmi_radon_search with steps 7 - 9: frames, dtype, n, loc and sigma as there.  lp NULL: the defaults.  lines: n * max_lines
+ * records (host), frame i's at lines[i * max_lines ..]; n_lines: n counts (host).  Out-of-range parameters (min_seg above the
+ * handle's min_len among them): LFDMI_ERR_ARG, and nothing runs.  On its first call the handle allocates a second V, M set
+ * (6 bytes per binned pixel per frame) and the lines' prefix arrays; lfdmi_radon_dims counts them from then on.  The frames
+ * are only read; the call refuses while calls are in flight, runs on the context's stream and waits for it once per round
+ * of each chunk (the host decides which frames continue). */
+int lfdmi_radon_search_lines(lfdmi_ctx *ctx, lfdmi_radon *radon, const void *frames, int dtype, int n, int loc, const float *sigma,
+                             const lfdmi_radon_lines_params *lp, lfdmi_radon_line *lines, int32_t *n_lines);
 
 #ifdef __cplusplus
 }

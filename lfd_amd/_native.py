@@ -41,6 +41,7 @@ SYMBOLS = (
     "lfdmi_default_sky_params", "lfdmi_sky_create", "lfdmi_sky_destroy", "lfdmi_sky_dims", "lfdmi_sky_frames", "lfdmi_sky_normalize",
     "lfdmi_inject_trails",
     "lfdmi_default_radon_params", "lfdmi_radon_create", "lfdmi_radon_destroy", "lfdmi_radon_dims", "lfdmi_radon_search",
+    "lfdmi_default_radon_lines_params", "lfdmi_radon_search_lines",
 )
 
 
@@ -199,6 +200,36 @@ RADON_DTYPE = np.dtype([("status", "<i4"), ("found", "<i4"), ("q", "<i4"), ("y0"
 RADON_OK, RADON_NO_LINE = 0, 1
 
 
+class RadonLinesParamsStruct(C.Structure):
+    """lfdmi_radon_lines_params (include/lfdmi.h: faint-trail search, steps 7 - 9)."""
+    _fields_ = [("max_lines", C.c_int32), ("peel_halfwidth", C.c_int32), ("min_seg", C.c_int32)]
+
+
+class RadonLine(C.Structure):
+    """lfdmi_radon_line: one record per frame and round of lfdmi_radon_search_lines."""
+    _fields_ = RadonResult._fields_ + [("c1", C.c_int32), ("c2", C.c_int32), ("seg_n_pix", C.c_int32), ("pad", C.c_int32),
+                                       ("seg_sum", C.c_float), ("seg_snr", C.c_float),
+                                       ("ex1", C.c_double), ("ey1", C.c_double), ("ex2", C.c_double), ("ey2", C.c_double)]
+
+
+RADON_LINE_DTYPE = np.dtype(RADON_DTYPE.descr + [("c1", "<i4"), ("c2", "<i4"), ("seg_n_pix", "<i4"), ("pad", "<i4"),
+                                                 ("seg_sum", "<f4"), ("seg_snr", "<f4"),
+                                                 ("ex1", "<f8"), ("ey1", "<f8"), ("ex2", "<f8"), ("ey2", "<f8")])
+RADON_MAX_LINES = 8
+
+
+def make_radon_lines_params(**params):
+    """lfdmi_default_radon_lines_params with the given fields replaced (unknown names raise)."""
+    p = RadonLinesParamsStruct()
+    lib().lfdmi_default_radon_lines_params(C.byref(p))
+    names = {k for k, _ in RadonLinesParamsStruct._fields_}
+    for k, v in params.items():
+        if k not in names:
+            raise TypeError(f"unknown radon lines parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
 def make_radon_params(**params):
     """lfdmi_default_radon_params with the given fields replaced (unknown names raise)."""
     p = RadonParamsStruct()
@@ -275,6 +306,10 @@ def lib():
         _lib.lfdmi_radon_destroy.argtypes = [C.c_void_p]
         _lib.lfdmi_radon_dims.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.lfdmi_radon_search.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        _lib.lfdmi_default_radon_lines_params.restype = None
+        _lib.lfdmi_default_radon_lines_params.argtypes = [C.c_void_p]
+        _lib.lfdmi_radon_search_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p]
     return _lib
 
 
@@ -1122,3 +1157,25 @@ class Radon:
         res = np.zeros(n, RADON_DTYPE)
         ctx._chk(self._lib.lfdmi_radon_search(ctx._h, self._r, _ptr(frames), code, n, loc, _ptr(sg), _ptr(res)))
         return res
+
+    def search_lines(self, frames, sigma=None, max_lines=4, peel_halfwidth=8, min_seg=64, pinned=False, native_device=False):
+        """Up to ``max_lines`` lines per frame by peeling, each with its extent (include/lfdmi.h: faint-trail search, steps
+        7 - 9); frames and sigma as in ``search``.  Returns (RADON_LINE_DTYPE records [n, max_lines], n_lines [n]): a frame's
+        found lines are its records 0 .. n_lines-1 in peel order, record n_lines (if there is room) is the round that stopped
+        it.  The first call allocates the second V, M set; ``dims()`` counts it from then on."""
+        if not self._r or not getattr(self.ctx, "_h", None):
+            raise ValueError("the radon handle is closed")
+        ctx = self.ctx
+        lp = make_radon_lines_params(max_lines=max_lines, peel_halfwidth=peel_halfwidth, min_seg=min_seg)
+        frames, code, n, h, w, loc = ctx._frames(frames, pinned, "Radon.search_lines", native_device=native_device)
+        if (h, w) != self.shape:
+            raise NativeError(ERR_ARG, f"Radon.search_lines: frames of {h} x {w}, the handle was made for {self.shape[0]} x {self.shape[1]}")
+        sg = None
+        if sigma is not None:
+            sg = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, np.float32), (n,)))
+        k = max(1, min(int(lp.max_lines), RADON_MAX_LINES))      # (out of range: the library refuses before it writes)
+        res = np.zeros((n, k), RADON_LINE_DTYPE)
+        nl = np.zeros(n, np.int32)
+        ctx._chk(self._lib.lfdmi_radon_search_lines(ctx._h, self._r, _ptr(frames), code, n, loc, _ptr(sg), C.byref(lp), _ptr(res),
+                                                    _ptr(nl)))
+        return res, nl

@@ -221,11 +221,21 @@ class _SkyStage:
 class _RadonStage:
     """The faint-trail search behind detection for ``DetectTrails(radon=True)`` (include/lfdmi.h: faint-trail search): a
     ``Radon`` handle per (context, shape), kept while it is large enough, and the radon.txt rows.  ``sigma``: the frames' sky
-    sigma (target_sigma of the sky normalisation when that ran, else 0.025)."""
+    sigma (target_sigma of the sky normalisation when that ran, else 0.025).  ``lines`` = K: up to K lines per frame by peeling
+    (``Radon.search_lines`` with ``lines_params``); a frame's record is then (records [K], n_lines) and every found line also
+    gets a row in ``seg_out`` (radon_segments.txt)."""
 
-    def __init__(self, out, params, sigma):
+    def __init__(self, out, params, sigma, lines=None, lines_params=None, seg_out=None):
         from ..radon import as_params
         self.out, self.params, self.sigma, self._handles = out, as_params(params), float(sigma), {}
+        self.lines, self.seg_out = lines, seg_out
+        self.lines_params = dict(lines_params or {}, max_lines=lines) if lines is not None else None
+
+    def _search(self, handle, frames, **where):
+        if self.lines is None:
+            return handle.search(frames, sigma=self.sigma, **where)
+        recs, nl = handle.search_lines(frames, sigma=self.sigma, **self.lines_params, **where)
+        return [(recs[j], int(nl[j])) for j in range(len(nl))]
 
     def _handle(self, ctx, shape, n):
         key = (id(ctx), tuple(shape))
@@ -245,7 +255,7 @@ class _RadonStage:
                 m += 1
             a, b = todo[k], todo[m] + 1
             part = frames.slice(a, b) if isinstance(frames, _native.DeviceFrames) else frames[a:b]
-            recs = self._handle(ctx, shape, min(b - a, 16)).search(part, sigma=self.sigma, **where)
+            recs = self._search(self._handle(ctx, shape, min(b - a, 16)), part, **where)
             out.update(zip(range(a, b), recs))
             k = m + 1
         return out
@@ -254,14 +264,24 @@ class _RadonStage:
         """one host frame -> its record"""
         img = _np.ascontiguousarray(img, _np.float32)
         with use_context(*img.shape) as ctx:
-            return self._handle(ctx, img.shape, 1).search(img, sigma=self.sigma)[0]
+            return self._search(self._handle(ctx, img.shape, 1), img)[0]
 
     def row(self, key, rec):
-        from ..radon import format_row
-        self.out.write(format_row(key, rec) + "\n")
+        """the rows of one frame's record: the line if it was found; with ``lines``, every found line in peel order"""
+        from ..radon import format_row, format_segment_row
+        if self.lines is None:
+            if int(rec["found"]):
+                self.out.write(format_row(key, rec) + "\n")
+            return
+        recs, nl = rec
+        for k in range(nl):
+            self.out.write(format_row(key, recs[k]) + "\n")
+            self.seg_out.write(format_segment_row(key, k, recs[k]) + "\n")
 
     def flush(self):
         self.out.flush()
+        if self.seg_out is not None:
+            self.seg_out.flush()
 
     def close(self):
         for h in self._handles.values():
@@ -438,7 +458,7 @@ def _emit(c, i, key, head, shape):
     line = c.rlines[i]
     if isinstance(line, Exception):
         _log_error(c.errors, key, line, c.debug)
-    elif line is not None and int(line["found"]):
+    elif line is not None:
         c.radon.row(key, line)
     if not detection or c.profiles is None:
         return
@@ -586,7 +606,11 @@ class DetectTrails:
     is faint in every pixel but long (include/lfdmi.h: faint-trail search; ``radon_params``: dict or
     ``lfd_amd.radon.RadonParams``), with the sky sigma ``target_sigma`` under ``normalize=True`` and 0.025 otherwise.  A line
     that is found gets a row in ``radon_file`` (default ``<savepath>/radon.txt``): ``run camcol filter field x1 y1 x2 y2 snr
-    n_pix``.  results.txt does not change with it.
+    n_pix``.  results.txt does not change with it.  ``radon_lines=K`` (default None: one line per frame, as above): up to K
+    lines per frame by peeling (steps 7 - 9 of the definition; ``radon_lines_params``: dict or ``lfd_amd.radon.RadonLinesParams``
+    with ``peel_halfwidth`` and ``min_seg``).  radon.txt then gets one row per found line, in peel order, and
+    ``radon_segments_file`` (default ``<savepath>/radon_segments.txt``) one row per found line with where the trail starts and
+    stops: ``run camcol filter field line ex1 ey1 ex2 ey2 seg_snr seg_n_pix``; rank files and resume treat it like radon.txt.
     """
 
     _FILTERS = ('u', 'g', 'r', 'i', 'z')
@@ -614,6 +638,14 @@ class DetectTrails:
         self.radon_file = kwargs.get("radon_file", os.path.join(save, "radon.txt"))
         from ..radon import as_params as radon_as_params
         self.radon_params = radon_as_params(kwargs.get("radon_params"))
+        self.radon_lines = kwargs.get("radon_lines")
+        self.radon_segments_file = kwargs.get("radon_segments_file", os.path.join(save, "radon_segments.txt"))
+        self.radon_lines_params = {}
+        if self.radon_lines is not None:
+            from ..radon import RadonLinesParams, RadonParams, as_lines_params
+            lp = {k: v for k, v in as_lines_params(kwargs.get("radon_lines_params")).items() if k != "max_lines"}
+            RadonLinesParams(**dict(lp, max_lines=self.radon_lines)).validate(RadonParams(**self.radon_params).min_len)
+            self.radon_lines_params = lp
         if self.trail_profiles:
             _native.make_trail_params(**self.trail_params)      # (unknown names raise here, not per frame)
         if self.defocus:
@@ -769,7 +801,9 @@ class DetectTrails:
                 (open(self.profiles + suffix, "a") if self.trail_profiles else contextlib.nullcontext()) as profiles, \
                 (open(self.defocus_file + suffix, "a") if self.defocus else contextlib.nullcontext()) as defocus_out, \
                 (open(self.sky_file + suffix, "a") if self.normalize else contextlib.nullcontext()) as sky_out, \
-                (open(self.radon_file + suffix, "a") if self.radon else contextlib.nullcontext()) as radon_out:
+                (open(self.radon_file + suffix, "a") if self.radon else contextlib.nullcontext()) as radon_out, \
+                (open(self.radon_segments_file + suffix, "a") if self.radon and self.radon_lines is not None
+                 else contextlib.nullcontext()) as segments_out:
             if self.trail_profiles:
                 profiles = _DefocusTee(profiles, defocus_out, self.defocus_params, self.trail_params)
             prof_kw = {"profiles": profiles, "trail_params": self.trail_params} if self.trail_profiles else {}
@@ -779,7 +813,8 @@ class DetectTrails:
             radon = None
             if self.radon:
                 sigma = _native.make_sky_params(**self.sky_params).target_sigma if self.normalize else 0.025
-                radon = prof_kw["radon"] = _RadonStage(radon_out, self.radon_params, sigma)
+                radon = prof_kw["radon"] = _RadonStage(radon_out, self.radon_params, sigma, self.radon_lines, self.radon_lines_params,
+                                                       segments_out)
             if fresh:
                 progress.write(header + "\n")
                 progress.flush()

@@ -1,7 +1,8 @@
 """Faint-trail search: the line of largest signal-to-noise of a whole frame by the dyadic fast Radon transform -- for trails
 that are faint in every pixel but long, which the detector cannot see (include/lfdmi.h: faint-trail search).  ``_native.Radon``
 is the device handle; this module holds the parameters, the host conversion of a working line to the frame (usable without a
-device), a one-call helper and the radon.txt format of ``DetectTrails(radon=True)``.
+device), a one-call helper and the radon.txt format of ``DetectTrails(radon=True)``; for several lines per frame (steps 7 - 9 of
+the definition): ``RadonLinesParams``, the dyadic path, a segment's end points, ``search_lines`` and the radon_segments.txt format.
 """
 import dataclasses
 import math
@@ -11,9 +12,11 @@ import numpy as np
 from . import _native
 
 RADON_DTYPE = _native.RADON_DTYPE
+RADON_LINE_DTYPE = _native.RADON_LINE_DTYPE
 OK, NO_LINE = _native.RADON_OK, _native.RADON_NO_LINE
 DEFAULT_SIGMA = 0.025
 RADON_COLUMNS = ("run", "camcol", "filter", "field", "x1", "y1", "x2", "y2", "snr", "n_pix")
+SEGMENT_COLUMNS = ("run", "camcol", "filter", "field", "line", "ex1", "ey1", "ex2", "ey2", "seg_snr", "seg_n_pix")
 
 
 @dataclasses.dataclass
@@ -58,6 +61,49 @@ def as_params(params):
     return dict(params)
 
 
+@dataclasses.dataclass
+class RadonLinesParams:
+    """lfdmi_radon_lines_params with its defaults; ``validate`` applies the library's rules without a device (``min_len``: the
+    handle's, which bounds ``min_seg``)."""
+    max_lines: int = 4
+    peel_halfwidth: int = 8
+    min_seg: int = 64
+
+    def as_dict(self):
+        return dataclasses.asdict(self)
+
+    def validate(self, min_len=None):
+        for name in ("max_lines", "peel_halfwidth", "min_seg"):
+            if int(getattr(self, name)) != getattr(self, name):
+                raise ValueError(f"{name} must be an integer")
+        if not 1 <= self.max_lines <= _native.RADON_MAX_LINES:
+            raise ValueError("max_lines must be 1 .. %d" % _native.RADON_MAX_LINES)
+        if self.peel_halfwidth < 0:
+            raise ValueError("peel_halfwidth must be >= 0")
+        if self.min_seg < 1 or (min_len is not None and self.min_seg > min_len):
+            raise ValueError("min_seg must be 1 .. min_len")
+        return self
+
+
+def default_lines_params():
+    """lfdmi_default_radon_lines_params as a RadonLinesParams (read from the library: no GPU needed)."""
+    p = _native.make_radon_lines_params()
+    return RadonLinesParams(**{k: getattr(p, k) for k, _ in _native.RadonLinesParamsStruct._fields_})
+
+
+def as_lines_params(params, min_len=None):
+    """None / dict / RadonLinesParams -> validated dict of lfdmi_radon_lines_params fields"""
+    if params is None:
+        return {}
+    if isinstance(params, RadonLinesParams):
+        return params.validate(min_len).as_dict()
+    unknown = set(params) - {f.name for f in dataclasses.fields(RadonLinesParams)}
+    if unknown:
+        raise TypeError(f"unknown radon lines parameter {sorted(unknown)[0]!r}")
+    RadonLinesParams(**params).validate(min_len)
+    return dict(params)
+
+
 def working_dims(shape, bin):
     """(Hb, Wb, P of orientations 0 and 1, P of orientations 2 and 3)"""
     h, w = int(shape[0]), int(shape[1])
@@ -88,6 +134,55 @@ def line_of(q, y0, s, shape, bin):
     return x1, y1, x2, y2, x1 * math.cos(theta) + y1 * math.sin(theta), theta
 
 
+def dyadic_path(s, P):
+    """Step 7 of the definition: d(c; s, P) for c = 0 .. P-1, the row offset of the dyadic line of slope s in each column of a
+    working array of width P (a power of two): line (q, y0, s) is the cells Q[y0 + d[c]][c]."""
+    s, P = int(s), int(P)
+    if P < 1 or P & (P - 1) or not 0 <= s < P:
+        raise ValueError("P must be a power of two and 0 <= s < P")
+    c = np.arange(P, dtype=np.int64)
+    d = np.zeros(P, np.int64)
+    n = P >> 1
+    while n:
+        d += np.where(c & n, (s + 1) >> 1, 0)
+        n >>= 1
+        s >>= 1
+    return d
+
+
+def segment_points(q, y0, s, c1, c2, shape, bin):
+    """Step 9's end points: the working points (c1, y0 + d(c1)) and (c2, y0 + d(c2)) of line (q, y0, s) as (ex1, ey1, ex2, ey2)
+    in the detection records' coordinates."""
+    if q not in (0, 1, 2, 3):
+        raise ValueError("q must be 0 .. 3")
+    if bin not in (1, 2, 4):
+        raise ValueError("bin must be 1, 2 or 4")
+    hb, wb, p01, p23 = working_dims(shape, bin)
+    P, C = (p01, wb) if q < 2 else (p23, hb)
+    if not 0 <= c1 <= c2 < C:
+        raise ValueError("0 <= c1 <= c2 < C")
+    d = dyadic_path(s, P)
+    out = []
+    for c in (int(c1), int(c2)):
+        r = int(y0) + int(d[c])
+        i, j = ((c, r), (c, hb - 1 - r), (r, c), (wb - 1 - r, c))[q]
+        out += [bin * i + (bin - 1) / 2.0, bin * j + (bin - 1) / 2.0]
+    return tuple(out)
+
+
+def search_lines(ctx, frames, sigma=None, **params):
+    """Search (n, h, w) or (h, w) frames on ``ctx`` for several lines each: (RADON_LINE_DTYPE records [n, max_lines], n_lines
+    [n]).  ``params``: fields of RadonParams and of RadonLinesParams.  The handle is created and destroyed per call."""
+    lnames = {f.name for f in dataclasses.fields(RadonLinesParams)}
+    lp = as_lines_params({k: v for k, v in params.items() if k in lnames})
+    rp = as_params({k: v for k, v in params.items() if k not in lnames})
+    arr = frames if _native._is_dev(frames) or isinstance(frames, _native.DeviceFrames) else np.asarray(frames)
+    shp = tuple(arr.shape)
+    n, h, w = (1, *shp) if len(shp) == 2 else shp
+    with _native.Radon(ctx, (h, w), max_frames=max(1, min(n, ctx.max_inflight)), **rp) as r:
+        return r.search_lines(arr, sigma=sigma, **lp)
+
+
 def search_frames(ctx, frames, sigma=None, **params):
     """Search (n, h, w) or (h, w) frames on ``ctx``: RADON_DTYPE records, one per frame.  For repeated calls keep a
     ``_native.Radon`` handle instead: this one is created and destroyed per call."""
@@ -115,5 +210,27 @@ def read_radon(path):
             r = {}
             for k, v in zip(RADON_COLUMNS, parts):
                 r[k] = v if k == "filter" else int(v) if k in ("run", "camcol", "field", "n_pix") else float(v)
+            rows.append(r)
+    return rows
+
+
+def format_segment_row(meta, line, rec):
+    """One radon_segments.txt row: meta = (run, camcol, filter, field), line = the record's place in peel order; floats with
+    repr."""
+    return " ".join(str(v) for v in (*meta, int(line), repr(float(rec["ex1"])), repr(float(rec["ey1"])), repr(float(rec["ex2"])),
+                                      repr(float(rec["ey2"])), repr(float(rec["seg_snr"])), int(rec["seg_n_pix"])))
+
+
+def read_segments(path):
+    """radon_segments.txt (rows only, no header line) -> list of dicts keyed by SEGMENT_COLUMNS."""
+    rows = []
+    with open(path) as f:
+        for ln in f:
+            parts = ln.split()
+            if not parts:
+                continue
+            r = {}
+            for k, v in zip(SEGMENT_COLUMNS, parts):
+                r[k] = v if k == "filter" else int(v) if k in ("run", "camcol", "field", "line", "seg_n_pix") else float(v)
             rows.append(r)
     return rows

@@ -3,7 +3,11 @@ between HIP events, beside the bytes each kernel has to move (the rows a level s
 16-bit counts) and the floor those bytes give at the copy rate the project quotes (4.8 TB/s, DESIGN.md: sky normalisation).
 Writes profiles/radon_probe.json.
 
-    python tools/radon_probe.py [--reps 5] [--frames 256] [--max-frames 16] [--out FILE] [--trace]
+    python tools/radon_probe.py [--reps 5] [--frames 256] [--max-frames 16] [--out FILE] [--trace] [--lines K]
+
+--lines K  also times lfdmi_radon_search_lines(max_lines=K) on the same frames with one faint streak added to every second
+           frame: ms per call and per round (a frame runs one round more than it has found lines, K at the most), beside the
+           plain search's time
 
 --trace  one more run per bin under `rocprofv3 --kernel-trace --stats` -> profiles/radon_probe_kernel_stats_bin<b>.csv
 Every GPU step is a child process under its own `timeout`.
@@ -47,6 +51,8 @@ def child(a):
     h, w = SHAPE
     g = torch.Generator(device="cuda").manual_seed(1)
     frames = torch.randn((a.frames, h, w), generator=g, device="cuda", dtype=torch.float32) * 0.025
+    if a.lines:
+        frames[::2, h // 3, :] += 0.02                       # a faint row: every second frame peels at least once
     for b in ((a.bin,) if a.bin else (1, 2, 4)):
         with _native.Context(0, h, w, 2) as ctx, _native.Radon(ctx, SHAPE, max_frames=a.max_frames, bin=b) as r:
             rec = r.search(frames)                                  # warm-up: module load, first touch
@@ -58,6 +64,22 @@ def child(a):
                 e1.record()
                 e1.synchronize()
                 ms.append(e0.elapsed_time(e1))
+            lines = {}
+            if a.lines:
+                recs, nl = r.search_lines(frames, max_lines=a.lines)      # warm-up: the second V, M set
+                lms = []
+                for _ in range(a.reps):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    recs, nl = r.search_lines(frames, max_lines=a.lines)
+                    e1.record()
+                    e1.synchronize()
+                    lms.append(e0.elapsed_time(e1))
+                rounds = int(np.minimum(nl + 1, a.lines).sum())           # frame-rounds the call ran
+                lmed = float(np.median(lms))
+                lines = {"lines_max": a.lines, "lines_ms_per_call": lmed, "lines_ms_all": lms, "lines_found": int(nl.sum()),
+                         "lines_frame_rounds": rounds, "lines_ms_per_frame_round": lmed / rounds,
+                         "plain_ms_per_call": float(np.median(ms)), "bytes_with_lines": r.dims()[2]}
             kb = kernel_bytes(SHAPE, b)
             total = float(sum(kb.values())) * a.frames
             med = float(np.median(ms))
@@ -66,7 +88,7 @@ def child(a):
                 "device_bytes_per_inflight_frame": r.bytes // a.max_frames, "ms_per_call": med, "ms_all": ms,
                 "ms_per_frame": med / a.frames, "bytes_per_frame_by_kernel": kb, "bytes_per_call": total,
                 "ms_floor_at_4.8_TBps": total / COPY_RATE * 1e3, "x_the_floor": med / (total / COPY_RATE * 1e3),
-                "snr_max": float(rec["snr"].max()), "found": int(rec["found"].sum())}), flush=True)
+                "snr_max": float(rec["snr"].max()), "found": int(rec["found"].sum()), **lines}), flush=True)
 
 
 def run_child(extra, timeout_s, prefix=()):
@@ -84,17 +106,19 @@ def main():
     ap.add_argument("--frames", type=int, default=256)
     ap.add_argument("--max-frames", type=int, default=16)
     ap.add_argument("--bin", type=int, default=0)
+    ap.add_argument("--lines", type=int, default=0)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "radon_probe.json"))
     ap.add_argument("--child", action="store_true")
     a = ap.parse_args()
     if a.child:
         child(a)
         return
-    common = ["--frames", str(a.frames), "--max-frames", str(a.max_frames)]
+    common = ["--frames", str(a.frames), "--max-frames", str(a.max_frames), "--lines", str(a.lines)]
     doc = {"tool": "tools/radon_probe.py", "copy_rate_TBps": COPY_RATE / 1e12,
            "runs": run_child(common + ["--reps", str(a.reps)], 500)}
     for r in doc["runs"]:
-        print({k: r[k] for k in ("bin", "ms_per_call", "ms_floor_at_4.8_TBps", "x_the_floor")}, flush=True)
+        print({k: r[k] for k in ("bin", "ms_per_call", "ms_floor_at_4.8_TBps", "x_the_floor", "lines_ms_per_call",
+                                 "lines_ms_per_frame_round", "lines_found") if k in r}, flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(doc, f, indent=1)
