@@ -827,6 +827,101 @@ void lfdmi_default_radon_lines_params(lfdmi_radon_lines_params *out);
 int lfdmi_radon_search_lines(lfdmi_ctx *ctx, lfdmi_radon *radon, const void *frames, int dtype, int n, int loc, const float *sigma,
                              const lfdmi_radon_lines_params *lp, lfdmi_radon_line *lines, int32_t *n_lines);
 
+/* ---- stacked cross-sections -------------------------------------------------------------------------------------------------
+ * lfdmi_measure_trails needs every 64-position piece of a trail to stand 5 sigma on its own; a trail of the faint-trail search
+ * never does.  lfdmi_stack_profiles measures such a trail's cross-section by the Radon idea turned by 90 degrees: the frame is
+ * summed ALONG a given segment, separately for every perpendicular offset, so the per-pixel noise averages down by the square
+ * root of the length in every bin.  It is a measurement for trails below `clip` per pixel (brighter pixels are not summed).
+ * The reference has no such step.  The procedure below is the definition; tests/stack_ref.py restates it in numpy and the
+ * device matches it bit for bit.  Notation: P = prof_half, K = P / step (an integer), nb = 2K+1 bins.
+ *
+ * 1. Pixels.  Coordinates are the detection records': x = column, y = row of the flipped frame, so (x, y) is buffer row H-1-y.
+ *    A pixel is valid when it is finite, not +-0 and |v| <= clip (float32; clip = +inf: no clipping): step 1 of the faint-trail
+ *    search.
+ * 2. Geometry, on the host in double, each operation rounded, no contraction.  A segment whose end points are not finite,
+ *    exceed 1e6 in magnitude or coincide: LFDMI_STACK_BAD_SEGMENT.  The major axis is x when |x2-x1| >= |y2-y1|, else y; a is
+ *    the coordinate along it, b the other one, A and B the frame's sizes along them; (a1, b1), (a2, b2) the end points as given.
+ *    g = (b2-b1) / (a2-a1), cosphi = 1 / sqrt(1 + g*g), inv = 1 / step.  The columns are the integers a in [a_first, a_last],
+ *    a_first = max(ceil(min(a1, a2)), 0), a_last = min(floor(max(a1, a2)), A-1); n_col of them; n_col < min_cols:
+ *    LFDMI_STACK_TOO_SHORT.  The centre of column a is bc(a) = b1 + g*((double)a - a1).
+ * 3. Bins.  u_k = (k - K) * step, k = 0 .. 2K.  A valid pixel (a, b), 0 <= b < B, falls in bin k = floor(t),
+ *    t = ((double)b - bc(a)) * cosphi * inv + (K + 0.5) (left to right), when 0 <= t < 2K+1; otherwise in none.
+ * 4. Sums.  The columns split into a left half [a_first, amid-1] and a right half [amid, a_last], amid = (a_first + a_last + 1)
+ *    >> 1.  Within a half the columns group into blocks by a >> 5.  Per (half, block, bin): one sequential float32 accumulator
+ *    from +0 over the bin's valid pixels, columns ascending, b ascending within a column.  Per (half, bin): the block sums are
+ *    added in ascending block order into one sequential float32 accumulator from +0.  Counts are exact int32.  A pass yields
+ *    A_L, A_R, N_L, N_R, each [2K+1].
+ * 5. Refinement, on the host in double; passes i = 0 .. n_iter, the last one only measures.  In pass i < n_iter, per half:
+ *    m_k = (double)A_k / (double)N_k where N_k > 0; bkg = the lower median (rank floor((m-1)/2), as in lfdmi_measure_trails) of
+ *    m_k over the wing bins |u_k| >= P - wing with N_k > 0.  With hb = floor(box / (2 step)) the box score of bin k is
+ *    (SA - bkg * SN) / sqrt(SN), SA / SN = the sums of (double)A_j / (double)N_j over j = max(k-hb, 0) .. min(k+hb, 2K)
+ *    ascending; the half's centre is the bin k of largest score among those with |u_k| <= max_shift and SN > 0, ties to the
+ *    lowest k; its shift is u_k.  Refinement stops -- this pass's sums are the result, the line stays -- when a half has no
+ *    wing bin or no scored bin, when either score is below k_ref * (double)sigma, or when the new line has |g| > 2.  Otherwise,
+ *    with the halves' middle columns aL = (a_first + (amid-1)) * 0.5, aR = (amid + a_last) * 0.5 and bL = bc(aL) + uL / cosphi,
+ *    bR = bc(aR) + uR / cosphi: a1 = aL, b1 = bL, g = (bR - bL) / (aR - aL), cosphi from g as in step 2.  The major axis and
+ *    the column range are kept.
+ * 6. Result, from the last pass run.  A_k = A_L + A_R (one float32 addition), N_k = N_L + N_R, m_k = A_k / (float)N_k
+ *    (float32), NaN when N_k = 0.  background (lower median of the non-NaN m_k over the wing bins), v_k = m_k - background
+ *    (float32; the profile row), peak, noise (1.4826 * lower median of |v_k| over the same wing bins), fwhm (the calc_fwhm
+ *    rule), fwhm_arcsec and depth exactly as step 5 of the trail profiles defines them.  status LFDMI_STACK_TOO_FAINT unless
+ *    peak > 0 and peak >= k_sig * noise; such a record keeps every measured value (it is a verdict, not a failure).  flux =
+ *    step * the sum of (double)v_k over the core bins |u_k| < P - wing, k ascending (the trail's flux per pixel of length);
+ *    flux_err = step * noise * sqrt(number of core bins); snr = flux / flux_err.  (x1, y1), (x2, y2): the final line's points
+ *    at a_first and a_last; d = their difference over its length (sqrt of the sum of squares), n = (d.y, -d.x) turned so that
+ *    n.y > 0 or (n.y == 0 and n.x > 0), theta = atan2(n.y, n.x), rho = x1 n.x + y1 n.y.  With am = (a_first + a_last) * 0.5
+ *    and index 0 the line as given: shift = (bc(am) - bc_0(am)) * cosphi_0 px, tilt = atan(g) - atan(g_0) rad.  min_valid = the
+ *    least N_k.  Records with LFDMI_STACK_BAD_SEGMENT or _TOO_SHORT have every double NaN, a NaN row, zero sums and counts.
+ *
+ * The device sums 32 columns by the band's cross extent per workgroup through LDS (k_stack_block), a pixel reaching exactly one
+ * bin: no float atomics, and step 4's order is kept; k_stack_combine adds the block sums. */
+#define LFDMI_STACK_MAX_HALF 40.0   /* prof_half + step / 2 at most (the band of 32 columns is kept in LDS) */
+enum { LFDMI_STACK_OK = 0, LFDMI_STACK_BAD_SEGMENT = 1, LFDMI_STACK_TOO_SHORT = 2, LFDMI_STACK_TOO_FAINT = 3 };
+typedef struct {
+    int32_t frame;            /* 0 .. n-1 */
+    int32_t pad;
+    double x1, y1, x2, y2;    /* flipped frame, as lfdmi_radon_line.ex1 .. ey2, a results row or an injected trail's truth */
+} lfdmi_stack_segment;
+typedef struct {
+    int32_t wing;             /* wing width in px for background and noise (1 .. < prof_half); default 8 */
+    int32_t n_iter;           /* refinement passes (0 .. 16); default 2 */
+    int32_t min_cols;         /* columns a segment needs (>= 2); default 64 */
+    float clip;               /* pixels above it in magnitude are not summed (> 0, +inf allowed); default 0.125 */
+    double prof_half;         /* P: profile half-width in px; default 24 */
+    double step;              /* bin step in px (> 0; P / step an integer, 1 .. 512; P + step / 2 <= LFDMI_STACK_MAX_HALF); default 0.5 */
+    double box;               /* window of the refinement's box score in px (>= 0); default 4 */
+    double max_shift;         /* the refinement looks within |u| <= max_shift px (>= 0); default 8 */
+    double k_sig;             /* TOO_FAINT below peak = k_sig * noise; default 6.  The restatement on 372 x 512 frames of sigma 0.025,
+                                 start line off by 1.5 px and 0.15 degrees: 16 noise-only frames peak / noise 1.7 - 3.7, 16 trails of
+                                 peak 0.02 (Gaussian sigma 2 px) 9.2 - 18.4 */
+    double k_ref;             /* a half moves the line when its box score reaches k_ref * sigma; default 4.  The same frames: the
+                                 smaller half score over sigma 0.1 - 2.0 (noise), 17.2 - 23.4 (trails) */
+    double pixscale;          /* arcsec per px; default 0.396 (SDSS) */
+} lfdmi_stack_params;
+typedef struct {
+    int32_t status;           /* LFDMI_STACK_* */
+    int32_t n_col;            /* columns summed */
+    int32_t min_valid;        /* fewest pixels in any bin */
+    int32_t n_pass;           /* passes run (1 .. n_iter + 1) */
+    double rho, theta;        /* the refined line */
+    double x1, y1, x2, y2;    /* its points at the first and last column */
+    double background, noise, peak;
+    double fwhm, fwhm_arcsec, depth;
+    double flux, flux_err, snr;
+    double shift, tilt;       /* how far the refinement moved the line: px at the middle column, rad */
+} lfdmi_stack;
+void lfdmi_default_stack_params(lfdmi_stack_params *out);
+/* frames: n frames of h x w, LFDMI_F32 or LFDMI_F32_BE, loc LFDMI_HOST / LFDMI_HOST_PINNED / LFDMI_DEVICE; only read.  segs: n_seg
+ * segments (host), any number per frame.  sigma: n float32 (host), the sky sigma of each frame, > 0; NULL: 0.025.  p NULL: the
+ * defaults.  out: n_seg records (host).  profiles: n_seg x (2K+1) float32, the rows v_k; sums / counts: n_seg x 2 x (2K+1)
+ * float32 / int32, A_L, A_R / N_L, N_R of the last pass (host; each may be NULL).  Out-of-range parameters, a segment's frame
+ * outside [0, n), a sigma that is not positive: LFDMI_ERR_ARG, and nothing runs.  The call keeps no state (its device memory
+ * comes from the stream's pool and goes back before it returns), refuses while calls are in flight, runs on the context's
+ * stream and waits for it once per pass (the host refines the lines in between). */
+int lfdmi_stack_profiles(lfdmi_ctx *ctx, const void *frames, int dtype, int n, int h, int w, int loc, const lfdmi_stack_segment *segs,
+                         int n_seg, const float *sigma, const lfdmi_stack_params *p, lfdmi_stack *out, float *profiles, float *sums,
+                         int32_t *counts);
+
 #ifdef __cplusplus
 }
 #endif

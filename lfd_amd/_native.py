@@ -42,6 +42,7 @@ SYMBOLS = (
     "lfdmi_inject_trails",
     "lfdmi_default_radon_params", "lfdmi_radon_create", "lfdmi_radon_destroy", "lfdmi_radon_dims", "lfdmi_radon_search",
     "lfdmi_default_radon_lines_params", "lfdmi_radon_search_lines",
+    "lfdmi_default_stack_params", "lfdmi_stack_profiles",
 )
 
 
@@ -230,6 +231,42 @@ def make_radon_lines_params(**params):
     return p
 
 
+class StackParamsStruct(C.Structure):
+    """lfdmi_stack_params (include/lfdmi.h: stacked cross-sections)."""
+    _fields_ = [("wing", C.c_int32), ("n_iter", C.c_int32), ("min_cols", C.c_int32), ("clip", C.c_float),
+                ("prof_half", C.c_double), ("step", C.c_double), ("box", C.c_double), ("max_shift", C.c_double),
+                ("k_sig", C.c_double), ("k_ref", C.c_double), ("pixscale", C.c_double)]
+
+
+# lfdmi_stack_segment: one record per segment of lfdmi_stack_profiles
+STACK_SEGMENT_DTYPE = np.dtype([("frame", "<i4"), ("pad", "<i4"), ("x1", "<f8"), ("y1", "<f8"), ("x2", "<f8"), ("y2", "<f8")])
+# lfdmi_stack: its result
+STACK_DTYPE = np.dtype([("status", "<i4"), ("n_col", "<i4"), ("min_valid", "<i4"), ("n_pass", "<i4"),
+                        ("rho", "<f8"), ("theta", "<f8"), ("x1", "<f8"), ("y1", "<f8"), ("x2", "<f8"), ("y2", "<f8"),
+                        ("background", "<f8"), ("noise", "<f8"), ("peak", "<f8"),
+                        ("fwhm", "<f8"), ("fwhm_arcsec", "<f8"), ("depth", "<f8"),
+                        ("flux", "<f8"), ("flux_err", "<f8"), ("snr", "<f8"), ("shift", "<f8"), ("tilt", "<f8")])
+STACK_OK, STACK_BAD_SEGMENT, STACK_TOO_SHORT, STACK_TOO_FAINT = 0, 1, 2, 3
+STACK_MAX_HALF = 40.0
+
+
+def make_stack_params(**params):
+    """lfdmi_default_stack_params with the given fields replaced (unknown names raise)."""
+    p = StackParamsStruct()
+    lib().lfdmi_default_stack_params(C.byref(p))
+    names = {k for k, _ in StackParamsStruct._fields_}
+    for k, v in params.items():
+        if k not in names:
+            raise TypeError(f"unknown stack parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def stack_bins(p):
+    """2K+1 profile bins of a StackParamsStruct"""
+    return 2 * int(round(p.prof_half / p.step)) + 1
+
+
 def make_radon_params(**params):
     """lfdmi_default_radon_params with the given fields replaced (unknown names raise)."""
     p = RadonParamsStruct()
@@ -310,6 +347,10 @@ def lib():
         _lib.lfdmi_default_radon_lines_params.argtypes = [C.c_void_p]
         _lib.lfdmi_radon_search_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p]
+        _lib.lfdmi_default_stack_params.restype = None
+        _lib.lfdmi_default_stack_params.argtypes = [C.c_void_p]
+        _lib.lfdmi_stack_profiles.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     return _lib
 
 
@@ -1007,6 +1048,28 @@ class Context:
         self._chk(self._lib.lfdmi_inject_trails(self._h, _ptr(fr), code, n, h, w, loc, _ptr(tr), len(tr), _ptr(tab), tab.shape[0],
                                                 tab.shape[1], C.c_double(float(table_step)), int(subsample)))
         return frames
+
+    # -- stacked cross-sections (lfdmi_stack_profiles) ----------------------------------------------------------------------------
+    def stack_profiles(self, frames, segments, sigma=None, pinned=False, native_device=False, raw=False, **params):
+        """The stacked cross-section of every segment (include/lfdmi.h: stacked cross-sections).  frames: what ``Radon.search``
+        takes ('<f4' or '>f4' numpy, torch CUDA float32, ``DeviceFrames``), only read; segments: STACK_SEGMENT_DTYPE records (or
+        anything ``np.asarray`` turns into them), coordinates of the flipped frame; sigma: None (0.025), a number or n values.
+        Returns (STACK_DTYPE records [n_seg], float32 rows [n_seg, 2K+1]); with raw=True also the last pass's sums (float32
+        [n_seg, 2, 2K+1]: left and right half) and counts (int32, the same shape)."""
+        frames, code, n, h, w, loc = self._frames(frames, pinned, "stack_profiles", native_device=native_device)
+        sg = np.ascontiguousarray(segments, STACK_SEGMENT_DTYPE).reshape(-1)
+        p = make_stack_params(**params)
+        sig = None
+        if sigma is not None:
+            sig = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, np.float32), (n,)))
+        nb = max(1, stack_bins(p)) if p.step > 0 and np.isfinite(p.prof_half / p.step) and p.prof_half / p.step < 1e6 else 1
+        out = np.zeros(len(sg), STACK_DTYPE)
+        prof = np.empty((len(sg), nb), np.float32)
+        sums = np.zeros((len(sg), 2, nb), np.float32) if raw else None
+        cnts = np.zeros((len(sg), 2, nb), np.int32) if raw else None
+        self._chk(self._lib.lfdmi_stack_profiles(self._h, _ptr(frames), code, n, h, w, loc, _ptr(sg), len(sg), _ptr(sig), C.byref(p),
+                                                 _ptr(out), _ptr(prof), _ptr(sums), _ptr(cnts)))
+        return (out, prof, sums, cnts) if raw else (out, prof)
 
     def pinned_buffer(self, nbytes):
         """Page-locked host memory next to this context's GPU (lfdmi_host_alloc) as a ``PinnedBuffer``."""

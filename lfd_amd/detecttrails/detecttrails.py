@@ -223,19 +223,34 @@ class _RadonStage:
     ``Radon`` handle per (context, shape), kept while it is large enough, and the radon.txt rows.  ``sigma``: the frames' sky
     sigma (target_sigma of the sky normalisation when that ran, else 0.025).  ``lines`` = K: up to K lines per frame by peeling
     (``Radon.search_lines`` with ``lines_params``); a frame's record is then (records [K], n_lines) and every found line also
-    gets a row in ``seg_out`` (radon_segments.txt)."""
+    gets a row in ``seg_out`` (radon_segments.txt).  ``prof_out`` (radon_profiles.txt; needs ``lines``): every found line's
+    segment is measured where the search left the frames (include/lfdmi.h: stacked cross-sections; ``stack_params``) and a frame's
+    record is (records [K], n_lines, [(stack record, row)] per found line); with ``defocus_out`` (radon_defocus.txt) the rows
+    added since the last ``flush`` are fitted in one call, as ``_DefocusTee`` does for profiles.txt."""
 
-    def __init__(self, out, params, sigma, lines=None, lines_params=None, seg_out=None):
+    def __init__(self, out, params, sigma, lines=None, lines_params=None, seg_out=None, prof_out=None, stack_params=None,
+                 defocus_out=None, defocus_params=None):
         from ..radon import as_params
         self.out, self.params, self.sigma, self._handles = out, as_params(params), float(sigma), {}
         self.lines, self.seg_out = lines, seg_out
         self.lines_params = dict(lines_params or {}, max_lines=lines) if lines is not None else None
+        self.prof_out, self.stack_params = prof_out, dict(stack_params or {})
+        self.defocus_out, self.defocus_params, self.pending = defocus_out, defocus_params, []
 
     def _search(self, handle, frames, **where):
         if self.lines is None:
             return handle.search(frames, sigma=self.sigma, **where)
         recs, nl = handle.search_lines(frames, sigma=self.sigma, **self.lines_params, **where)
-        return [(recs[j], int(nl[j])) for j in range(len(nl))]
+        if self.prof_out is None:
+            return [(recs[j], int(nl[j])) for j in range(len(nl))]
+        from ..stack import segments_from_radon_lines
+        segs, where_ = segments_from_radon_lines(recs, nl)
+        meas = [[] for _ in range(len(nl))]
+        if len(segs):
+            srec, rows = handle.ctx.stack_profiles(frames, segs, sigma=self.sigma, **where, **self.stack_params)
+            for (j, _), r, row in zip(where_, srec, rows):
+                meas[j].append((r, row))
+        return [(recs[j], int(nl[j]), meas[j]) for j in range(len(nl))]
 
     def _handle(self, ctx, shape, n):
         key = (id(ctx), tuple(shape))
@@ -273,15 +288,35 @@ class _RadonStage:
             if int(rec["found"]):
                 self.out.write(format_row(key, rec) + "\n")
             return
-        recs, nl = rec
+        recs, nl = rec[:2]
         for k in range(nl):
             self.out.write(format_row(key, recs[k]) + "\n")
             self.seg_out.write(format_segment_row(key, k, recs[k]) + "\n")
+        if self.prof_out is not None:
+            from ..stack import format_row as format_profile_row
+            for k, (srec, prow) in enumerate(rec[2]):
+                self.prof_out.write(format_profile_row(key, k, srec) + "\n")
+                if self.defocus_out is not None:
+                    self.pending.append(((*key, k), srec, prow))
 
     def flush(self):
         self.out.flush()
         if self.seg_out is not None:
             self.seg_out.flush()
+        if self.prof_out is not None:
+            self.prof_out.flush()
+        if self.defocus_out is not None:
+            if self.pending:
+                from .. import defocus
+                from ..stack import to_trails
+                tp = {"prof_half": self.stack_params.get("prof_half", 24.0), "prof_step": self.stack_params.get("step", 0.5),
+                      "wing": self.stack_params.get("wing", 8), "pixscale": self.stack_params.get("pixscale", 0.396)}
+                ctx, bank = defocus_bank(self.defocus_params, tp)
+                trails = to_trails(_np.array([r for _, r, _ in self.pending], _native.STACK_DTYPE))
+                fit = ctx.fit_defocus(bank, trails, _np.stack([p for _, _, p in self.pending]))
+                self.defocus_out.write("".join(defocus.format_row(k, f) + "\n" for (k, _, _), f in zip(self.pending, fit)))
+                self.pending = []
+            self.defocus_out.flush()
 
     def close(self):
         for h in self._handles.values():
@@ -611,6 +646,13 @@ class DetectTrails:
     with ``peel_halfwidth`` and ``min_seg``).  radon.txt then gets one row per found line, in peel order, and
     ``radon_segments_file`` (default ``<savepath>/radon_segments.txt``) one row per found line with where the trail starts and
     stops: ``run camcol filter field line ex1 ey1 ex2 ey2 seg_snr seg_n_pix``; rank files and resume treat it like radon.txt.
+    ``radon_profiles=True`` (needs ``radon_lines``): every found line's segment is measured by the stacked cross-sections
+    (include/lfdmi.h: stacked cross-sections; ``stack_params``: dict or ``lfd_amd.stack.StackParams``) on the frames where the
+    search left them, and ``radon_profiles_file`` (default ``<savepath>/radon_profiles.txt``) gets one row per found line: ``run
+    camcol filter field line status x1 y1 x2 y2 n_col background noise peak fwhm fwhm_arcsec depth flux flux_err snr``.  With
+    ``defocus=True`` the rows are fitted too (a bank built for the stack's prof_half / step / wing) and written to
+    ``radon_defocus_file`` (default ``<savepath>/radon_defocus.txt``): defocus.txt's columns with the line's index after the
+    field.  Rank files and resume treat both like radon_segments.txt; every other output stays byte for byte what it is.
     """
 
     _FILTERS = ('u', 'g', 'r', 'i', 'z')
@@ -646,6 +688,15 @@ class DetectTrails:
             lp = {k: v for k, v in as_lines_params(kwargs.get("radon_lines_params")).items() if k != "max_lines"}
             RadonLinesParams(**dict(lp, max_lines=self.radon_lines)).validate(RadonParams(**self.radon_params).min_len)
             self.radon_lines_params = lp
+        self.radon_profiles = bool(kwargs.get("radon_profiles", False))
+        self.radon_profiles_file = kwargs.get("radon_profiles_file", os.path.join(save, "radon_profiles.txt"))
+        self.radon_defocus_file = kwargs.get("radon_defocus_file", os.path.join(save, "radon_defocus.txt"))
+        self.stack_params = {}
+        if self.radon_profiles:
+            if not self.radon or self.radon_lines is None:
+                raise ValueError("radon_profiles=True needs radon=True and radon_lines=K: the segments it measures are theirs")
+            from ..stack import as_params as stack_as_params
+            self.stack_params = stack_as_params(kwargs.get("stack_params"))
         if self.trail_profiles:
             _native.make_trail_params(**self.trail_params)      # (unknown names raise here, not per frame)
         if self.defocus:
@@ -803,7 +854,10 @@ class DetectTrails:
                 (open(self.sky_file + suffix, "a") if self.normalize else contextlib.nullcontext()) as sky_out, \
                 (open(self.radon_file + suffix, "a") if self.radon else contextlib.nullcontext()) as radon_out, \
                 (open(self.radon_segments_file + suffix, "a") if self.radon and self.radon_lines is not None
-                 else contextlib.nullcontext()) as segments_out:
+                 else contextlib.nullcontext()) as segments_out, \
+                (open(self.radon_profiles_file + suffix, "a") if self.radon_profiles else contextlib.nullcontext()) as rprof_out, \
+                (open(self.radon_defocus_file + suffix, "a") if self.radon_profiles and self.defocus
+                 else contextlib.nullcontext()) as rdef_out:
             if self.trail_profiles:
                 profiles = _DefocusTee(profiles, defocus_out, self.defocus_params, self.trail_params)
             prof_kw = {"profiles": profiles, "trail_params": self.trail_params} if self.trail_profiles else {}
@@ -814,7 +868,7 @@ class DetectTrails:
             if self.radon:
                 sigma = _native.make_sky_params(**self.sky_params).target_sigma if self.normalize else 0.025
                 radon = prof_kw["radon"] = _RadonStage(radon_out, self.radon_params, sigma, self.radon_lines, self.radon_lines_params,
-                                                       segments_out)
+                                                       segments_out, rprof_out, self.stack_params, rdef_out, self.defocus_params)
             if fresh:
                 progress.write(header + "\n")
                 progress.flush()
