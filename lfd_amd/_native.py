@@ -109,16 +109,22 @@ TRAIL_DTYPE = np.dtype([("status", "<i4"), ("n_pos", "<i4"), ("n_seg", "<i4"), (
 TRAIL_OK, TRAIL_NOT_FOUND, TRAIL_TOO_SHORT, TRAIL_TOO_FAINT = 0, 1, 2, 3
 
 
-def make_trail_params(**params):
-    """lfdmi_default_trail_params with the given fields replaced (unknown names raise)."""
-    p = TrailParams()
-    lib().lfdmi_default_trail_params(C.byref(p))
-    names = {k for k, _ in TrailParams._fields_}
+def _make_params(struct, defaults, what, params, convert=None):
+    """``struct`` filled by the library's ``defaults`` function, with the given fields replaced (unknown names raise);
+    convert: (name, value) -> value, applied to every override."""
+    p = struct()
+    getattr(lib(), defaults)(C.byref(p))
+    names = {k for k, _ in struct._fields_}
     for k, v in params.items():
         if k not in names:
-            raise TypeError(f"unknown trail parameter {k!r}")
-        setattr(p, k, v)
+            raise TypeError(f"unknown {what} parameter {k!r}")
+        setattr(p, k, convert(k, v) if convert else v)
     return p
+
+
+def make_trail_params(**params):
+    """lfdmi_default_trail_params with the given fields replaced (unknown names raise)."""
+    return _make_params(TrailParams, "lfdmi_default_trail_params", "trail", params)
 
 
 def trail_bins(p):
@@ -163,18 +169,15 @@ SKY_SUBTRACT, SKY_NORMALISE = 0, 1
 SKY_OK, SKY_NO_SKY, SKY_NO_NOISE = 0, 1, 2
 
 
+def _sky_mode(k, v):
+    if k == "mode" and isinstance(v, str):
+        return {"subtract": SKY_SUBTRACT, "normalise": SKY_NORMALISE, "normalize": SKY_NORMALISE}[v.lower()]
+    return v
+
+
 def make_sky_params(**params):
     """lfdmi_default_sky_params with the given fields replaced (unknown names raise; mode also as "subtract" / "normalise")."""
-    p = SkyParamsStruct()
-    lib().lfdmi_default_sky_params(C.byref(p))
-    names = {k for k, _ in SkyParamsStruct._fields_}
-    for k, v in params.items():
-        if k not in names:
-            raise TypeError(f"unknown sky parameter {k!r}")
-        if k == "mode" and isinstance(v, str):
-            v = {"subtract": SKY_SUBTRACT, "normalise": SKY_NORMALISE, "normalize": SKY_NORMALISE}[v.lower()]
-        setattr(p, k, v)
-    return p
+    return _make_params(SkyParamsStruct, "lfdmi_default_sky_params", "sky", params, _sky_mode)
 
 
 # lfdmi_inject_trail: one record per trail of lfdmi_inject_trails (include/lfdmi.h: trail injection)
@@ -221,14 +224,7 @@ RADON_MAX_LINES = 8
 
 def make_radon_lines_params(**params):
     """lfdmi_default_radon_lines_params with the given fields replaced (unknown names raise)."""
-    p = RadonLinesParamsStruct()
-    lib().lfdmi_default_radon_lines_params(C.byref(p))
-    names = {k for k, _ in RadonLinesParamsStruct._fields_}
-    for k, v in params.items():
-        if k not in names:
-            raise TypeError(f"unknown radon lines parameter {k!r}")
-        setattr(p, k, v)
-    return p
+    return _make_params(RadonLinesParamsStruct, "lfdmi_default_radon_lines_params", "radon lines", params)
 
 
 class StackParamsStruct(C.Structure):
@@ -252,14 +248,7 @@ STACK_MAX_HALF = 40.0
 
 def make_stack_params(**params):
     """lfdmi_default_stack_params with the given fields replaced (unknown names raise)."""
-    p = StackParamsStruct()
-    lib().lfdmi_default_stack_params(C.byref(p))
-    names = {k for k, _ in StackParamsStruct._fields_}
-    for k, v in params.items():
-        if k not in names:
-            raise TypeError(f"unknown stack parameter {k!r}")
-        setattr(p, k, v)
-    return p
+    return _make_params(StackParamsStruct, "lfdmi_default_stack_params", "stack", params)
 
 
 def stack_bins(p):
@@ -269,14 +258,7 @@ def stack_bins(p):
 
 def make_radon_params(**params):
     """lfdmi_default_radon_params with the given fields replaced (unknown names raise)."""
-    p = RadonParamsStruct()
-    lib().lfdmi_default_radon_params(C.byref(p))
-    names = {k for k, _ in RadonParamsStruct._fields_}
-    for k, v in params.items():
-        if k not in names:
-            raise TypeError(f"unknown radon parameter {k!r}")
-        setattr(p, k, v)
-    return p
+    return _make_params(RadonParamsStruct, "lfdmi_default_radon_params", "radon", params)
 
 
 _lib = None
@@ -372,6 +354,13 @@ def _dtype_code(a):
         return {"uint8": U8, "float32": F32, "float64": F64}[name]
     except KeyError:
         raise TypeError(f"unsupported image dtype {a.dtype}") from None
+
+
+def _sigma(sigma, n):
+    """None, a number or n values -> None or n float32 values"""
+    if sigma is None:
+        return None
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, np.float32), (n,)))
 
 
 def make_params(d, dim=False):
@@ -1059,9 +1048,7 @@ class Context:
         frames, code, n, h, w, loc = self._frames(frames, pinned, "stack_profiles", native_device=native_device)
         sg = np.ascontiguousarray(segments, STACK_SEGMENT_DTYPE).reshape(-1)
         p = make_stack_params(**params)
-        sig = None
-        if sigma is not None:
-            sig = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, np.float32), (n,)))
+        sig = _sigma(sigma, n)
         nb = max(1, stack_bins(p)) if p.step > 0 and np.isfinite(p.prof_half / p.step) and p.prof_half / p.step < 1e6 else 1
         out = np.zeros(len(sg), STACK_DTYPE)
         prof = np.empty((len(sg), nb), np.float32)
@@ -1088,31 +1075,29 @@ class Context:
         return out
 
 
-class Sky:
-    """lfdmi_sky: the sky normalisation of frames of ``shape`` on ``ctx``'s device (include/lfdmi.h: sky normalisation).  The
-    handle owns the meshes and a device buffer of ``max_frames`` normalised frames; ``Context.close()`` closes it first."""
+class _Handle:
+    """What ``Sky`` and ``Radon`` share: a library handle made on a context for frames of one shape, closed with the context
+    at the latest.  A subclass names itself (``_what``), its params function, its create and destroy symbols and the attribute
+    its handle is read under (``_attr``)."""
 
     def __init__(self, ctx, shape, max_frames=None, **params):
-        self._s = C.c_void_p()
+        setattr(self, self._attr, C.c_void_p())
         self._lib = lib()
         self.ctx = ctx
         if not getattr(ctx, "_h", None):
             raise ValueError("the context is closed")
         self.shape = (int(shape[0]), int(shape[1]))
         self.max_frames = int(ctx.max_inflight if max_frames is None else max_frames)
-        self.params = make_sky_params(**params)
-        ctx._chk(self._lib.lfdmi_sky_create(ctx._h, self.shape[0], self.shape[1], self.max_frames, C.byref(self.params),
-                                            C.byref(self._s)))
+        self.params = self._make_params(**params)
+        ctx._chk(getattr(self._lib, self._create)(ctx._h, self.shape[0], self.shape[1], self.max_frames, C.byref(self.params),
+                                                   C.byref(getattr(self, self._attr))))
         import weakref
         ctx.__dict__.setdefault("_skies", weakref.WeakSet()).add(self)
-        ny, nx, nb = C.c_int32(), C.c_int32(), C.c_int64()
-        self._lib.lfdmi_sky_dims(self._s, C.byref(ny), C.byref(nx), C.byref(nb))
-        self.ny, self.nx, self.bytes = ny.value, nx.value, nb.value
 
     def close(self):
-        if getattr(self, "_s", None):
-            self._lib.lfdmi_sky_destroy(self._s)
-            self._s = C.c_void_p()
+        if getattr(self, self._attr, None):
+            getattr(self._lib, self._destroy)(getattr(self, self._attr))
+            setattr(self, self._attr, C.c_void_p())
 
     def __enter__(self):
         return self
@@ -1126,24 +1111,44 @@ class Sky:
         except Exception:
             pass
 
+    def _open(self, need_ctx=True):
+        """the handle, refused when it (or, for a call, its context) is closed"""
+        if not getattr(self, self._attr) or (need_ctx and not getattr(self.ctx, "_h", None)):
+            raise ValueError(f"the {self._what} handle is closed")
+        return getattr(self, self._attr)
+
+    def _frames(self, frames, pinned, what, **kw):
+        """``Context._frames`` of frames that must have the handle's shape"""
+        frames, code, n, h, w, loc = self.ctx._frames(frames, pinned, what, **kw)
+        if (h, w) != self.shape:
+            raise NativeError(ERR_ARG, f"{what}: frames of {h} x {w}, the handle was made for {self.shape[0]} x {self.shape[1]}")
+        return frames, code, n, h, w, loc
+
+
+class Sky(_Handle):
+    """lfdmi_sky: the sky normalisation of frames of ``shape`` on ``ctx``'s device (include/lfdmi.h: sky normalisation).  The
+    handle owns the meshes and a device buffer of ``max_frames`` normalised frames; ``Context.close()`` closes it first."""
+    _what, _attr, _create, _destroy = "sky", "_s", "lfdmi_sky_create", "lfdmi_sky_destroy"
+    _make_params = staticmethod(make_sky_params)
+
+    def __init__(self, ctx, shape, max_frames=None, **params):
+        super().__init__(ctx, shape, max_frames, **params)
+        ny, nx, nb = C.c_int32(), C.c_int32(), C.c_int64()
+        self._lib.lfdmi_sky_dims(self._s, C.byref(ny), C.byref(nx), C.byref(nb))
+        self.ny, self.nx, self.bytes = ny.value, nx.value, nb.value
+
     def frames(self, n=None):
         """The handle's device buffer as ``DeviceFrames`` (``NativeDeviceFrames``: native float32)."""
-        if not self._s:
-            raise ValueError("the sky handle is closed")
         n = self.max_frames if n is None else int(n)
-        return NativeDeviceFrames(self._lib.lfdmi_sky_frames(self._s), (n, *self.shape))
+        return NativeDeviceFrames(self._lib.lfdmi_sky_frames(self._open(need_ctx=False)), (n, *self.shape))
 
     def normalize(self, frames, out=None, meshes=False, pinned=False):
         """Normalise ``frames`` ('<f4' / '>f4' numpy, torch CUDA float32, ``DeviceFrames`` holding big-endian data).  out: None =
         the handle's device buffer (``frames(n)``; n <= max_frames), "inplace" for torch CUDA float32 frames, or a float32 numpy
         array / torch CUDA tensor of the frames' shape.  Returns the SKY_DTYPE records [n], and with meshes=True also the
         filtered sky and sigma meshes, float32 [n, ny, nx] each."""
-        if not self._s or not getattr(self.ctx, "_h", None):
-            raise ValueError("the sky handle is closed")
-        ctx = self.ctx
-        frames, code, n, h, w, loc = ctx._frames(frames, pinned, "Sky.normalize")
-        if (h, w) != self.shape:
-            raise NativeError(ERR_ARG, f"Sky.normalize: frames of {h} x {w}, the handle was made for {self.shape[0]} x {self.shape[1]}")
+        s, ctx = self._open(), self.ctx
+        frames, code, n, h, w, loc = self._frames(frames, pinned, "Sky.normalize")
         if isinstance(out, str):
             if out != "inplace":
                 raise ValueError("out: None, 'inplace' or an array")
@@ -1158,28 +1163,19 @@ class Sky:
         rec = np.zeros(n, SKY_DTYPE)
         mb = np.empty((n, self.ny, self.nx), np.float32) if meshes else None
         ms = np.empty((n, self.ny, self.nx), np.float32) if meshes else None
-        ctx._chk(self._lib.lfdmi_sky_normalize(ctx._h, self._s, _ptr(frames), code, n, loc, _ptr(out), out_loc, _ptr(rec), _ptr(mb),
+        ctx._chk(self._lib.lfdmi_sky_normalize(ctx._h, s, _ptr(frames), code, n, loc, _ptr(out), out_loc, _ptr(rec), _ptr(mb),
                                                _ptr(ms)))
         return (rec, mb, ms) if meshes else rec
 
 
-class Radon:
+class Radon(_Handle):
     """lfdmi_radon: the faint-trail search of frames of ``shape`` on ``ctx``'s device (include/lfdmi.h: faint-trail search).
     The handle owns the transform's planes for ``max_frames`` frames; ``Context.close()`` closes it first."""
+    _what, _attr, _create, _destroy = "radon", "_r", "lfdmi_radon_create", "lfdmi_radon_destroy"
+    _make_params = staticmethod(make_radon_params)
 
     def __init__(self, ctx, shape, max_frames=None, **params):
-        self._r = C.c_void_p()
-        self._lib = lib()
-        self.ctx = ctx
-        if not getattr(ctx, "_h", None):
-            raise ValueError("the context is closed")
-        self.shape = (int(shape[0]), int(shape[1]))
-        self.max_frames = int(ctx.max_inflight if max_frames is None else max_frames)
-        self.params = make_radon_params(**params)
-        ctx._chk(self._lib.lfdmi_radon_create(ctx._h, self.shape[0], self.shape[1], self.max_frames, C.byref(self.params),
-                                              C.byref(self._r)))
-        import weakref
-        ctx.__dict__.setdefault("_skies", weakref.WeakSet()).add(self)
+        super().__init__(ctx, shape, max_frames, **params)
         self.p01, self.p23, self.bytes = self.dims()
 
     def dims(self):
@@ -1188,37 +1184,14 @@ class Radon:
         self.ctx._chk(self._lib.lfdmi_radon_dims(self._r, C.byref(a), C.byref(b), C.byref(nb)))
         return a.value, b.value, nb.value
 
-    def close(self):
-        if getattr(self, "_r", None):
-            self._lib.lfdmi_radon_destroy(self._r)
-            self._r = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def search(self, frames, sigma=None, pinned=False, native_device=False):
         """The line of largest signal-to-noise of every frame ('<f4' / '>f4' numpy, torch CUDA float32, ``DeviceFrames``), only
         read.  sigma: None (0.025), a number or n values, the frames' sky sigma.  Returns RADON_DTYPE records [n]."""
-        if not self._r or not getattr(self.ctx, "_h", None):
-            raise ValueError("the radon handle is closed")
-        ctx = self.ctx
-        frames, code, n, h, w, loc = ctx._frames(frames, pinned, "Radon.search", native_device=native_device)
-        if (h, w) != self.shape:
-            raise NativeError(ERR_ARG, f"Radon.search: frames of {h} x {w}, the handle was made for {self.shape[0]} x {self.shape[1]}")
-        sg = None
-        if sigma is not None:
-            sg = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, np.float32), (n,)))
+        r, ctx = self._open(), self.ctx
+        frames, code, n, h, w, loc = self._frames(frames, pinned, "Radon.search", native_device=native_device)
+        sg = _sigma(sigma, n)
         res = np.zeros(n, RADON_DTYPE)
-        ctx._chk(self._lib.lfdmi_radon_search(ctx._h, self._r, _ptr(frames), code, n, loc, _ptr(sg), _ptr(res)))
+        ctx._chk(self._lib.lfdmi_radon_search(ctx._h, r, _ptr(frames), code, n, loc, _ptr(sg), _ptr(res)))
         return res
 
     def search_lines(self, frames, sigma=None, max_lines=4, peel_halfwidth=8, min_seg=64, pinned=False, native_device=False):
@@ -1226,19 +1199,13 @@ class Radon:
         7 - 9); frames and sigma as in ``search``.  Returns (RADON_LINE_DTYPE records [n, max_lines], n_lines [n]): a frame's
         found lines are its records 0 .. n_lines-1 in peel order, record n_lines (if there is room) is the round that stopped
         it.  The first call allocates the second V, M set; ``dims()`` counts it from then on."""
-        if not self._r or not getattr(self.ctx, "_h", None):
-            raise ValueError("the radon handle is closed")
-        ctx = self.ctx
+        r, ctx = self._open(), self.ctx
         lp = make_radon_lines_params(max_lines=max_lines, peel_halfwidth=peel_halfwidth, min_seg=min_seg)
-        frames, code, n, h, w, loc = ctx._frames(frames, pinned, "Radon.search_lines", native_device=native_device)
-        if (h, w) != self.shape:
-            raise NativeError(ERR_ARG, f"Radon.search_lines: frames of {h} x {w}, the handle was made for {self.shape[0]} x {self.shape[1]}")
-        sg = None
-        if sigma is not None:
-            sg = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, np.float32), (n,)))
+        frames, code, n, h, w, loc = self._frames(frames, pinned, "Radon.search_lines", native_device=native_device)
+        sg = _sigma(sigma, n)
         k = max(1, min(int(lp.max_lines), RADON_MAX_LINES))      # (out of range: the library refuses before it writes)
         res = np.zeros((n, k), RADON_LINE_DTYPE)
         nl = np.zeros(n, np.int32)
-        ctx._chk(self._lib.lfdmi_radon_search_lines(ctx._h, self._r, _ptr(frames), code, n, loc, _ptr(sg), C.byref(lp), _ptr(res),
+        ctx._chk(self._lib.lfdmi_radon_search_lines(ctx._h, r, _ptr(frames), code, n, loc, _ptr(sg), C.byref(lp), _ptr(res),
                                                     _ptr(nl)))
         return res, nl

@@ -1,6 +1,5 @@
 // defocus.hip -- host side of the defocus bank and fit (include/lfdmi.h: defocus fit; kernels in k_defocus.h).  Its own translation
-// unit: the detection kernels' code object does not change with it.  The context's internals are reached through the ctx_*
-// functions of lfdmi.hip.
+// unit: the detection kernels' code object does not change with it.  The context's internals are reached through unit.h.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -10,25 +9,8 @@
 #include <string>
 #include <vector>
 
-#include "../../include/lfdmi.h"
 #include "k_defocus.h"
-
-int ctx_begin(lfdmi_ctx *ctx);
-int ctx_fail(lfdmi_ctx *ctx, int code, const std::string &msg);
-hipStream_t ctx_stream(lfdmi_ctx *ctx);
-int ctx_device(lfdmi_ctx *ctx);
-void **ctx_defocus(lfdmi_ctx *ctx, void (*release)(lfdmi_ctx *));
-
-#define DHIP(expr)                                                                                      \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return ctx_fail(ctx, LFDMI_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-#define DKCHK(name)                                                                                     \
-    do {                                                                                                \
-        hipError_t e_ = hipGetLastError();                                                              \
-        if (e_ != hipSuccess) return ctx_fail(ctx, LFDMI_ERR_HIP, std::string("launch ") + name + ": " + hipGetErrorString(e_)); \
-    } while (0)
+#include "unit.h"
 
 struct lfdmi_defocus_bank {
     lfdmi_ctx *ctx = nullptr;  // read and fit only: destroy does not touch the context (it may be gone by then)
@@ -63,7 +45,7 @@ static void ws_free(DefocusWs *w) {
 static void ws_release(lfdmi_ctx *ctx) {
     void **slot = ctx_defocus(ctx, nullptr);
     if (*slot) {
-        hipSetDevice(ctx_device(ctx));
+        DeviceGuard on(ctx_device(ctx));
         hipStreamSynchronize(ctx_stream(ctx));
         ws_free((DefocusWs *)*slot);
         delete (DefocusWs *)*slot;
@@ -159,44 +141,44 @@ extern "C" int lfdmi_defocus_bank_create(lfdmi_ctx *ctx, const lfdmi_defocus_par
     auto run = [&]() -> int {
         hipStream_t st = ctx_stream(ctx);
         const size_t ng = (size_t)p.n_h + p.n_r + p.n_se;
-        DHIP(hipMalloc(&b->d_grid, ng * sizeof(double)));
-        DHIP(hipMalloc(&b->cols, (size_t)p.ncol * p.nbp * sizeof(float)));
-        DHIP(hipMalloc(&b->samp, (size_t)p.n_models * p.nq * sizeof(double)));
-        DHIP(hipMalloc(&b->gridv, (size_t)p.n_models * 2 * sizeof(double)));
-        DHIP(hipMalloc(&b->valid, (size_t)p.n_models * sizeof(int)));
-        DHIP(hipMalloc(&b->d_gvalid, (size_t)p.n_groups * sizeof(int)));
+        UHIP(hipMalloc(&b->d_grid, ng * sizeof(double)));
+        UHIP(hipMalloc(&b->cols, (size_t)p.ncol * p.nbp * sizeof(float)));
+        UHIP(hipMalloc(&b->samp, (size_t)p.n_models * p.nq * sizeof(double)));
+        UHIP(hipMalloc(&b->gridv, (size_t)p.n_models * 2 * sizeof(double)));
+        UHIP(hipMalloc(&b->valid, (size_t)p.n_models * sizeof(int)));
+        UHIP(hipMalloc(&b->d_gvalid, (size_t)p.n_groups * sizeof(int)));
         b->bytes = ng * 8 + (size_t)p.ncol * p.nbp * 4 + (size_t)p.n_models * (p.nq * 8 + 16 + 4) + (size_t)p.n_groups * 4;
-        DHIP(hipMalloc(&od, n_od * L * sizeof(double)));
-        DHIP(hipMalloc(&o, n_od * L * sizeof(double)));
-        DHIP(hipMalloc(&d, n_od * L * sizeof(double)));
-        DHIP(hipMalloc(&odf, n_od * sizeof(double)));
-        DHIP(hipMalloc(&odhw, n_od * sizeof(int)));
-        DHIP(hipMalloc(&ks, p.n_se * LK * sizeof(double)));
-        DHIP(hipMalloc(&s, p.n_se * LK * sizeof(double)));
-        DHIP(hipMalloc(&sb, p.n_se * LK * sizeof(double)));
-        DHIP(hipMalloc(&kshw, p.n_se * sizeof(int)));
+        UHIP(hipMalloc(&od, n_od * L * sizeof(double)));
+        UHIP(hipMalloc(&o, n_od * L * sizeof(double)));
+        UHIP(hipMalloc(&d, n_od * L * sizeof(double)));
+        UHIP(hipMalloc(&odf, n_od * sizeof(double)));
+        UHIP(hipMalloc(&odhw, n_od * sizeof(int)));
+        UHIP(hipMalloc(&ks, p.n_se * LK * sizeof(double)));
+        UHIP(hipMalloc(&s, p.n_se * LK * sizeof(double)));
+        UHIP(hipMalloc(&sb, p.n_se * LK * sizeof(double)));
+        UHIP(hipMalloc(&kshw, p.n_se * sizeof(int)));
         std::vector<double> g(b->heights);
         g.insert(g.end(), b->radii.begin(), b->radii.end());
         g.insert(g.end(), b->seeings.begin(), b->seeings.end());
-        DHIP(hipMemcpyAsync(b->d_grid, g.data(), ng * sizeof(double), hipMemcpyHostToDevice, st));
+        UHIP(hipMemcpyAsync(b->d_grid, g.data(), ng * sizeof(double), hipMemcpyHostToDevice, st));
         const double *dh = b->d_grid, *dr = dh + p.n_h, *ds = dr + p.n_r;
         k_def_od<<<n_od, 256, 0, st>>>(dh, dr, p, od, o, d, odhw, odf);
-        DKCHK("k_def_od");
+        ULAUNCH("k_def_od");
         k_def_kernel<<<p.n_se, 256, 0, st>>>(ds, p, ks, s, sb, kshw);
-        DKCHK("k_def_kernel");
+        ULAUNCH("k_def_kernel");
         k_def_sample<<<p.n_models, 256, 0, st>>>(dh, dr, ds, p, od, odhw, ks, kshw, b->samp, b->gridv, b->valid, b->cols);
-        DKCHK("k_def_sample");
+        ULAUNCH("k_def_sample");
         std::vector<int> valid(p.n_models);
         b->dfwhm.resize(n_od);
-        DHIP(hipMemcpyAsync(valid.data(), b->valid, valid.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-        DHIP(hipMemcpyAsync(b->dfwhm.data(), odf, n_od * sizeof(double), hipMemcpyDeviceToHost, st));
+        UHIP(hipMemcpyAsync(valid.data(), b->valid, valid.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+        UHIP(hipMemcpyAsync(b->dfwhm.data(), odf, n_od * sizeof(double), hipMemcpyDeviceToHost, st));
         b->gridv_h.resize((size_t)p.n_models * 2);
-        DHIP(hipMemcpyAsync(b->gridv_h.data(), b->gridv, b->gridv_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-        DHIP(hipStreamSynchronize(st));
+        UHIP(hipMemcpyAsync(b->gridv_h.data(), b->gridv, b->gridv_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        UHIP(hipStreamSynchronize(st));
         b->gvalid.assign(p.n_groups, 0);
         for (int m = 0; m < p.n_models; m++)
             if (valid[m]) b->gvalid[m / p.n_r] = 1;
-        DHIP(hipMemcpy(b->d_gvalid, b->gvalid.data(), p.n_groups * sizeof(int), hipMemcpyHostToDevice));
+        UHIP(hipMemcpy(b->d_gvalid, b->gvalid.data(), p.n_groups * sizeof(int), hipMemcpyHostToDevice));
         return 0;
     };
     rc = run();
@@ -231,11 +213,11 @@ extern "C" int lfdmi_defocus_bank_read(const lfdmi_defocus_bank *b, float *colum
     if (rc) return rc;
     const DefDev &p = b->p;
     if (columns)
-        DHIP(hipMemcpy2D(columns, p.nb * sizeof(float), b->cols, p.nbp * sizeof(float), p.nb * sizeof(float), p.ncol, hipMemcpyDeviceToHost));
+        UHIP(hipMemcpy2D(columns, p.nb * sizeof(float), b->cols, p.nbp * sizeof(float), p.nb * sizeof(float), p.ncol, hipMemcpyDeviceToHost));
     if (grid) {
         const std::vector<double> &gv = b->gridv_h;
         std::vector<int> valid(p.n_models);
-        DHIP(hipMemcpy(valid.data(), b->valid, valid.size() * sizeof(int), hipMemcpyDeviceToHost));
+        UHIP(hipMemcpy(valid.data(), b->valid, valid.size() * sizeof(int), hipMemcpyDeviceToHost));
         for (int m = 0; m < p.n_models; m++) {
             const int ir = m % p.n_r, ih = (m / p.n_r) % (p.n_h + 1), ise = m / (p.n_r * (p.n_h + 1));
             lfdmi_defocus_model &g = grid[m];
@@ -260,8 +242,8 @@ static void fit_blank(lfdmi_defocus_fit *o, int status) {
 }
 
 template <class T> static int ws_buf(lfdmi_ctx *ctx, T **ptr, size_t count) {
-    if (*ptr) { DHIP(hipFree(*ptr)); *ptr = nullptr; }
-    DHIP(hipMalloc((void **)ptr, std::max<size_t>(count, 1) * sizeof(T)));
+    if (*ptr) { UHIP(hipFree(*ptr)); *ptr = nullptr; }
+    UHIP(hipMalloc((void **)ptr, std::max<size_t>(count, 1) * sizeof(T)));
     return 0;
 }
 
@@ -311,7 +293,7 @@ extern "C" int lfdmi_fit_defocus(lfdmi_ctx *ctx, const lfdmi_defocus_bank *b, co
     hipStream_t st = ctx_stream(ctx);
     const size_t rows = std::min<size_t>(act.size(), FIT_CHUNK), rows_pad = (rows + DEF_BM - 1) / DEF_BM * DEF_BM;
     if (W.cap_rows < rows_pad || W.cap_nbp < (size_t)p.nbp || W.cap_groups < (size_t)p.n_groups || W.cap_h < (size_t)nh1) {
-        DHIP(hipStreamSynchronize(st));
+        UHIP(hipStreamSynchronize(st));
         const size_t R = std::max(rows_pad, W.cap_rows), NBP = std::max<size_t>(p.nbp, W.cap_nbp),
                      G = std::max<size_t>(p.n_groups, W.cap_groups), H = std::max<size_t>(nh1, W.cap_h);
         if ((rc = ws_buf(ctx, &W.V, R * NBP)) || (rc = ws_buf(ctx, &W.prof, R * NBP)) || (rc = ws_buf(ctx, &W.noise, R)) ||
@@ -343,21 +325,21 @@ extern "C" int lfdmi_fit_defocus(lfdmi_ctx *ctx, const lfdmi_defocus_bank *b, co
             hn[r] = trails[i].noise;
             hs[r] = slice[i];
         }
-        DHIP(hipMemcpyAsync(W.V, hv.data(), hv.size() * sizeof(float), hipMemcpyHostToDevice, st));
-        DHIP(hipMemcpyAsync(W.prof, hp.data(), hp.size() * sizeof(float), hipMemcpyHostToDevice, st));
-        DHIP(hipMemcpyAsync(W.noise, hn.data(), hn.size() * sizeof(double), hipMemcpyHostToDevice, st));
-        DHIP(hipMemcpyAsync(W.slice, hs.data(), hs.size() * sizeof(int), hipMemcpyHostToDevice, st));
-        DHIP(hipMemsetAsync(W.gmax, 0, (size_t)na * p.n_groups * sizeof(unsigned), st));
+        UHIP(hipMemcpyAsync(W.V, hv.data(), hv.size() * sizeof(float), hipMemcpyHostToDevice, st));
+        UHIP(hipMemcpyAsync(W.prof, hp.data(), hp.size() * sizeof(float), hipMemcpyHostToDevice, st));
+        UHIP(hipMemcpyAsync(W.noise, hn.data(), hn.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        UHIP(hipMemcpyAsync(W.slice, hs.data(), hs.size() * sizeof(int), hipMemcpyHostToDevice, st));
+        UHIP(hipMemsetAsync(W.gmax, 0, (size_t)na * p.n_groups * sizeof(unsigned), st));
         const dim3 grid((unsigned)((p.ncol + DEF_BN - 1) / DEF_BN), (unsigned)(na_pad / DEF_BM));
         k_def_gemm<<<grid, 256, 0, st>>>(W.V, na, b->cols, p, W.slice, b->valid, W.gmax);
-        DKCHK("k_def_gemm");
+        ULAUNCH("k_def_gemm");
         k_def_pick<<<na, 64, 0, st>>>(W.V, W.prof, W.noise, b->cols, b->samp, p, W.slice, b->valid, b->d_gvalid, W.gmax, W.res, W.cbh);
-        DKCHK("k_def_pick");
+        ULAUNCH("k_def_pick");
         hres.resize((size_t)na * 5);
         hcbh.resize((size_t)na * nh1);
-        DHIP(hipMemcpyAsync(hres.data(), W.res, hres.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-        DHIP(hipMemcpyAsync(hcbh.data(), W.cbh, hcbh.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-        DHIP(hipStreamSynchronize(st));
+        UHIP(hipMemcpyAsync(hres.data(), W.res, hres.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        UHIP(hipMemcpyAsync(hcbh.data(), W.cbh, hcbh.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        UHIP(hipStreamSynchronize(st));
         for (int r = 0; r < na; r++) {
             const int i = act[a0 + r];
             const double *rs = &hres[(size_t)r * 5], *cb = &hcbh[(size_t)r * nh1];

@@ -1,6 +1,6 @@
 // inject.hip -- host side of the trail injection (include/lfdmi.h: trail injection; kernels in k_inject.h).  Its own translation
 // unit in its own directory, like sky/: the detection kernels' code object does not change with it.  The context's internals
-// are reached through the ctx_* functions of lfdmi.hip.  The call keeps no state: its device memory comes from the stream's
+// are reached through unit.h.  The call keeps no state: its device memory comes from the stream's
 // pool (hipMallocAsync) and goes back before the call's one wait.
 #include <hip/hip_runtime.h>
 
@@ -12,52 +12,14 @@
 #include <string>
 #include <vector>
 
-#include "../../../include/lfdmi.h"
+#include "../unit.h"
 #include "k_inject.h"
 
-int ctx_begin(lfdmi_ctx *ctx);
-int ctx_fail(lfdmi_ctx *ctx, int code, const std::string &msg);
-hipStream_t ctx_stream(lfdmi_ctx *ctx);
-
 static_assert(INJ_MAX_TABLE == LFDMI_INJECT_MAX_TABLE, "the LDS table holds the header's cap");
-
-#define IHIP(expr)                                                                                      \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return ctx_fail(ctx, LFDMI_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-#define IKCHK(name)                                                                                     \
-    do {                                                                                                \
-        hipError_t e_ = hipGetLastError();                                                              \
-        if (e_ != hipSuccess) return ctx_fail(ctx, LFDMI_ERR_HIP, std::string("launch ") + name + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 #define INJ_LIST_MAX (8u << 20)         // (job, tile) pairs listed at a time: 64 MB
 #define INJ_STAGE_BYTES (512ull << 20)  // device staging of host frames at a time
 #define INJ_RENDER_BLOCKS 2048          // twice what 256 CUs hold at once (4 blocks of 4 waves each at 112 VGPRs): blocks walk the list
-
-namespace {
-// stream-ordered allocations of one call: whatever path leaves the call, they are queued for release behind its work
-struct Pool {
-    hipStream_t st;
-    std::vector<void *> mem;
-    explicit Pool(hipStream_t s) : st(s) {}
-    ~Pool() {   // (a call that fails leaves here: the queued copies still read the call's host arrays, so it waits)
-        if (!mem.empty()) { release(); (void)hipStreamSynchronize(st); }
-    }
-    void release() {
-        for (void *m : mem) (void)hipFreeAsync(m, st);
-        mem.clear();
-    }
-    template <class T> hipError_t get(T **out, size_t count) {
-        void *m = nullptr;
-        hipError_t e = hipMallocAsync(&m, std::max<size_t>(count, 1) * sizeof(T), st);
-        if (e == hipSuccess) mem.push_back(m);
-        *out = (T *)m;
-        return e;
-    }
-};
-}   // namespace
 
 extern "C" int lfdmi_inject_trails(lfdmi_ctx *ctx, void *frames, int dtype, int n, int h, int w, int loc, const lfdmi_inject_trail *trails,
                                    int n_trails, const float *tables, int n_tables, int table_len, double table_step, int subsample) {
@@ -65,7 +27,7 @@ extern "C" int lfdmi_inject_trails(lfdmi_ctx *ctx, void *frames, int dtype, int 
     int rc = ctx_begin(ctx);
     if (rc) return rc;
     if (dtype != LFDMI_F32) return ctx_fail(ctx, LFDMI_ERR_ARG, "lfdmi_inject_trails takes LFDMI_F32 frames");
-    if (loc != LFDMI_HOST && loc != LFDMI_DEVICE && loc != LFDMI_HOST_PINNED) return ctx_fail(ctx, LFDMI_ERR_ARG, "bad loc");
+    if ((rc = unit_loc(ctx, loc))) return rc;
     if (n < 0 || n_trails < 0 || h < 1 || w < 1 || (double)h * w > 1e9)
         return ctx_fail(ctx, LFDMI_ERR_ARG, "lfdmi_inject_trails: n, n_trails >= 0, h, w positive, h * w at most 1e9");
     if ((n > 0 && !frames) || (n_trails > 0 && (!trails || !tables))) return ctx_fail(ctx, LFDMI_ERR_ARG, "NULL argument");
@@ -135,34 +97,34 @@ extern "C" int lfdmi_inject_trails(lfdmi_ctx *ctx, void *frames, int dtype, int 
     float *d_tab = nullptr, *d_buf = nullptr;
     int2 *d_list = nullptr;
     int *d_count = nullptr;
-    IHIP(pool.get(&d_tr, (size_t)n_trails));
-    IHIP(pool.get(&d_job, nj));
-    IHIP(pool.get(&d_tab, (size_t)n_tables * table_len));
-    IHIP(pool.get(&d_list, CH * ntiles));
-    IHIP(pool.get(&d_count, 1));
-    if (!in_dev) IHIP(pool.get(&d_buf, CH * N));
-    IHIP(hipMemcpyAsync(d_tr, ht.data(), (size_t)n_trails * sizeof(InjTrail), hipMemcpyHostToDevice, st));
-    IHIP(hipMemcpyAsync(d_job, hj.data(), nj * sizeof(InjJob), hipMemcpyHostToDevice, st));
-    IHIP(hipMemcpyAsync(d_tab, tables, (size_t)n_tables * table_len * sizeof(float), hipMemcpyHostToDevice, st));
+    UHIP(pool.get(&d_tr, (size_t)n_trails));
+    UHIP(pool.get(&d_job, nj));
+    UHIP(pool.get(&d_tab, (size_t)n_tables * table_len));
+    UHIP(pool.get(&d_list, CH * ntiles));
+    UHIP(pool.get(&d_count, 1));
+    if (!in_dev) UHIP(pool.get(&d_buf, CH * N));
+    UHIP(hipMemcpyAsync(d_tr, ht.data(), (size_t)n_trails * sizeof(InjTrail), hipMemcpyHostToDevice, st));
+    UHIP(hipMemcpyAsync(d_job, hj.data(), nj * sizeof(InjJob), hipMemcpyHostToDevice, st));
+    UHIP(hipMemcpyAsync(d_tab, tables, (size_t)n_tables * table_len * sizeof(float), hipMemcpyHostToDevice, st));
     float *base = in_dev ? (float *)frames : d_buf;
     for (size_t j0 = 0; j0 < nj; j0 += CH) {
         const size_t c = std::min(CH, nj - j0);
         if (!in_dev)
             for (size_t k = 0; k < c; k++)
-                IHIP(hipMemcpyAsync(d_buf + k * N, (const char *)frames + (size_t)jframe[j0 + k] * FB, FB, hipMemcpyHostToDevice, st));
-        IHIP(hipMemsetAsync(d_count, 0, sizeof(int), st));
+                UHIP(hipMemcpyAsync(d_buf + k * N, (const char *)frames + (size_t)jframe[j0 + k] * FB, FB, hipMemcpyHostToDevice, st));
+        UHIP(hipMemsetAsync(d_count, 0, sizeof(int), st));
         const size_t pairs = c * ntiles;
         k_inject_cull<<<(unsigned)((pairs + INJ_THREADS - 1) / INJ_THREADS), INJ_THREADS, 0, st>>>(d_job + j0, (int)c, d_tr, p, d_list, d_count);
-        IKCHK("k_inject_cull");
+        ULAUNCH("k_inject_cull");
         k_inject_render<<<(unsigned)std::min<size_t>(pairs, INJ_RENDER_BLOCKS), INJ_THREADS, 0, st>>>(base, d_job + j0, d_tr, d_tab, p, d_list,
                                                                                                   d_count);
-        IKCHK("k_inject_render");
+        ULAUNCH("k_inject_render");
         if (!in_dev)
             for (size_t k = 0; k < c; k++)
-                IHIP(hipMemcpyAsync((char *)frames + (size_t)jframe[j0 + k] * FB, d_buf + k * N, FB, hipMemcpyDeviceToHost, st));
+                UHIP(hipMemcpyAsync((char *)frames + (size_t)jframe[j0 + k] * FB, d_buf + k * N, FB, hipMemcpyDeviceToHost, st));
     }
     pool.release();
     // (the host arrays above are read by the queued copies: they live until this wait)
-    IHIP(hipStreamSynchronize(st));
+    UHIP(hipStreamSynchronize(st));
     return 0;
 }

@@ -30,6 +30,7 @@
 #include "k_frame.h"
 #include "k_trail.h"
 #include "fits_reader.h"
+#include "unit.h"
 
 #define LFD_PI 3.1415926535897932384626433832795
 #define MAX_ANGLES 4096 // rows of the cos/sin table (theta >= pi/4096)
@@ -3151,8 +3152,7 @@ extern "C" int lfdmi_get_stage(lfdmi_ctx *ctx, int slot, int which, int h, int w
     return sync(ctx, 1);
 }
 
-// ---- the context as defocus.hip sees it (host side, not exported) -----------------------------------------------------------
-#define LFD_HIDDEN __attribute__((visibility("hidden")))
+// ---- the context as the measurement units see it (unit.h; host side, not exported) -------------------------------------------
 LFD_HIDDEN int ctx_begin(lfdmi_ctx *ctx) { // an entry point's start: not while calls are in flight; the ctx's device, no stale error
     RET(idle(ctx));
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, LFDMI_ERR_HIP, "hipSetDevice");
@@ -3323,11 +3323,7 @@ extern "C" int lfdmi_measure_trails(lfdmi_ctx *ctx, const void *frames, int dtyp
         o->n_pos = std::min(s.s1 * dp.L + dp.L, s.npos) - s.s0 * dp.L;
         o->n_seg = s.s1 - s.s0 + 1;
         o->min_valid = s.min_valid;
-        // the final line's rho / theta: the normal turned into theta in [0, pi]
-        double nx = s.dy, ny = -s.dx;
-        if (ny < 0.0 || (ny == 0.0 && nx < 0.0)) { nx = -nx; ny = -ny; }
-        o->theta = atan2(ny, nx);
-        o->rho = s.fx * nx + s.fy * ny;
+        line_rho_theta(s.fx, s.fy, s.dx, s.dy, &o->rho, &o->theta);   // the final line
         o->x1 = r[0]; o->y1 = r[1]; o->x2 = r[2]; o->y2 = r[3];
         o->background = r[4]; o->noise = r[5]; o->peak = r[6];
         o->fwhm = r[7]; o->fwhm_arcsec = r[8]; o->depth = r[9];

@@ -1,6 +1,6 @@
 // radon.hip -- host side of the faint-trail search (include/lfdmi.h: faint-trail search; kernels in k_radon.h).  Its own
 // translation unit in its own directory, like sky/ and inject/: the detection kernels' code object does not change with it.
-// The context's internals are reached through the ctx_* functions of lfdmi.hip; the handle owns every byte of device memory
+// The context's internals are reached through unit.h; the handle owns every byte of device memory
 // the search uses.
 #include <hip/hip_runtime.h>
 
@@ -11,25 +11,9 @@
 #include <string>
 #include <vector>
 
-#include "../../../include/lfdmi.h"
+#include "../unit.h"
 #include "k_radon.h"
 #include "k_radon_lines.h"
-
-int ctx_begin(lfdmi_ctx *ctx);
-int ctx_fail(lfdmi_ctx *ctx, int code, const std::string &msg);
-hipStream_t ctx_stream(lfdmi_ctx *ctx);
-int ctx_device(lfdmi_ctx *ctx);
-
-#define RHIP(expr)                                                                                      \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return ctx_fail(ctx, LFDMI_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-#define RKCHK(name)                                                                                     \
-    do {                                                                                                \
-        hipError_t e_ = hipGetLastError();                                                              \
-        if (e_ != hipSuccess) return ctx_fail(ctx, LFDMI_ERR_HIP, std::string("launch ") + name + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 struct lfdmi_radon {
     lfdmi_ctx *ctx = nullptr;   // lfdmi_radon_search only: destroy does not touch the context (it may be gone by then)
@@ -102,15 +86,15 @@ extern "C" int lfdmi_radon_create(lfdmi_ctx *ctx, int h, int w, int max_frames, 
     p.part_stride = std::max(s->np[0], s->np[1]);
     auto run = [&]() -> int {
         const size_t F = (size_t)max_frames, px = (size_t)hb * wb, E = (size_t)p.frame_elems;
-        RHIP(hipMalloc(&s->V, F * px * sizeof(float)));
-        RHIP(hipMalloc(&s->M, F * px * sizeof(uint16_t)));
+        UHIP(hipMalloc(&s->V, F * px * sizeof(float)));
+        UHIP(hipMalloc(&s->M, F * px * sizeof(uint16_t)));
         for (int k = 0; k < 2; k++) {
-            RHIP(hipMalloc(&s->S[k], F * E * sizeof(float)));
-            RHIP(hipMalloc(&s->N[k], F * E * sizeof(uint16_t)));
+            UHIP(hipMalloc(&s->S[k], F * E * sizeof(float)));
+            UHIP(hipMalloc(&s->N[k], F * E * sizeof(uint16_t)));
         }
-        RHIP(hipMalloc(&s->sigma, F * sizeof(float)));
-        RHIP(hipMalloc(&s->part, F * 4 * (size_t)p.part_stride * sizeof(RadonPart)));
-        RHIP(hipMalloc(&s->rec, F * sizeof(RadonRec)));
+        UHIP(hipMalloc(&s->sigma, F * sizeof(float)));
+        UHIP(hipMalloc(&s->part, F * 4 * (size_t)p.part_stride * sizeof(RadonPart)));
+        UHIP(hipMalloc(&s->rec, F * sizeof(RadonRec)));
         s->bytes = (int64_t)(F * px * 6 + F * E * 12 + F * 4 + F * 4 * (size_t)p.part_stride * sizeof(RadonPart) + F * sizeof(RadonRec));
         return 0;
     };
@@ -123,14 +107,11 @@ extern "C" int lfdmi_radon_create(lfdmi_ctx *ctx, int h, int w, int max_frames, 
 extern "C" void lfdmi_radon_destroy(lfdmi_radon *s) {
     if (!s) return;
     // lfdmi_radon_search returns after its stream has drained, so no work of the context still uses these buffers
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) cur = -1;
-    hipSetDevice(s->device);
+    DeviceGuard on(s->device);   // the caller's current device stays what it was
     for (void *x : {(void *)s->V, (void *)s->M, (void *)s->S[0], (void *)s->S[1], (void *)s->N[0], (void *)s->N[1], (void *)s->sigma,
                     (void *)s->stage, (void *)s->part, (void *)s->rec, (void *)s->V2, (void *)s->M2, (void *)s->pre, (void *)s->cnt,
                     (void *)s->lnd, (void *)s->ext})
         if (x) hipFree(x);
-    if (cur >= 0 && cur != s->device) hipSetDevice(cur);   // the caller's current device stays what it was
     delete s;
 }
 
@@ -142,27 +123,37 @@ extern "C" int lfdmi_radon_dims(const lfdmi_radon *s, int32_t *p01, int32_t *p23
     return 0;
 }
 
-// definition step 6
-static void radon_line(const RadonDev &p, int q, int y0, int sl, lfdmi_radon_result &o) {
-    const int P = p.P[q >> 1], b = p.b;
-    double px[2], py[2];
-    for (int k = 0; k < 2; k++) {
-        const int c = k ? P - 1 : 0, r = k ? y0 + sl : y0;
-        int i, j;
-        if (q == 0) { i = c; j = r; }
-        else if (q == 1) { i = c; j = p.hb - 1 - r; }
-        else if (q == 2) { i = r; j = c; }
-        else { i = p.wb - 1 - r; j = c; }
-        px[k] = (double)b * i + (double)(b - 1) / 2.0;
-        py[k] = (double)b * j + (double)(b - 1) / 2.0;
-    }
-    double theta = atan2(-(px[1] - px[0]), py[1] - py[0]);
+// the working point (c, r) of orientation q in pixels (step 6's mapping)
+static void radon_point(const RadonDev &p, int q, int c, int r, double &x, double &y) {
+    int i, j;
+    if (q == 0) { i = c; j = r; }
+    else if (q == 1) { i = c; j = p.hb - 1 - r; }
+    else if (q == 2) { i = r; j = c; }
+    else { i = p.wb - 1 - r; j = c; }
+    x = (double)p.b * i + (double)(p.b - 1) / 2.0;
+    y = (double)p.b * j + (double)(p.b - 1) / 2.0;
+}
+
+// definition step 6 (o: an lfdmi_radon_result, or the lfdmi_radon_line that begins with its fields)
+template <class T> static void radon_line(const RadonDev &p, int q, int y0, int sl, T &o) {
+    radon_point(p, q, 0, y0, o.x1, o.y1);
+    radon_point(p, q, p.P[q >> 1] - 1, y0 + sl, o.x2, o.y2);
+    double theta = atan2(-(o.x2 - o.x1), o.y2 - o.y1);
     const double pi = 3.141592653589793;
     if (theta < 0.0) theta += pi;
     if (theta >= pi) theta -= pi;
-    o.x1 = px[0]; o.y1 = py[0]; o.x2 = px[1]; o.y2 = py[1];
     o.theta = theta;
-    o.rho = px[0] * cos(theta) + py[0] * sin(theta);
+    o.rho = o.x1 * cos(theta) + o.y1 * sin(theta);
+}
+
+// the record of a frame's best line as the caller gets it (o zeroed before)
+template <class T> static void radon_fill(const lfdmi_radon *s, const RadonDev &p, const RadonRec &r, T &o) {
+    o.status = r.status;
+    if (o.status != LFDMI_RADON_OK) return;
+    o.q = r.q; o.y0 = r.y0; o.s = r.s; o.n_pix = r.n_pix;
+    o.sum = r.sum; o.snr = r.snr;
+    o.found = o.snr >= s->par.threshold;
+    radon_line(p, o.q, o.y0, o.s, o);
 }
 
 // definition steps 3 - 6 of the nf frames in V, M (sigma in s->sigma): their records in s->rec
@@ -175,7 +166,7 @@ static int radon_transform(lfdmi_ctx *ctx, lfdmi_radon *s, const RadonDev &p, co
             gy = std::max(gy, p.P[o] / G);
         }
         k_radon_first<<<dim3(gx, gy, nf * 4), RAD_THREADS, 0, st>>>(V, M, p, s->S[0], s->N[0]);
-        RKCHK("k_radon_first");
+        ULAUNCH("k_radon_first");
     }
     for (int o = 0; o < 2; o++) {
         const int P = p.P[o], R = p.R[o];
@@ -183,70 +174,95 @@ static int radon_transform(lfdmi_ctx *ctx, lfdmi_radon *s, const RadonDev &p, co
         for (; 2 * lv < P; lv *= 2, cur ^= 1) {   // (only reached with lv >= RAD_G)
             const dim3 grid(ceil_div(R + 2 * lv - 1, RAD_Y), P / (2 * RAD_TT), nf * 2);
             k_radon_level<4, false><<<grid, RAD_THREADS, 0, st>>>(s->S[cur], s->N[cur], s->S[cur ^ 1], s->N[cur ^ 1], p, o, lv, nullptr, nullptr);
-            RKCHK("k_radon_level");
+            ULAUNCH("k_radon_level");
         }
         const int tt = std::min(RAD_TT, lv);
         const dim3 grid(ceil_div(R + P - 1, RAD_Y), P / (2 * tt), nf * 2);
         if (lv >= RAD_TT) k_radon_level<4, true><<<grid, RAD_THREADS, 0, st>>>(s->S[cur], s->N[cur], nullptr, nullptr, p, o, lv, s->sigma, s->part);
         else k_radon_level<1, true><<<grid, RAD_THREADS, 0, st>>>(s->S[cur], s->N[cur], nullptr, nullptr, p, o, lv, s->sigma, s->part);
-        RKCHK("k_radon_level (last)");
+        ULAUNCH("k_radon_level (last)");
     }
     k_radon_finish<<<nf, RAD_THREADS, 0, st>>>(s->part, p, s->np[0], s->np[1], s->rec);
-    RKCHK("k_radon_finish");
+    ULAUNCH("k_radon_finish");
     return 0;
 }
 
-extern "C" int lfdmi_radon_search(lfdmi_ctx *ctx, lfdmi_radon *s, const void *frames, int dtype, int n, int loc, const float *sigma,
-                                  lfdmi_radon_result *results) {
-    if (!ctx) return LFDMI_ERR_ARG;
-    int rc = ctx_begin(ctx);
-    if (rc) return rc;
-    if (!s || s->ctx != ctx) return ctx_fail(ctx, LFDMI_ERR_ARG, "lfdmi_radon_search: the handle belongs to another context");
-    if (n < 0 || (n > 0 && (!frames || !results))) return ctx_fail(ctx, LFDMI_ERR_ARG, "NULL argument");
-    if (dtype != LFDMI_F32 && dtype != LFDMI_F32_BE) return ctx_fail(ctx, LFDMI_ERR_ARG, "lfdmi_radon_search takes LFDMI_F32 / LFDMI_F32_BE frames");
-    if (loc != LFDMI_HOST && loc != LFDMI_DEVICE && loc != LFDMI_HOST_PINNED) return ctx_fail(ctx, LFDMI_ERR_ARG, "bad loc");
-    std::vector<float> hsig(n, 0.025f);
-    if (sigma)
-        for (int i = 0; i < n; i++) {
-            if (!std::isfinite(sigma[i]) || !(sigma[i] > 0)) return ctx_fail(ctx, LFDMI_ERR_ARG, "lfdmi_radon_search: sigma must be positive");
-            hsig[i] = sigma[i];
-        }
-    if (n == 0) return 0;
-    RadonDev p = s->p;
-    p.be = dtype == LFDMI_F32_BE;
-    const size_t PX = (size_t)p.h * p.w, FB = PX * sizeof(float);
-    const bool in_dev = loc == LFDMI_DEVICE;
-    const int CH = s->max_frames;
-    if (!in_dev && !s->stage) {
-        RHIP(hipMalloc(&s->stage, (size_t)CH * FB));
-        s->bytes += (int64_t)((size_t)CH * FB);
+// what the two searches do alike: the checks of the handle and of the arguments, the frames' sigma on the host, the staging
+// buffer of host frames, and the front of every chunk
+struct LFD_HIDDEN RadonCall {
+    lfdmi_ctx *ctx;
+    lfdmi_radon *s;
+    const char *fn;
+    const void *frames = nullptr;
+    RadonDev p;
+    std::vector<float> hsig;
+    size_t PX = 0, FB = 0;
+    bool in_dev = false;
+    int CH = 0;
+    hipStream_t st = nullptr;
+
+    int begin() {
+        if (!ctx) return LFDMI_ERR_ARG;
+        int rc = ctx_begin(ctx);
+        if (rc) return rc;
+        if (!s || s->ctx != ctx) return ctx_fail(ctx, LFDMI_ERR_ARG, std::string(fn) + ": the handle belongs to another context");
+        return 0;
     }
-    hipStream_t st = ctx_stream(ctx);
-    std::vector<RadonRec> hrec(n);
-    for (int c0 = 0; c0 < n; c0 += CH) {
-        const int nf = std::min(CH, n - c0);
+    // (outs: every output array of the call is there)
+    int args(const void *fr, bool outs, int dtype, int n, int loc, const float *sigma) {
+        int rc;
+        if (n < 0 || (n > 0 && (!fr || !outs))) return ctx_fail(ctx, LFDMI_ERR_ARG, "NULL argument");
+        if ((rc = unit_dtype(ctx, fn, dtype)) || (rc = unit_loc(ctx, loc)) || (rc = unit_sigma(ctx, fn, sigma, n, &hsig))) return rc;
+        frames = fr;
+        p = s->p;
+        p.be = dtype == LFDMI_F32_BE;
+        PX = (size_t)p.h * p.w; FB = PX * sizeof(float);
+        in_dev = loc == LFDMI_DEVICE;
+        CH = s->max_frames;
+        return 0;
+    }
+    // the staging buffer, allocated by the first call with host frames
+    int stage() {
+        if (!in_dev && !s->stage) {
+            UHIP(hipMalloc(&s->stage, (size_t)CH * FB));
+            s->bytes += (int64_t)((size_t)CH * FB);
+        }
+        st = ctx_stream(ctx);
+        return 0;
+    }
+    // frames c0 .. c0 + nf - 1 and their sigma on the device, steps 1 and 2 into s->V, s->M
+    int chunk(int c0, int nf) {
         const uint32_t *src = (const uint32_t *)frames + (size_t)c0 * PX;
         if (!in_dev) {
-            RHIP(hipMemcpyAsync(s->stage, (const char *)frames + (size_t)c0 * FB, (size_t)nf * FB, hipMemcpyHostToDevice, st));
+            UHIP(hipMemcpyAsync(s->stage, (const char *)frames + (size_t)c0 * FB, (size_t)nf * FB, hipMemcpyHostToDevice, st));
             src = (const uint32_t *)s->stage;
         }
-        RHIP(hipMemcpyAsync(s->sigma, hsig.data() + c0, (size_t)nf * sizeof(float), hipMemcpyHostToDevice, st));
+        UHIP(hipMemcpyAsync(s->sigma, hsig.data() + c0, (size_t)nf * sizeof(float), hipMemcpyHostToDevice, st));
         k_radon_prep<<<dim3(ceil_div(p.wb, RAD_THREADS), p.hb, nf), RAD_THREADS, 0, st>>>(src, p, s->V, s->M);
-        RKCHK("k_radon_prep");
-        rc = radon_transform(ctx, s, p, s->V, s->M, nf, st);
-        if (rc) return rc;
-        RHIP(hipMemcpyAsync(hrec.data() + c0, s->rec, (size_t)nf * sizeof(RadonRec), hipMemcpyDeviceToHost, st));
+        ULAUNCH("k_radon_prep");
+        return 0;
     }
-    RHIP(hipStreamSynchronize(st));
+};
+
+extern "C" int lfdmi_radon_search(lfdmi_ctx *ctx, lfdmi_radon *s, const void *frames, int dtype, int n, int loc, const float *sigma,
+                                  lfdmi_radon_result *results) {
+    RadonCall c{ctx, s, "lfdmi_radon_search"};
+    int rc;
+    if ((rc = c.begin()) || (rc = c.args(frames, results, dtype, n, loc, sigma))) return rc;
+    if (n == 0) return 0;
+    if ((rc = c.stage())) return rc;
+    const RadonDev &p = c.p;
+    hipStream_t st = c.st;
+    std::vector<RadonRec> hrec(n);
+    for (int c0 = 0; c0 < n; c0 += c.CH) {
+        const int nf = std::min(c.CH, n - c0);
+        if ((rc = c.chunk(c0, nf)) || (rc = radon_transform(ctx, s, p, s->V, s->M, nf, st))) return rc;
+        UHIP(hipMemcpyAsync(hrec.data() + c0, s->rec, (size_t)nf * sizeof(RadonRec), hipMemcpyDeviceToHost, st));
+    }
+    UHIP(hipStreamSynchronize(st));
     for (int i = 0; i < n; i++) {
-        lfdmi_radon_result &o = results[i];
-        memset(&o, 0, sizeof(o));
-        o.status = hrec[i].status;
-        if (o.status != LFDMI_RADON_OK) continue;
-        o.q = hrec[i].q; o.y0 = hrec[i].y0; o.s = hrec[i].s; o.n_pix = hrec[i].n_pix;
-        o.sum = hrec[i].sum; o.snr = hrec[i].snr;
-        o.found = o.snr >= s->par.threshold;
-        radon_line(p, o.q, o.y0, o.s, o);
+        memset(&results[i], 0, sizeof(results[i]));
+        radon_fill(s, p, hrec[i], results[i]);
     }
     return 0;
 }
@@ -265,59 +281,34 @@ static int radon_path(int c, int sl, int P) {
     return d;
 }
 
-// the working point (c, r) of orientation q in pixels (step 6's mapping)
-static void radon_point(const RadonDev &p, int q, int c, int r, double &x, double &y) {
-    int i, j;
-    if (q == 0) { i = c; j = r; }
-    else if (q == 1) { i = c; j = p.hb - 1 - r; }
-    else if (q == 2) { i = r; j = c; }
-    else { i = p.wb - 1 - r; j = c; }
-    x = (double)p.b * i + (double)(p.b - 1) / 2.0;
-    y = (double)p.b * j + (double)(p.b - 1) / 2.0;
-}
-
 extern "C" int lfdmi_radon_search_lines(lfdmi_ctx *ctx, lfdmi_radon *s, const void *frames, int dtype, int n, int loc, const float *sigma,
                                         const lfdmi_radon_lines_params *lp, lfdmi_radon_line *lines, int32_t *n_lines) {
-    if (!ctx) return LFDMI_ERR_ARG;
-    int rc = ctx_begin(ctx);
+    RadonCall c{ctx, s, "lfdmi_radon_search_lines"};
+    int rc = c.begin();
     if (rc) return rc;
-    if (!s || s->ctx != ctx) return ctx_fail(ctx, LFDMI_ERR_ARG, "lfdmi_radon_search_lines: the handle belongs to another context");
     lfdmi_radon_lines_params lq;
     if (lp) lq = *lp; else lfdmi_default_radon_lines_params(&lq);
     if (lq.max_lines < 1 || lq.max_lines > LFDMI_RADON_MAX_LINES || lq.peel_halfwidth < 0 || lq.min_seg < 1 || lq.min_seg > s->par.min_len)
         return ctx_fail(ctx, LFDMI_ERR_ARG, "radon lines params out of range (include/lfdmi.h: lfdmi_radon_lines_params)");
-    if (n < 0 || (n > 0 && (!frames || !lines || !n_lines))) return ctx_fail(ctx, LFDMI_ERR_ARG, "NULL argument");
-    if (dtype != LFDMI_F32 && dtype != LFDMI_F32_BE) return ctx_fail(ctx, LFDMI_ERR_ARG, "lfdmi_radon_search_lines takes LFDMI_F32 / LFDMI_F32_BE frames");
-    if (loc != LFDMI_HOST && loc != LFDMI_DEVICE && loc != LFDMI_HOST_PINNED) return ctx_fail(ctx, LFDMI_ERR_ARG, "bad loc");
-    std::vector<float> hsig(n, 0.025f);
-    if (sigma)
-        for (int i = 0; i < n; i++) {
-            if (!std::isfinite(sigma[i]) || !(sigma[i] > 0)) return ctx_fail(ctx, LFDMI_ERR_ARG, "lfdmi_radon_search_lines: sigma must be positive");
-            hsig[i] = sigma[i];
-        }
+    if ((rc = c.args(frames, lines && n_lines, dtype, n, loc, sigma))) return rc;
     if (n == 0) return 0;
-    RadonDev p = s->p;
-    p.be = dtype == LFDMI_F32_BE;
-    const size_t PX = (size_t)p.h * p.w, FB = PX * sizeof(float);
-    const bool in_dev = loc == LFDMI_DEVICE;
-    const int CH = s->max_frames, K = lq.max_lines;
+    const RadonDev &p = c.p;
+    const std::vector<float> &hsig = c.hsig;
+    const int CH = c.CH, K = lq.max_lines;
     const int hw = (int)(((int64_t)lq.peel_halfwidth + p.b - 1) / p.b);
     const int pstride = std::max(p.hb, p.wb) + 1;
-    if (!in_dev && !s->stage) {
-        RHIP(hipMalloc(&s->stage, (size_t)CH * FB));
-        s->bytes += (int64_t)((size_t)CH * FB);
-    }
+    if ((rc = c.stage())) return rc;
     if (!s->V2) {
         const size_t F = (size_t)CH, px = (size_t)p.hb * p.wb;
-        RHIP(hipMalloc(&s->V2, F * px * sizeof(float)));
-        RHIP(hipMalloc(&s->M2, F * px * sizeof(uint16_t)));
-        RHIP(hipMalloc(&s->pre, F * pstride * sizeof(float)));
-        RHIP(hipMalloc(&s->cnt, F * pstride * sizeof(int)));
-        RHIP(hipMalloc(&s->lnd, F * sizeof(RadonLineDev)));
-        RHIP(hipMalloc(&s->ext, F * sizeof(RadonExtDev)));
+        UHIP(hipMalloc(&s->V2, F * px * sizeof(float)));
+        UHIP(hipMalloc(&s->M2, F * px * sizeof(uint16_t)));
+        UHIP(hipMalloc(&s->pre, F * pstride * sizeof(float)));
+        UHIP(hipMalloc(&s->cnt, F * pstride * sizeof(int)));
+        UHIP(hipMalloc(&s->lnd, F * sizeof(RadonLineDev)));
+        UHIP(hipMalloc(&s->ext, F * sizeof(RadonExtDev)));
         s->bytes += (int64_t)(F * px * 6 + F * pstride * 8 + F * (sizeof(RadonLineDev) + sizeof(RadonExtDev)));
     }
-    hipStream_t st = ctx_stream(ctx);
+    hipStream_t st = c.st;
     memset(lines, 0, (size_t)n * K * sizeof(*lines));
     memset(n_lines, 0, (size_t)n * sizeof(*n_lines));
     float *Vs[2] = {s->V, s->V2};
@@ -330,14 +321,7 @@ extern "C" int lfdmi_radon_search_lines(lfdmi_ctx *ctx, lfdmi_radon *s, const vo
     std::vector<int> alive, found_frames[2];
     for (int c0 = 0; c0 < n; c0 += CH) {
         const int nf = std::min(CH, n - c0);
-        const uint32_t *src = (const uint32_t *)frames + (size_t)c0 * PX;
-        if (!in_dev) {
-            RHIP(hipMemcpyAsync(s->stage, (const char *)frames + (size_t)c0 * FB, (size_t)nf * FB, hipMemcpyHostToDevice, st));
-            src = (const uint32_t *)s->stage;
-        }
-        RHIP(hipMemcpyAsync(s->sigma, hsig.data() + c0, (size_t)nf * sizeof(float), hipMemcpyHostToDevice, st));
-        k_radon_prep<<<dim3(ceil_div(p.wb, RAD_THREADS), p.hb, nf), RAD_THREADS, 0, st>>>(src, p, s->V, s->M);
-        RKCHK("k_radon_prep");
+        if ((rc = c.chunk(c0, nf))) return rc;
         alive.resize(nf);
         for (int a = 0; a < nf; a++) alive[a] = c0 + a;     // slot -> frame
         int cur = 0, pending = -1;                          // pending: the round whose segments are on their way to hx[round & 1]
@@ -357,20 +341,13 @@ extern "C" int lfdmi_radon_search_lines(lfdmi_ctx *ctx, lfdmi_radon *s, const vo
             const int na = (int)alive.size(), b = k & 1;
             rc = radon_transform(ctx, s, p, Vs[cur], Ms[cur], na, st);
             if (rc) return rc;
-            RHIP(hipMemcpyAsync(hrec.data(), s->rec, (size_t)na * sizeof(RadonRec), hipMemcpyDeviceToHost, st));
-            RHIP(hipStreamSynchronize(st));
+            UHIP(hipMemcpyAsync(hrec.data(), s->rec, (size_t)na * sizeof(RadonRec), hipMemcpyDeviceToHost, st));
+            UHIP(hipStreamSynchronize(st));
             if (pending >= 0) { segments(pending); pending = -1; }
             hl[b].clear(); found_frames[b].clear(); hs[b].clear();
             for (int a = 0; a < na; a++) {
                 lfdmi_radon_line &o = lines[(size_t)alive[a] * K + k];
-                o.status = hrec[a].status;
-                if (o.status != LFDMI_RADON_OK) continue;
-                o.q = hrec[a].q; o.y0 = hrec[a].y0; o.s = hrec[a].s; o.n_pix = hrec[a].n_pix;
-                o.sum = hrec[a].sum; o.snr = hrec[a].snr;
-                o.found = o.snr >= s->par.threshold;
-                lfdmi_radon_result r;
-                radon_line(p, o.q, o.y0, o.s, r);
-                o.x1 = r.x1; o.y1 = r.y1; o.x2 = r.x2; o.y2 = r.y2; o.rho = r.rho; o.theta = r.theta;
+                radon_fill(s, p, hrec[a], o);
                 if (!o.found) continue;
                 n_lines[alive[a]] = k + 1;
                 hl[b].push_back(RadonLineDev{a, o.q, o.y0, o.s});
@@ -380,10 +357,10 @@ extern "C" int lfdmi_radon_search_lines(lfdmi_ctx *ctx, lfdmi_radon *s, const vo
             const int nl = (int)hl[b].size();
             if (!nl) break;
             hx[b].resize(nl);
-            RHIP(hipMemcpyAsync(s->lnd, hl[b].data(), (size_t)nl * sizeof(RadonLineDev), hipMemcpyHostToDevice, st));
+            UHIP(hipMemcpyAsync(s->lnd, hl[b].data(), (size_t)nl * sizeof(RadonLineDev), hipMemcpyHostToDevice, st));
             k_radon_extent<<<nl, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, s->sigma, lq.min_seg, s->pre, s->cnt, pstride, s->ext);
-            RKCHK("k_radon_extent");
-            RHIP(hipMemcpyAsync(hx[b].data(), s->ext, (size_t)nl * sizeof(RadonExtDev), hipMemcpyDeviceToHost, st));
+            ULAUNCH("k_radon_extent");
+            UHIP(hipMemcpyAsync(hx[b].data(), s->ext, (size_t)nl * sizeof(RadonExtDev), hipMemcpyDeviceToHost, st));
             pending = k;
             if (k + 1 == K) break;
             // the found frames go on: slot e of the other set is the frame of line e
@@ -394,13 +371,13 @@ extern "C" int lfdmi_radon_search_lines(lfdmi_ctx *ctx, lfdmi_radon *s, const vo
                 const dim3 grid(ceil_div(p.wb, RAD_THREADS), ceil_div(p.hb, RADL_ROWS), nl);
                 k_radon_peel<1><<<grid, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, hw, Vs[cur ^ 1], Ms[cur ^ 1]);
             }
-            RKCHK("k_radon_peel");
-            RHIP(hipMemcpyAsync(s->sigma, hs[b].data(), (size_t)nl * sizeof(float), hipMemcpyHostToDevice, st));
+            ULAUNCH("k_radon_peel");
+            UHIP(hipMemcpyAsync(s->sigma, hs[b].data(), (size_t)nl * sizeof(float), hipMemcpyHostToDevice, st));
             alive = found_frames[b];
             cur ^= 1;
         }
         if (pending >= 0) {
-            RHIP(hipStreamSynchronize(st));
+            UHIP(hipStreamSynchronize(st));
             segments(pending);
         }
     }

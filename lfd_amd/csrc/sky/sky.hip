@@ -1,6 +1,6 @@
 // sky.hip -- host side of the sky normalisation (include/lfdmi.h: sky normalisation; kernels in k_sky.h).  Its own translation
 // unit in its own directory: the detection kernels' code object does not change with it.  The context's internals are reached
-// through the ctx_* functions of lfdmi.hip; the handle owns every byte of device and page-locked memory the pass uses.
+// through unit.h; the handle owns every byte of device and page-locked memory the pass uses.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -10,24 +10,8 @@
 #include <string>
 #include <vector>
 
-#include "../../../include/lfdmi.h"
+#include "../unit.h"
 #include "k_sky.h"
-
-int ctx_begin(lfdmi_ctx *ctx);
-int ctx_fail(lfdmi_ctx *ctx, int code, const std::string &msg);
-hipStream_t ctx_stream(lfdmi_ctx *ctx);
-int ctx_device(lfdmi_ctx *ctx);
-
-#define SHIP(expr)                                                                                      \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return ctx_fail(ctx, LFDMI_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-#define SKCHK(name)                                                                                     \
-    do {                                                                                                \
-        hipError_t e_ = hipGetLastError();                                                              \
-        if (e_ != hipSuccess) return ctx_fail(ctx, LFDMI_ERR_HIP, std::string("launch ") + name + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 #define SKY_PIN_SLOTS 4   // page-locked staging slots (one frame each) for LFDMI_HOST frames
 
@@ -108,22 +92,22 @@ extern "C" int lfdmi_sky_create(lfdmi_ctx *ctx, int h, int w, int max_frames, co
     axis_tables(h, q.cell, p.ny, ri, rty, &rs);
     auto run = [&]() -> int {
         const size_t M = (size_t)max_frames * s->nc;
-        SHIP(hipMalloc(&s->buf, (size_t)max_frames * s->N * sizeof(float)));
-        for (float **m : {&s->cb, &s->cs, &s->fb, &s->fs, &s->mb, &s->ms}) SHIP(hipMalloc(m, M * sizeof(float)));
-        SHIP(hipMalloc(&s->ne, M * sizeof(int)));
-        SHIP(hipMalloc(&s->rec, (size_t)max_frames * sizeof(SkyRec)));
-        SHIP(hipMalloc(&s->col_i, (size_t)w * sizeof(int)));
-        SHIP(hipMalloc(&s->col_tx, (size_t)w * sizeof(float)));
-        SHIP(hipMalloc(&s->rstart, (size_t)(p.ny + 1) * sizeof(int)));
-        SHIP(hipMalloc(&s->row_ty, (size_t)h * sizeof(float)));
+        UHIP(hipMalloc(&s->buf, (size_t)max_frames * s->N * sizeof(float)));
+        for (float **m : {&s->cb, &s->cs, &s->fb, &s->fs, &s->mb, &s->ms}) UHIP(hipMalloc(m, M * sizeof(float)));
+        UHIP(hipMalloc(&s->ne, M * sizeof(int)));
+        UHIP(hipMalloc(&s->rec, (size_t)max_frames * sizeof(SkyRec)));
+        UHIP(hipMalloc(&s->col_i, (size_t)w * sizeof(int)));
+        UHIP(hipMalloc(&s->col_tx, (size_t)w * sizeof(float)));
+        UHIP(hipMalloc(&s->rstart, (size_t)(p.ny + 1) * sizeof(int)));
+        UHIP(hipMalloc(&s->row_ty, (size_t)h * sizeof(float)));
         s->bytes = (int64_t)((size_t)max_frames * s->N * 4 + M * 28 + (size_t)max_frames * sizeof(SkyRec) + (size_t)w * 8 +
                              (size_t)(p.ny + 1) * 4 + (size_t)h * 4);
-        SHIP(hipMemcpy(s->col_i, ci.data(), (size_t)w * sizeof(int), hipMemcpyHostToDevice));
-        SHIP(hipMemcpy(s->col_tx, col_t.data(), (size_t)w * sizeof(float), hipMemcpyHostToDevice));
-        SHIP(hipMemcpy(s->rstart, rs.data(), (size_t)(p.ny + 1) * sizeof(int), hipMemcpyHostToDevice));
-        SHIP(hipMemcpy(s->row_ty, rty.data(), (size_t)h * sizeof(float), hipMemcpyHostToDevice));
+        UHIP(hipMemcpy(s->col_i, ci.data(), (size_t)w * sizeof(int), hipMemcpyHostToDevice));
+        UHIP(hipMemcpy(s->col_tx, col_t.data(), (size_t)w * sizeof(float), hipMemcpyHostToDevice));
+        UHIP(hipMemcpy(s->rstart, rs.data(), (size_t)(p.ny + 1) * sizeof(int), hipMemcpyHostToDevice));
+        UHIP(hipMemcpy(s->row_ty, rty.data(), (size_t)h * sizeof(float), hipMemcpyHostToDevice));
         if (s->lds > 48 * 1024)   // a 128 x 128 cell: 64 KB of the CU's 160 KB
-            SHIP(hipFuncSetAttribute((const void *)k_sky_cells, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds));
+            UHIP(hipFuncSetAttribute((const void *)k_sky_cells, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds));
         return 0;
     };
     rc = run();
@@ -135,9 +119,7 @@ extern "C" int lfdmi_sky_create(lfdmi_ctx *ctx, int h, int w, int max_frames, co
 extern "C" void lfdmi_sky_destroy(lfdmi_sky *s) {
     if (!s) return;
     // lfdmi_sky_normalize returns after its stream has drained, so no work of the context still uses these buffers
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) cur = -1;
-    hipSetDevice(s->device);
+    DeviceGuard on(s->device);   // the caller's current device stays what it was
     for (void *x : {(void *)s->buf, (void *)s->cb, (void *)s->cs, (void *)s->fb, (void *)s->fs, (void *)s->mb, (void *)s->ms, (void *)s->ne,
                     (void *)s->rec, (void *)s->col_i, (void *)s->col_tx, (void *)s->rstart, (void *)s->row_ty})
         if (x) hipFree(x);
@@ -145,7 +127,6 @@ extern "C" void lfdmi_sky_destroy(lfdmi_sky *s) {
         if (s->pin[k]) hipHostFree(s->pin[k]);
         if (s->pin_ev[k]) hipEventDestroy(s->pin_ev[k]);
     }
-    if (cur >= 0 && cur != s->device) hipSetDevice(cur);   // the caller's current device stays what it was
     delete s;
 }
 
@@ -166,8 +147,7 @@ extern "C" int lfdmi_sky_normalize(lfdmi_ctx *ctx, lfdmi_sky *s, const void *fra
     if (rc) return rc;
     if (!s || s->ctx != ctx) return ctx_fail(ctx, LFDMI_ERR_ARG, "lfdmi_sky_normalize: the handle belongs to another context");
     if (n < 0 || (n > 0 && (!frames || !rec))) return ctx_fail(ctx, LFDMI_ERR_ARG, "NULL argument");
-    if (dtype != LFDMI_F32 && dtype != LFDMI_F32_BE) return ctx_fail(ctx, LFDMI_ERR_ARG, "lfdmi_sky_normalize takes LFDMI_F32 / LFDMI_F32_BE frames");
-    if (loc != LFDMI_HOST && loc != LFDMI_DEVICE && loc != LFDMI_HOST_PINNED) return ctx_fail(ctx, LFDMI_ERR_ARG, "bad loc");
+    if ((rc = unit_dtype(ctx, "lfdmi_sky_normalize", dtype)) || (rc = unit_loc(ctx, loc))) return rc;
     if (out && out_loc != LFDMI_HOST && out_loc != LFDMI_DEVICE && out_loc != LFDMI_HOST_PINNED) return ctx_fail(ctx, LFDMI_ERR_ARG, "bad out_loc");
     const size_t N = s->N, nc = s->nc, FB = N * sizeof(float);
     const bool in_dev = loc == LFDMI_DEVICE, out_dev = out && out_loc == LFDMI_DEVICE, out_host = out && !out_dev;
@@ -185,8 +165,8 @@ extern "C" int lfdmi_sky_normalize(lfdmi_ctx *ctx, lfdmi_sky *s, const void *fra
     if (loc == LFDMI_HOST)
         for (int k = 0; k < SKY_PIN_SLOTS && k < n; k++)
             if (!s->pin[k]) {
-                SHIP(hipHostMalloc(&s->pin[k], FB, hipHostMallocDefault));
-                SHIP(hipEventCreateWithFlags(&s->pin_ev[k], hipEventDisableTiming));
+                UHIP(hipHostMalloc(&s->pin[k], FB, hipHostMallocDefault));
+                UHIP(hipEventCreateWithFlags(&s->pin_ev[k], hipEventDisableTiming));
             }
     SkyDev p = s->p;
     p.be = dtype == LFDMI_F32_BE;
@@ -202,12 +182,12 @@ extern "C" int lfdmi_sky_normalize(lfdmi_ctx *ctx, lfdmi_sky *s, const void *fra
                 const char *from = (const char *)frames + (size_t)(c0 + k) * FB;
                 if (loc == LFDMI_HOST) {
                     const int slot = staged % SKY_PIN_SLOTS;
-                    if (staged >= SKY_PIN_SLOTS) SHIP(hipEventSynchronize(s->pin_ev[slot]));
+                    if (staged >= SKY_PIN_SLOTS) UHIP(hipEventSynchronize(s->pin_ev[slot]));
                     memcpy(s->pin[slot], from, FB);
                     from = (const char *)s->pin[slot];
-                    SHIP(hipMemcpyAsync(s->buf + (size_t)k * N, from, FB, hipMemcpyHostToDevice, st));
-                    SHIP(hipEventRecord(s->pin_ev[slot], st));
-                } else SHIP(hipMemcpyAsync(s->buf + (size_t)k * N, from, FB, hipMemcpyHostToDevice, st));
+                    UHIP(hipMemcpyAsync(s->buf + (size_t)k * N, from, FB, hipMemcpyHostToDevice, st));
+                    UHIP(hipEventRecord(s->pin_ev[slot], st));
+                } else UHIP(hipMemcpyAsync(s->buf + (size_t)k * N, from, FB, hipMemcpyHostToDevice, st));
             }
             src = (const uint32_t *)s->buf;
         }
@@ -215,21 +195,21 @@ extern "C" int lfdmi_sky_normalize(lfdmi_ctx *ctx, lfdmi_sky *s, const void *fra
         float *dst = out_dev ? (float *)out + (size_t)c0 * N : s->buf;
         const int vec_in = p.w % 4 == 0 && p.cell % 4 == 0 && ((uintptr_t)src % 16) == 0;
         k_sky_cells<<<dim3(p.nx, p.ny, nf), SKY_THREADS, s->lds, st>>>(src, N, p, vec_in, s->lds != 0, s->cb, s->cs, s->ne);
-        SKCHK("k_sky_cells");
+        ULAUNCH("k_sky_cells");
         k_sky_mesh<<<nf, SKY_THREADS, 0, st>>>(p, s->cb, s->cs, s->ne, s->fb, s->fs, s->mb, s->ms, s->rec);
-        SKCHK("k_sky_mesh");
+        ULAUNCH("k_sky_mesh");
         const bool v4 = p.w % 4 == 0 && ((uintptr_t)src % 16) == 0 && ((uintptr_t)dst % 16) == 0;
         const int span = SKY_THREADS * (v4 ? 4 : 1);
         const dim3 grid((p.w + span - 1) / span, p.ny * SKY_ROW_SPLIT, nf);
         if (v4) k_sky_apply<4><<<grid, SKY_THREADS, 0, st>>>(src, N, dst, N, p, s->mb, s->rec, s->col_i, s->col_tx, s->rstart, s->row_ty);
         else k_sky_apply<1><<<grid, SKY_THREADS, 0, st>>>(src, N, dst, N, p, s->mb, s->rec, s->col_i, s->col_tx, s->rstart, s->row_ty);
-        SKCHK("k_sky_apply");
-        if (out_host) SHIP(hipMemcpyAsync((char *)out + (size_t)c0 * FB, s->buf, (size_t)nf * FB, hipMemcpyDeviceToHost, st));
-        SHIP(hipMemcpyAsync(hrec.data() + c0, s->rec, (size_t)nf * sizeof(SkyRec), hipMemcpyDeviceToHost, st));
-        if (mesh_sky) SHIP(hipMemcpyAsync(mesh_sky + (size_t)c0 * nc, s->mb, (size_t)nf * nc * sizeof(float), hipMemcpyDeviceToHost, st));
-        if (mesh_sigma) SHIP(hipMemcpyAsync(mesh_sigma + (size_t)c0 * nc, s->ms, (size_t)nf * nc * sizeof(float), hipMemcpyDeviceToHost, st));
+        ULAUNCH("k_sky_apply");
+        if (out_host) UHIP(hipMemcpyAsync((char *)out + (size_t)c0 * FB, s->buf, (size_t)nf * FB, hipMemcpyDeviceToHost, st));
+        UHIP(hipMemcpyAsync(hrec.data() + c0, s->rec, (size_t)nf * sizeof(SkyRec), hipMemcpyDeviceToHost, st));
+        if (mesh_sky) UHIP(hipMemcpyAsync(mesh_sky + (size_t)c0 * nc, s->mb, (size_t)nf * nc * sizeof(float), hipMemcpyDeviceToHost, st));
+        if (mesh_sigma) UHIP(hipMemcpyAsync(mesh_sigma + (size_t)c0 * nc, s->ms, (size_t)nf * nc * sizeof(float), hipMemcpyDeviceToHost, st));
     }
-    SHIP(hipStreamSynchronize(st));
+    UHIP(hipStreamSynchronize(st));
     for (int i = 0; i < n; i++) {
         lfdmi_sky_frame &o = rec[i];
         o.status = hrec[i].status; o.ny = p.ny; o.nx = p.nx; o.n_empty = hrec[i].n_empty;

@@ -1,6 +1,6 @@
 // stack.hip -- host side of the stacked cross-sections (include/lfdmi.h: stacked cross-sections; kernels in k_stack.h).  Its own
 // translation unit in its own directory, like sky/, inject/ and radon/: the detection kernels' code object does not change with
-// it.  The context's internals are reached through the ctx_* functions of lfdmi.hip.  The call keeps no state: its device
+// it.  The context's internals are reached through unit.h.  The call keeps no state: its device
 // memory comes from the stream's pool (hipMallocAsync) and goes back before the call returns.
 #include <hip/hip_runtime.h>
 
@@ -12,49 +12,13 @@
 #include <string>
 #include <vector>
 
-#include "../../../include/lfdmi.h"
+#include "../unit.h"
 #include "k_stack.h"
-
-int ctx_begin(lfdmi_ctx *ctx);
-int ctx_fail(lfdmi_ctx *ctx, int code, const std::string &msg);
-hipStream_t ctx_stream(lfdmi_ctx *ctx);
-
-#define SHIP(expr)                                                                                      \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return ctx_fail(ctx, LFDMI_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-#define SKCHK(name)                                                                                     \
-    do {                                                                                                \
-        hipError_t e_ = hipGetLastError();                                                              \
-        if (e_ != hipSuccess) return ctx_fail(ctx, LFDMI_ERR_HIP, std::string("launch ") + name + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 #define STK_STAGE_BYTES (1ull << 30)   // device staging of host frames at a time
 #define STK_PART_BYTES (128ull << 20)  // block sums and counts of one launch
 
 namespace {
-// stream-ordered allocations of one call: whatever path leaves the call, they are queued for release behind its work
-struct Pool {
-    hipStream_t st;
-    std::vector<void *> mem;
-    explicit Pool(hipStream_t s) : st(s) {}
-    ~Pool() {   // (a call that fails leaves here: the queued copies still read the call's host arrays, so it waits)
-        if (!mem.empty()) { release(); (void)hipStreamSynchronize(st); }
-    }
-    void release() {
-        for (void *m : mem) (void)hipFreeAsync(m, st);
-        mem.clear();
-    }
-    template <class T> hipError_t get(T **out, size_t count) {
-        void *m = nullptr;
-        hipError_t e = hipMallocAsync(&m, std::max<size_t>(count, 1) * sizeof(T), st);
-        if (e == hipSuccess) mem.push_back(m);
-        *out = (T *)m;
-        return e;
-    }
-};
-
 struct Line {
     double a1, b1, g, cosphi;
     double bc(double a) const { return b1 + g * (a - a1); }
@@ -187,10 +151,7 @@ void finalize(const Seg &s, const float *A, const int32_t *N, int K, const lfdmi
     o.x1 = s.xmajor ? af : bf; o.y1 = s.xmajor ? bf : af;
     o.x2 = s.xmajor ? al : bl; o.y2 = s.xmajor ? bl : al;
     const double dx = o.x2 - o.x1, dy = o.y2 - o.y1, len = sqrt(dx * dx + dy * dy);
-    double nx = dy / len, ny = -(dx / len);
-    if (ny < 0.0 || (ny == 0.0 && nx < 0.0)) { nx = -nx; ny = -ny; }
-    o.theta = atan2(ny, nx);
-    o.rho = o.x1 * nx + o.y1 * ny;
+    line_rho_theta(o.x1, o.y1, dx / len, dy / len, &o.rho, &o.theta);
     const double am = (af + al) * 0.5;
     o.shift = (s.l.bc(am) - s.l0.bc(am)) * s.l0.cosphi;
     o.tilt = atan(s.l.g) - atan(s.l0.g);
@@ -225,8 +186,7 @@ extern "C" int lfdmi_stack_profiles(lfdmi_ctx *ctx, const void *frames, int dtyp
     if (!ctx) return LFDMI_ERR_ARG;
     int rc = ctx_begin(ctx);
     if (rc) return rc;
-    if (dtype != LFDMI_F32 && dtype != LFDMI_F32_BE) return ctx_fail(ctx, LFDMI_ERR_ARG, "lfdmi_stack_profiles takes LFDMI_F32 / LFDMI_F32_BE frames");
-    if (loc != LFDMI_HOST && loc != LFDMI_DEVICE && loc != LFDMI_HOST_PINNED) return ctx_fail(ctx, LFDMI_ERR_ARG, "bad loc");
+    if ((rc = unit_dtype(ctx, "lfdmi_stack_profiles", dtype)) || (rc = unit_loc(ctx, loc))) return rc;
     if (n < 0 || n_seg < 0 || h < 1 || w < 1 || h > 65536 || w > 65536)
         return ctx_fail(ctx, LFDMI_ERR_ARG, "lfdmi_stack_profiles: n, n_seg >= 0, h and w 1 .. 65536");
     if ((n > 0 && !frames) || (n_seg > 0 && (!segs || !out))) return ctx_fail(ctx, LFDMI_ERR_ARG, "NULL argument");
@@ -237,9 +197,7 @@ extern "C" int lfdmi_stack_profiles(lfdmi_ctx *ctx, const void *frames, int dtyp
     for (int i = 0; i < n_seg; i++)
         if (segs[i].frame < 0 || segs[i].frame >= n)
             return ctx_fail(ctx, LFDMI_ERR_ARG, "lfdmi_stack_profiles: segment " + std::to_string(i) + ": frame outside [0, n)");
-    if (sigma)
-        for (int i = 0; i < n; i++)
-            if (!std::isfinite(sigma[i]) || !(sigma[i] > 0)) return ctx_fail(ctx, LFDMI_ERR_ARG, "lfdmi_stack_profiles: sigma must be positive");
+    if ((rc = unit_sigma(ctx, "lfdmi_stack_profiles", sigma, n, nullptr))) return rc;
     if (n_seg == 0) return 0;
 
     const int nb = 2 * K + 1;
@@ -302,18 +260,18 @@ extern "C" int lfdmi_stack_profiles(lfdmi_ctx *ctx, const void *frames, int dtyp
         size_t total_items = 0;
         for (int i : active) total_items += (size_t)((sg[i].a_last >> 5) - (sg[i].a_first >> 5) + 2);
         cap_items = std::min(cap_items, total_items);
-        SHIP(pool.get(&d_seg, na0));
-        SHIP(pool.get(&d_item, cap_items));
-        SHIP(pool.get(&d_half, 2 * na0));
-        SHIP(pool.get(&d_ps, cap_items * nb));
-        SHIP(pool.get(&d_pc, cap_items * nb));
-        SHIP(pool.get(&d_sum, na0 * row2));
-        SHIP(pool.get(&d_cnt, na0 * row2));
+        UHIP(pool.get(&d_seg, na0));
+        UHIP(pool.get(&d_item, cap_items));
+        UHIP(pool.get(&d_half, 2 * na0));
+        UHIP(pool.get(&d_ps, cap_items * nb));
+        UHIP(pool.get(&d_pc, cap_items * nb));
+        UHIP(pool.get(&d_sum, na0 * row2));
+        UHIP(pool.get(&d_cnt, na0 * row2));
         const uint32_t *base = (const uint32_t *)frames;
         if (!in_dev) {
-            SHIP(pool.get(&d_buf, gframes[gi].size() * N));
+            UHIP(pool.get(&d_buf, gframes[gi].size() * N));
             for (size_t k = 0; k < gframes[gi].size(); k++)
-                SHIP(hipMemcpyAsync(d_buf + k * N, (const char *)frames + (size_t)gframes[gi][k] * FB, FB, hipMemcpyHostToDevice, st));
+                UHIP(hipMemcpyAsync(d_buf + k * N, (const char *)frames + (size_t)gframes[gi][k] * FB, FB, hipMemcpyHostToDevice, st));
             base = d_buf;
         }
         for (int pass = 0; pass <= q.n_iter && !active.empty(); pass++) {
@@ -336,7 +294,7 @@ extern "C" int lfdmi_stack_profiles(lfdmi_ctx *ctx, const void *frames, int dtyp
             S |= 1;
             if (S > STK_MAX_STRIDE) return ctx_fail(ctx, LFDMI_ERR_CAPACITY, "lfdmi_stack_profiles: the band does not fit the LDS tile");
             dp.S = S;
-            SHIP(hipMemcpyAsync(d_seg, hs.data(), na * sizeof(StkSeg), hipMemcpyHostToDevice, st));
+            UHIP(hipMemcpyAsync(d_seg, hs.data(), na * sizeof(StkSeg), hipMemcpyHostToDevice, st));
             // launches of whole segments; the item and half lists of every launch live until the pass's wait
             for (size_t e0 = 0; e0 < na;) {
                 litems.emplace_back();
@@ -362,19 +320,19 @@ extern "C" int lfdmi_stack_profiles(lfdmi_ctx *ctx, const void *frames, int dtyp
                     }
                 }
                 if (it.size() > cap_items) return ctx_fail(ctx, LFDMI_ERR_CAPACITY, "lfdmi_stack_profiles: block list overflow");
-                SHIP(hipMemcpyAsync(d_item, it.data(), it.size() * sizeof(StkItem), hipMemcpyHostToDevice, st));
-                SHIP(hipMemcpyAsync(d_half + 2 * e0, hv.data(), hv.size() * sizeof(StkHalf), hipMemcpyHostToDevice, st));
+                UHIP(hipMemcpyAsync(d_item, it.data(), it.size() * sizeof(StkItem), hipMemcpyHostToDevice, st));
+                UHIP(hipMemcpyAsync(d_half + 2 * e0, hv.data(), hv.size() * sizeof(StkHalf), hipMemcpyHostToDevice, st));
                 if (!it.empty()) {
                     k_stack_block<<<(unsigned)it.size(), STK_THREADS, (size_t)STK_COLS * S * 8, st>>>(base, d_seg, d_item, dp, d_ps, d_pc);
-                    SKCHK("k_stack_block");
+                    ULAUNCH("k_stack_block");
                 }
                 k_stack_combine<<<(unsigned)hv.size(), STK_THREADS, 0, st>>>(d_half + 2 * e0, nb, d_ps, d_pc, d_sum, d_cnt);
-                SKCHK("k_stack_combine");
+                ULAUNCH("k_stack_combine");
                 e0 = e;
             }
-            SHIP(hipMemcpyAsync(pA.data(), d_sum, na * row2 * sizeof(float), hipMemcpyDeviceToHost, st));
-            SHIP(hipMemcpyAsync(pN.data(), d_cnt, na * row2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            SHIP(hipStreamSynchronize(st));
+            UHIP(hipMemcpyAsync(pA.data(), d_sum, na * row2 * sizeof(float), hipMemcpyDeviceToHost, st));
+            UHIP(hipMemcpyAsync(pN.data(), d_cnt, na * row2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            UHIP(hipStreamSynchronize(st));
             std::vector<int> next;
             for (size_t e = 0; e < na; e++) {
                 const int i = active[e];

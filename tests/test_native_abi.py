@@ -74,3 +74,38 @@ def test_product_never_imports_oracle():
                 with open(os.path.join(dirpath, f)) as fh:
                     text = fh.read()
                 assert "lfd_oracle" not in text and "from oracle" not in text and "import oracle" not in text, f
+
+
+# make_*_params: (what its TypeError names, the struct, the library's defaults function, an override)
+MAKERS = {"make_trail_params": ("trail", "TrailParams", "lfdmi_default_trail_params", ("seg_len", 32)),
+          "make_sky_params": ("sky", "SkyParamsStruct", "lfdmi_default_sky_params", ("cell", 128)),
+          "make_radon_params": ("radon", "RadonParamsStruct", "lfdmi_default_radon_params", ("min_len", 100)),
+          "make_radon_lines_params": ("radon lines", "RadonLinesParamsStruct", "lfdmi_default_radon_lines_params", ("max_lines", 2)),
+          "make_stack_params": ("stack", "StackParamsStruct", "lfdmi_default_stack_params", ("step", 0.25))}
+
+
+@pytest.mark.parametrize("maker", sorted(MAKERS))
+def test_make_params(maker):
+    from lfd_amd import _native
+    what, struct, defaults, (name, value) = MAKERS[maker]
+    make, struct = getattr(_native, maker), getattr(_native, struct)
+    want = struct()
+    getattr(_native.lib(), defaults)(C.byref(want))
+    got = make()
+    assert type(got) is struct and bytes(got) == bytes(want)                     # the library's defaults
+    assert getattr(want, name) != value
+    got = make(**{name: value})
+    assert getattr(got, name) == value                                           # an override, and nothing else
+    setattr(want, name, value)
+    assert bytes(got) == bytes(want)
+    with pytest.raises(TypeError) as e:
+        make(**{name: value, "no_such_field": 1})
+    assert str(e.value) == f"unknown {what} parameter 'no_such_field'"
+
+
+def test_make_sky_params_takes_the_mode_by_name():
+    from lfd_amd import _native
+    assert _native.make_sky_params(mode="subtract").mode == _native.SKY_SUBTRACT
+    for name in ("normalise", "normalize", "Normalise"):
+        assert _native.make_sky_params(mode=name).mode == _native.SKY_NORMALISE
+    assert _native.make_sky_params(mode=_native.SKY_SUBTRACT).mode == _native.SKY_SUBTRACT
