@@ -3,6 +3,7 @@ one rounded operation of the definition, so the device has to reproduce these re
 import math
 
 import numpy as np
+from numpy.lib.stride_tricks import as_strided
 
 OK, NO_LINE = 0, 1
 DEFAULTS = {"bin": 2, "clip": 0.125, "min_len": 256, "threshold": 8.0}
@@ -56,15 +57,16 @@ def transform(Q):
     rows = R + P - 1
     F = np.zeros((P, rows, 1), Q.dtype)
     F[:C, P - 1:P - 1 + R, 0] = Q.T
-    yi = np.arange(rows)[:, None]
     n = 1
     while n < P:
         A = F[0::2]
         B = np.concatenate([F[1::2], np.zeros((P // (2 * n), n + 1, n), Q.dtype)], axis=1)    # rows above R-1 read +0
-        t = np.arange(n)[None, :]
+        # D[j][y][t] = B[j][y + t][t], y = 0 .. rows: the diagonal as a view (a step of one row and one slope), not a gather
+        sj, sy, st = B.strides
+        D = as_strided(B, (B.shape[0], rows + 1, n), (sj, sy, sy + st), writeable=False)
         out = np.empty((P // (2 * n), rows, 2 * n), Q.dtype)
-        out[:, :, 0::2] = A + B[:, yi + t, t]            # s = 2t:     F_n[2j][y][t] + F_n[2j+1][y + t][t]
-        out[:, :, 1::2] = A + B[:, yi + t + 1, t]        # s = 2t + 1: F_n[2j][y][t] + F_n[2j+1][y + t + 1][t]
+        out[:, :, 0::2] = A + D[:, :rows]                # s = 2t:     F_n[2j][y][t] + F_n[2j+1][y + t][t]
+        out[:, :, 1::2] = A + D[:, 1:]                   # s = 2t + 1: F_n[2j][y][t] + F_n[2j+1][y + t + 1][t]
         F = out
         n *= 2
     return F[0, :rows, :]
