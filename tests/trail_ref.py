@@ -67,7 +67,32 @@ def positions(h, w, f, d, L):
     if a > b:
         return 0, 0, 0
     npos = b - a + 1
-    return a, npos, npos // L + (1 if 2 * (npos % L) >= L else 0)
+    return a, npos, n_segments(npos, L)
+
+
+def n_segments(npos, L):
+    """segments of npos positions: the full ones, and a last partial one of at least L/2 positions (step 4)"""
+    return npos // L + (1 if 2 * (npos % L) >= L else 0)
+
+
+def wing_values(md, R, wing):
+    """the wings |u| > R - wing of one segment's m_s(u), u = -R .. R, in index order (step 4)"""
+    return np.concatenate([md[:wing], md[2 * R + 1 - wing:]])
+
+
+def longest_run(flags):
+    """(first segment, length) of the longest run of consecutive significant segments; a tie: the first (step 4)"""
+    best0 = bestn = cur0 = curn = 0
+    for sg, f in enumerate(flags):
+        if f:
+            if curn == 0:
+                cur0 = sg
+            curn += 1
+            if curn > bestn:
+                bestn, best0 = curn, cur0
+        else:
+            curn = 0
+    return best0, bestn
 
 
 def medians(img, star, f, d, ts, us):
@@ -93,7 +118,7 @@ def _segment(m, R, wing, k_sig):
     if np.isnan(m).any():
         return False, 0.0, 0.0
     md = m.astype(np.float64)
-    wings = np.concatenate([md[:wing], md[2 * R + 1 - wing:]])
+    wings = wing_values(md, R, wing)
     b = float(lowmed(wings))
     sd = 1.4826 * float(lowmed(np.abs(wings - b)))
     A = float(np.max(md - b))
@@ -137,16 +162,7 @@ def measure(img, rho, theta, found=1, star_mask=None, **params):
             ts = tmin + np.arange(sg * L, min(sg * L + L, npos))
             m, _ = medians(img, star_mask, f, d, ts, us)
             seg.append(_segment(m, R, wing, p["k_sig"]))
-        best0 = bestn = cur0 = curn = 0
-        for sg in range(nseg):
-            if seg[sg][0]:
-                if curn == 0:
-                    cur0 = sg
-                curn += 1
-                if curn > bestn:
-                    bestn, best0 = curn, cur0
-            else:
-                curn = 0
+        best0, bestn = longest_run([sg[0] for sg in seg])
         if bestn < 2:
             rec["status"] = TOO_FAINT
             return rec, prof
