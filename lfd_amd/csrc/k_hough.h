@@ -174,8 +174,9 @@ k_hough_vote(const uint32_t *list0, const uint32_t *list1, const int *counters, 
     const int AW = 1 << aw_log2;
     int a0 = slab * AW;
     int na = min(AW, numangle - a0);
-    const int lo = slab < VOTE_MAX_SLABS ? rng.lo[slab] : -((numrho - 1) / 2);
-    const int nb = (slab < VOTE_MAX_SLABS ? rng.hi[slab] : numrho - 1 - (numrho - 1) / 2) - lo + 1;
+    // (the slab may take in the guard bins -1 and numrho: see below)
+    const int lo = slab < VOTE_MAX_SLABS ? rng.lo[slab] : -((numrho - 1) / 2) - 1;
+    const int nb = (slab < VOTE_MAX_SLABS ? rng.hi[slab] : numrho - (numrho - 1) / 2) - lo + 1;
     int n = cls ? (im ? nb_b : nb_e) : (im ? na_b : na_e);
     if ((size_t)n > list_cap) n = (int)list_cap;
     int per = ((n + nsplit - 1) / nsplit + 63) / 64 * 64;
@@ -201,8 +202,11 @@ k_hough_vote(const uint32_t *list0, const uint32_t *list1, const int *counters, 
     bool act = ang < na;
     const float c = c_pre, s = s_pre;
     const int nw = NT / 64;
-    // |r| <= (numrho-1)/2 by construction (numrho ~ 2(w+h)/rho, |j cos + i sin| < w+h), as in
-    // OpenCV, which indexes its accumulator without a range check.
+    // numrho = round((2(w+h)+1)/rho) holds every bin while both sides are longer than rho.  On a frame with a side shorter
+    // than rho, x cos / rho alone can round one bin past either end (never two: |r| - (numrho-1)/2 < 1.75 - (h+1.5)/rho);
+    // OpenCV, which indexes its accumulator without a range check, counts such a vote in the guard cell beside the row,
+    // where the neighbour comparison of the edge bin reads it.  So do we: the slab rows reach from bin -1 to bin numrho
+    // (host: vote ranges), and the flush writes the guard rows like any other.
     // Vote address (bytes) = (rint(v) << (aw_log2+2)) + lanebase.  rint (round-half-even,
     // |v| < 2^22) uses the 1.5*2^23 trick: bits(v + 12582912.f) = 0x4B400000 + rint(v); the
     // constant is folded into the base (address arithmetic is mod 2^32).  Lanes without an angle
@@ -303,7 +307,7 @@ k_hough_vote(const uint32_t *list0, const uint32_t *list1, const int *counters, 
     __syncthreads();
     int *ag = accum + ((size_t)g * 2 + im) * acc_cap;
     const int ts = numangle + 2; // transposed row length
-    const int r0 = (numrho - 1) / 2 + lo; // accumulator row of the slab's first bin
+    const int r0 = (numrho - 1) / 2 + lo; // accumulator row of the slab's first bin (-1: the guard row in front of bin 0)
     if (merge) {
         for (int k = threadIdx.x; k < nb * AW; k += NT) {
             int rr = r0 + (k >> aw_log2), al = k & (AW - 1);
@@ -312,16 +316,12 @@ k_hough_vote(const uint32_t *list0, const uint32_t *list1, const int *counters, 
         }
         return;
     }
-    for (int k = threadIdx.x; k < numrho * AW; k += NT) { // rows outside lo .. hi are zero
-        int rr = k >> aw_log2, al = k & (AW - 1);
+    for (int k = threadIdx.x; k < (numrho + 2) * AW; k += NT) { // bins -1 .. numrho; rows outside lo .. hi are zero
+        int rr = (k >> aw_log2) - 1, al = k & (AW - 1);
         int rl = rr - r0;
         if (al < na) ag[(size_t)(rr + 1) * ts + a0 + al + 1] = (rl >= 0 && rl < nb) ? acc[rl * AW + al] : 0;
     }
-    // guard cells: bins -1 and numrho for this slab's angles; angles -1 and numangle for all bins
-    for (int k = threadIdx.x; k < na; k += NT) {
-        ag[a0 + k + 1] = 0;
-        ag[(size_t)(numrho + 1) * ts + a0 + k + 1] = 0;
-    }
+    // guard cells: angles -1 and numangle for all bins
     if (slab == 0)
         for (int k = threadIdx.x; k < numrho + 2; k += NT) { ag[(size_t)k * ts] = 0; ag[(size_t)k * ts + ts - 1] = 0; }
 }

@@ -1386,7 +1386,8 @@ static int run_hough(lfdmi_ctx *ctx, int nc, int h, int w, double rho, double th
         int AW = 1 << aw_log2;
         nslabs = (na + AW - 1) / AW;
         nbmax = 1;
-        for (int sl = 0; sl < VOTE_MAX_SLABS; sl++) { rng.lo[sl] = -half; rng.hi[sl] = nr - 1 - half; }
+        // (bins -1 and numrho, OpenCV's guard cells, belong to the range: a frame with a side shorter than rho votes there)
+        for (int sl = 0; sl < VOTE_MAX_SLABS; sl++) { rng.lo[sl] = -half - 1; rng.hi[sl] = nr - half; }
         if (nslabs <= VOTE_MAX_SLABS && (int)tab_host.size() == 2 * na) {
             for (int sl = 0; sl < nslabs; sl++) {
                 double rmin = 0, rmax = 0;
@@ -1400,11 +1401,11 @@ static int run_hough(lfdmi_ctx *ctx, int nc, int h, int w, double rho, double th
                         }
                 }
                 int lo = (int)floor(rmin) - 2, hi = (int)ceil(rmax) + 2;
-                rng.lo[sl] = lo < -half ? -half : lo;
-                rng.hi[sl] = hi > nr - 1 - half ? nr - 1 - half : hi;
+                rng.lo[sl] = lo < -half - 1 ? -half - 1 : lo;
+                rng.hi[sl] = hi > nr - half ? nr - half : hi;
                 nbmax = std::max(nbmax, rng.hi[sl] - rng.lo[sl] + 1);
             }
-        } else nbmax = nr;
+        } else nbmax = nr + 2;
         if (((size_t)nbmax << aw_log2) * 4 + 256 <= 152 * 1024 || aw_log2 == 0) break;
     }
     if (((size_t)nbmax << aw_log2) * 4 + 256 > 152 * 1024) return fail(ctx, LFDMI_ERR_CAPACITY, "numrho too large for LDS");
