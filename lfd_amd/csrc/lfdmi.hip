@@ -233,6 +233,7 @@ struct lfdmi_ctx {
     bool eroded_valid = false;         // the last dim front end wrote its whole eroded plane (LFDMI_STAGE_ERODED readable even without
                                        // the other stage images: the parity tests of lfdmi_detect_batch's bit-plane front end)
     int vote_split = 4;                // pieces a frame's Hough list is cut into at most
+    int vote_aw = -1;                  // LFDMI_VOTE_AW=0..6: log2 of the angles per vote workgroup, clamped to what fits (-1: run_hough chooses)
     int pe_rows = 12;                  // rows per band of k_prep_erode
     bool fuse_prep_erode = true;       // dim pass: prep + histogram + erosion in one kernel (LFDMI_FUSE_PREP_ERODE=0: separate)
     // general run kernels beside the per-frame ones: launched once this context has met a frame that needs them
@@ -400,6 +401,7 @@ static int create_impl(int device, int max_h, int max_w, int max_inflight, const
     if (const char *e = getenv("LFDMI_DELTA_DIM")) ctx->delta_dim = atoi(e) != 0;
     if (const char *e = getenv("LFDMI_SPARSE_ERODE_FILL")) ctx->sparse_erode_fill = atoi(e) != 0;
     if (const char *e = getenv("LFDMI_VOTE_SPLIT")) { int v = atoi(e); if (v >= 1 && v <= 16) ctx->vote_split = v; }
+    if (const char *e = getenv("LFDMI_VOTE_AW")) { int v = atoi(e); if (*e && v >= 0 && v <= 6) ctx->vote_aw = v; }
     if (const char *e = getenv("LFDMI_PE_ROWS")) { int v = atoi(e); if (v >= 2 && v <= 64) ctx->pe_rows = v; }
     if (const char *e = getenv("LFDMI_FRAME_DBG")) ctx->frame_dbg = atoi(e);
     if (const char *e = getenv("LFDMI_FRAME_RUNCAP")) { int v = atoi(e); if (v >= 0 && v < FRAME_RUNCAP) ctx->frame_runcap = v; }
@@ -1376,19 +1378,20 @@ static int run_hough(lfdmi_ctx *ctx, int nc, int h, int w, double rho, double th
     int na = ctx->numangle, nr = ctx->numrho;
     // Angles per workgroup (AW, a power of two <= 64) and the accumulator rows each angle slab can reach:
     // r = x c + y s over the image rectangle (+- 2 bins of slack).  The LDS slab of a workgroup holds only those rows,
-    // AW votes wide; the largest AW whose widest slab fits in LDS is used (SDSS, rho 20: 64 angles x <= 128 rows;
-    // 4096 x 4096, rho 5: 16 angles x ~1 160 rows).
+    // AW votes wide; the largest AW whose widest slab fits in LDS (SDSS, rho 20: 64 angles x <= 128 rows;
+    // 4096 x 4096, rho 5: 16 angles x ~1 160 rows) is where the choice starts; large batches take a narrower one (below).
     const std::vector<float> &tab_host = ctx->tabs[ctx->tab_cur].host;
     const int half = (nr - 1) / 2;
     VoteRanges rng;
     int aw_log2 = 6, nslabs = 1, nbmax = nr;
-    for (;; aw_log2--) {
-        int AW = 1 << aw_log2;
+    const bool have_tab = (int)tab_host.size() == 2 * na;
+    auto slab_ranges = [&](int awl) { // nslabs, rng.lo / hi and nbmax (rows of the widest slab) for slabs of 1 << awl angles
+        int AW = 1 << awl;
         nslabs = (na + AW - 1) / AW;
         nbmax = 1;
         // (bins -1 and numrho, OpenCV's guard cells, belong to the range: a frame with a side shorter than rho votes there)
         for (int sl = 0; sl < VOTE_MAX_SLABS; sl++) { rng.lo[sl] = -half - 1; rng.hi[sl] = nr - half; }
-        if (nslabs <= VOTE_MAX_SLABS && (int)tab_host.size() == 2 * na) {
+        if (nslabs <= VOTE_MAX_SLABS && have_tab) {
             for (int sl = 0; sl < nslabs; sl++) {
                 double rmin = 0, rmax = 0;
                 for (int n = sl * AW; n < na && n < (sl + 1) * AW; n++) {
@@ -1406,9 +1409,41 @@ static int run_hough(lfdmi_ctx *ctx, int nc, int h, int w, double rho, double th
                 nbmax = std::max(nbmax, rng.hi[sl] - rng.lo[sl] + 1);
             }
         } else nbmax = nr + 2;
+    };
+    for (;; aw_log2--) {
+        slab_ranges(aw_log2);
         if (((size_t)nbmax << aw_log2) * 4 + 256 <= 152 * 1024 || aw_log2 == 0) break;
     }
     if (((size_t)nbmax << aw_log2) * 4 + 256 > 152 * 1024) return fail(ctx, LFDMI_ERR_CAPACITY, "numrho too large for LDS");
+    // pieces a pixel list is cut into so that a launch carries several workgroups per CU, at the width that fits
+    static const int vote_wgs = getenv("LFDMI_VOTE_WGS") ? atoi(getenv("LFDMI_VOTE_WGS")) : 6144;
+    int nsplit = 1;
+    while (nsplit < ctx->vote_split && nslabs * n_img * nc * nsplit < vote_wgs) nsplit <<= 1;
+    // Narrow slabs instead of pieces: every piece zeroes a whole slab in LDS and merges it into a zeroed global
+    // accumulator with atomics, work that grows with (workgroups x slab size) and that the result does not need, and a
+    // few wide workgroups per frame leave the launch's tail to the longest of them.  Where the narrowest slabs that still
+    // have ranges and chunk classes (slab count <= VOTE_MAX_SLABS: 23 slabs of 8 angles for 180 angles) reach on their
+    // own the workgroup count the pieces are cut for, the lists stay whole, every slab is stored directly, and a
+    // workgroup has 512 threads (SDSS, rho 20, 256 frames: 46 workgroups per frame instead of 3 slabs x 8 pieces).
+    // Measured against the wider unsplit shapes and the pieces in profiles/r11_ab_vote_shape.txt.
+    // LFDMI_VOTE_AW (ctx->vote_aw, log2) forces the width: below the width that fits, whole lists; at it, the pieces.
+    bool narrow_path = false;
+    {
+        const int fit = aw_log2, want = ctx->vote_aw; // want < 0: by the rule above
+        int narrow = -1, ns_narrow = 0;
+        for (int awl = fit - 1; awl >= 0 && have_tab; awl--) {
+            const int ns = (na + (1 << awl) - 1) >> awl;
+            if (ns > VOTE_MAX_SLABS) break;
+            narrow = awl; ns_narrow = ns;
+            if (want >= 0 && awl <= want) break; // (forced below the last width with ranges: that last one)
+        }
+        if (narrow >= 0 && (want >= 0 ? want < fit : (long long)ns_narrow * n_img * nc >= vote_wgs)) {
+            aw_log2 = narrow;
+            slab_ranges(aw_log2);
+            nsplit = 1;
+            narrow_path = true;
+        }
+    }
     // Chunk length per slab: (len - 1) * max |cos / rho| over the slab's angles stays below one bin (k_hough_vote's two-bin
     // split; its exact checks do not depend on this bound, only its speed does).  Class A: the length every slab can take;
     // class B: the slabs that can take at least twice that (angles away from the horizontal), with their own, longer cut.
@@ -1435,10 +1470,6 @@ static int run_hough(lfdmi_ctx *ctx, int nc, int h, int w, double rho, double th
     }
     dim3 wg = word_grid(h, w, nc);
     {
-        // cut each pixel list into pieces so that a launch carries several workgroups per CU
-        int nsplit = 1;
-        static const int vote_wgs = getenv("LFDMI_VOTE_WGS") ? atoi(getenv("LFDMI_VOTE_WGS")) : 6144;
-        while (nsplit < ctx->vote_split && nslabs * n_img * nc * nsplit < vote_wgs) nsplit <<= 1;
         // two images: their pieces come out of one pool per slab, shared out by list length on the device (k_hough_vote: balance)
         const bool vote_balance = ctx->vote_balance; // (developer switch LFDMI_VOTE_BALANCE)
         // (unsplit lists -- 4096 x 4096 frames at rho = 5: 12 slabs x 2 images x 256 frames fill the GPU already -- gain nothing from
@@ -1455,7 +1486,8 @@ static int run_hough(lfdmi_ctx *ctx, int nc, int h, int w, double rho, double th
         const int vsplit = balance ? 2 * nsplit : nsplit;
         dim3 vgrid(nslabs * vsplit, balance ? 1 : n_img, nc);
         size_t vlds = ((size_t)nbmax << aw_log2) * 4 + 256;
-        static const int vote_threads = getenv("LFDMI_VOTE_THREADS") ? std::max(64, std::min(1024, atoi(getenv("LFDMI_VOTE_THREADS")) & ~63)) : VOTE_THREADS; // developer knob
+        static const int vote_threads_env = getenv("LFDMI_VOTE_THREADS") ? std::max(64, std::min(1024, atoi(getenv("LFDMI_VOTE_THREADS")) & ~63)) : 0; // developer knob
+        const int vote_threads = vote_threads_env ? vote_threads_env : (narrow_path ? VOTE_THREADS / 2 : VOTE_THREADS);
 #define LFD_LAUNCH_VOTE(L)                                                                                          \
     case L:                                                                                                         \
         k_hough_vote<L><<<vgrid, vote_threads, vlds, ctx->stream>>>(ctx->pix_equ, ctx->pix_box, ctx->counters,           \
