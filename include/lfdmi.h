@@ -766,7 +766,34 @@ int lfdmi_inject_trails(lfdmi_ctx *ctx, void *frames, int dtype, int n, int h, i
  *    lowest (c1, c2); min_seg <= min_len, so a found line always has one.  ex1, ey1, ex2, ey2 (double, on the host) are the
  *    working points (c1, y0 + d(c1)) and (c2, y0 + d(c2)) through step 6's mapping.  Nothing is decided on seg_snr: it is a
  *    measurement, the maximum over about C * C / 2 intervals and therefore biased upward.  The device scores each of those
- *    intervals: C * C / 2 scores per found line (C = 1024 / 745 for an SDSS frame at bin 2). */
+ *    intervals: C * C / 2 scores per found line (C = 1024 / 745 for an SDSS frame at bin 2).
+ *
+ * lfdmi_radon_search_short finds a faint trail that starts and stops inside the frame.  Steps 5 and 9 score it only as part of
+ * a full crossing, whose noise divides it: a trail over a fraction f of its line scores f times the full-length trail, where
+ * sqrt(f) is possible.  The transform already holds the sums of shorter lines: F_L[j][y][s] of step 4 is the sum along a
+ * dyadic line of strip j, L columns long, and every such level is scored here.  tests/radon_short_ref.py restates steps
+ * 10 - 12.
+ * 10. Short candidates.  The scored levels of orientation q are L = min_strip, 2 min_strip, .. P/2 (min_strip a power of two
+ *    >= 64; an orientation with P/2 < min_strip has none; level 32 and below exist only inside the first kernel's on-chip
+ *    memory and are deliberately not scored: a 32-column candidate has too few pixels to stand above the many more lines of
+ *    its level).  Entry (L, q, j, y, s), 0 <= j < P/L, y in [-(L-1), R-1], 0 <= s < L, has the sum S = F_L[j][y][s] and the count
+ *    N, the same recursion on M.  It is a candidate when 2 N >= L b b: at least half of the strip line's pixels are valid (one
+ *    integer rule, no knob; it also keeps a strip that straddles C or the frame's edge from scoring its few pixels).  Its
+ *    score is S / (sigma * sqrtf((float)N)) with step 5's three roundings.  The frame's short candidate is the one of largest
+ *    score; ties go to the lowest (L, q, j, s, y).  No candidate: LFDMI_RADON_NO_LINE, as in step 6.
+ *    found = snr >= short_threshold.
+ * 11. Parent line.  Sp = s * (P / L), y0 = y - d(j L; Sp, P) with d of step 7: the full dyadic line (q, y0, Sp) whose path over
+ *    the columns of strip j is exactly the candidate's (the high bits of a column of strip j are j L's, and below level L the
+ *    slope Sp has come down to s).  d(j L; Sp, P) is exactly s j, so y0 = y - s j >= -(L-1) P / L: the parent row may be
+ *    negative but never lies below -(P-1), the lowest row of step 4; rows that do not exist are +0 in steps 8 and 9.  The
+ *    record's q, y0, s and x1 .. theta are the parent line's, by step 6; n_pix, sum and snr are the candidate's.
+ * 12. Extent and rounds.  Step 9 runs on the parent line with min_seg, which is at most min_strip b b / 2, so a found
+ *    candidate always has a segment (its own strip is one); c1 .. ey2 are that segment's.  The rounds are step 8's with the
+ *    parent line: its band of peel_halfwidth is blotted, the frame transformed again, until found = 0, LFDMI_RADON_NO_LINE or
+ *    max_lines.
+ *    short_threshold defaults to 8.5: the noise-only 372 x 512 frames of step 5's figures peak at 4.6 - 5.81 (bin 1) and
+ *    4.18 - 5.05 (bin 2) over all their levels, and 1.4 times the largest is 8.13 (the plain search keeps 8 / 5.33 = 1.5; a
+ *    whole frame has 16 times the lines of these crops). */
 enum { LFDMI_RADON_OK = 0, LFDMI_RADON_NO_LINE = 1 };
 #define LFDMI_RADON_MAX_LINES 8
 typedef struct {
@@ -826,6 +853,39 @@ void lfdmi_default_radon_lines_params(lfdmi_radon_lines_params *out);
  * of each chunk (the host decides which frames continue). */
 int lfdmi_radon_search_lines(lfdmi_ctx *ctx, lfdmi_radon *radon, const void *frames, int dtype, int n, int loc, const float *sigma,
                              const lfdmi_radon_lines_params *lp, lfdmi_radon_line *lines, int32_t *n_lines);
+typedef struct {
+    int32_t min_strip;        /* the shortest scored strip width L: a power of two >= 64; default 64 */
+    int32_t max_lines;        /* records per frame at most, 1 .. LFDMI_RADON_MAX_LINES; default 4 */
+    int32_t peel_halfwidth;   /* half-width in pixels of the band blotted around a found candidate's parent line (>= 0); default 8 */
+    int32_t min_seg;          /* valid pixels a segment needs, 1 .. min_strip * bin * bin / 2; default 32 */
+    float short_threshold;    /* found = snr >= short_threshold; finite and > 0; default 8.5 (step 12) */
+    int32_t pad;
+} lfdmi_radon_short_params;
+typedef struct {
+    int32_t status;       /* as in lfdmi_radon_line, down to ey2: q, y0, s and x1 .. theta are the parent line (step 11), */
+    int32_t found;        /* n_pix, sum and snr the candidate's, found = snr >= short_threshold */
+    int32_t q, y0, s;
+    int32_t n_pix;
+    float sum, snr;
+    double x1, y1, x2, y2, rho, theta;
+    int32_t c1, c2;
+    int32_t seg_n_pix;
+    int32_t pad;
+    float seg_sum, seg_snr;
+    double ex1, ey1, ex2, ey2;
+    int32_t level, strip, ys, ss;   /* the candidate (step 10): L, j, y, s */
+} lfdmi_radon_short;
+void lfdmi_default_radon_short_params(lfdmi_radon_short_params *out);
+/* lfdmi_radon_search with steps 10 - 12: frames, dtype, n, loc and sigma as there.  sp NULL: the defaults.  lines: n * max_lines
+ * records (host), frame i's at lines[i * max_lines ..], and n_lines: n counts (host), laid out as lfdmi_radon_search_lines'
+ * (step 8).  plain: NULL, or n records (host) that receive, bit for bit, what lfdmi_radon_search returns for these frames: round
+ * 0 runs the last level as well.  Out-of-range parameters: LFDMI_ERR_ARG, and nothing runs.  On its first call the handle
+ * allocates what lfdmi_radon_search_lines' first call does (if it has not) and the scoring levels' partial records;
+ * lfdmi_radon_dims counts them from then on.  The frames are only read; the call refuses while calls are in flight, runs on
+ * the context's stream and waits for it once per round of each chunk. */
+int lfdmi_radon_search_short(lfdmi_ctx *ctx, lfdmi_radon *radon, const void *frames, int dtype, int n, int loc, const float *sigma,
+                             const lfdmi_radon_short_params *sp, lfdmi_radon_short *lines, int32_t *n_lines,
+                             lfdmi_radon_result *plain);
 
 /* ---- stacked cross-sections -------------------------------------------------------------------------------------------------
  * lfdmi_measure_trails needs every 64-position piece of a trail to stand 5 sigma on its own; a trail of the faint-trail search

@@ -42,6 +42,7 @@ SYMBOLS = (
     "lfdmi_inject_trails",
     "lfdmi_default_radon_params", "lfdmi_radon_create", "lfdmi_radon_destroy", "lfdmi_radon_dims", "lfdmi_radon_search",
     "lfdmi_default_radon_lines_params", "lfdmi_radon_search_lines",
+    "lfdmi_default_radon_short_params", "lfdmi_radon_search_short",
     "lfdmi_default_stack_params", "lfdmi_stack_profiles",
 )
 
@@ -227,6 +228,25 @@ def make_radon_lines_params(**params):
     return _make_params(RadonLinesParamsStruct, "lfdmi_default_radon_lines_params", "radon lines", params)
 
 
+class RadonShortParamsStruct(C.Structure):
+    """lfdmi_radon_short_params (include/lfdmi.h: faint-trail search, steps 10 - 12)."""
+    _fields_ = [("min_strip", C.c_int32), ("max_lines", C.c_int32), ("peel_halfwidth", C.c_int32), ("min_seg", C.c_int32),
+                ("short_threshold", C.c_float), ("pad", C.c_int32)]
+
+
+class RadonShort(C.Structure):
+    """lfdmi_radon_short: one record per frame and round of lfdmi_radon_search_short."""
+    _fields_ = RadonLine._fields_ + [("level", C.c_int32), ("strip", C.c_int32), ("ys", C.c_int32), ("ss", C.c_int32)]
+
+
+RADON_SHORT_DTYPE = np.dtype(RADON_LINE_DTYPE.descr + [("level", "<i4"), ("strip", "<i4"), ("ys", "<i4"), ("ss", "<i4")])
+
+
+def make_radon_short_params(**params):
+    """lfdmi_default_radon_short_params with the given fields replaced (unknown names raise)."""
+    return _make_params(RadonShortParamsStruct, "lfdmi_default_radon_short_params", "radon short", params)
+
+
 class StackParamsStruct(C.Structure):
     """lfdmi_stack_params (include/lfdmi.h: stacked cross-sections)."""
     _fields_ = [("wing", C.c_int32), ("n_iter", C.c_int32), ("min_cols", C.c_int32), ("clip", C.c_float),
@@ -329,6 +349,10 @@ def lib():
         _lib.lfdmi_default_radon_lines_params.argtypes = [C.c_void_p]
         _lib.lfdmi_radon_search_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p]
+        _lib.lfdmi_default_radon_short_params.restype = None
+        _lib.lfdmi_default_radon_short_params.argtypes = [C.c_void_p]
+        _lib.lfdmi_radon_search_short.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.lfdmi_default_stack_params.restype = None
         _lib.lfdmi_default_stack_params.argtypes = [C.c_void_p]
         _lib.lfdmi_stack_profiles.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
@@ -1209,3 +1233,21 @@ class Radon(_Handle):
         ctx._chk(self._lib.lfdmi_radon_search_lines(ctx._h, r, _ptr(frames), code, n, loc, _ptr(sg), C.byref(lp), _ptr(res),
                                                     _ptr(nl)))
         return res, nl
+
+    def search_short(self, frames, sigma=None, plain=False, pinned=False, native_device=False, **params):
+        """Short trails: every stored level of the transform scored strip by strip, the best candidate's parent line, its
+        extent, and peeling rounds as in ``search_lines`` (include/lfdmi.h: faint-trail search, steps 10 - 12); frames and
+        sigma as in ``search``, ``params`` the fields of lfdmi_radon_short_params.  Returns (RADON_SHORT_DTYPE records
+        [n, max_lines], n_lines [n]) and, with ``plain``, a third item: the RADON_DTYPE records ``search`` returns for these
+        frames.  The first call allocates the rounds' buffers and the partial records; ``dims()`` counts them from then on."""
+        r, ctx = self._open(), self.ctx
+        sp = make_radon_short_params(**params)
+        frames, code, n, h, w, loc = self._frames(frames, pinned, "Radon.search_short", native_device=native_device)
+        sg = _sigma(sigma, n)
+        k = max(1, min(int(sp.max_lines), RADON_MAX_LINES))      # (out of range: the library refuses before it writes)
+        res = np.zeros((n, k), RADON_SHORT_DTYPE)
+        nl = np.zeros(n, np.int32)
+        pl = np.zeros(n, RADON_DTYPE) if plain else None
+        ctx._chk(self._lib.lfdmi_radon_search_short(ctx._h, r, _ptr(frames), code, n, loc, _ptr(sg), C.byref(sp), _ptr(res),
+                                                    _ptr(nl), _ptr(pl)))
+        return (res, nl, pl) if plain else (res, nl)

@@ -6,6 +6,8 @@
 //                    from global memory, the right strip's, which sits on a diagonal (row y + t, slope t), through an LDS tile
 //                    filled by row-contiguous loads; 16-byte accesses
 //   k_radon_level<FINAL>  the last level: never written; every output is scored and the best (snr, s, y) of the workgroup kept
+//   k_radon_level<SCORE>  a stored level 2n >= min_strip that also scores every output it stores as a short candidate (step 10)
+//                    and keeps the workgroup's best in one partial record; the short search only (k_radon_short.h)
 //   k_radon_finish   one workgroup per frame: the best of the partial records, ties to the lowest (q, s, y)
 // A value of level n is stored only for rows -(n-1) .. R-1: what lies outside is +0 by the definition and is neither written
 // nor read.  Built with -ffp-contract=off; the score uses the correctly rounded intrinsics.
@@ -32,6 +34,10 @@ struct RadonDev {
 struct RadonPart {
     float snr, sum;
     int s, y, n;            // n < 0: no candidate
+};
+struct RadonShortPart {     // a workgroup's best short candidate of one level (its L, q come from the record's place)
+    float snr, sum;
+    int s, y, n, j;         // n < 0: no candidate
 };
 struct RadonRec {
     int status, q, y0, s, n_pix;
@@ -164,10 +170,14 @@ template <> struct RadVec<1> {
 };
 
 // Level n -> 2n of orientation pair o (grid.z = frame * 2 + (q & 1)).  VEC = 4 needs n >= 32; VEC = 1 takes any n.  FINAL: 2n = P.
-template <int VEC, bool FINAL>
+// SCORE (never FINAL, VEC = 4 only): every stored output with N >= n b b (step 10: 2 N >= L b b, L = 2n) is scored, and the
+// workgroup's best goes to spart[f * stotal + soff + (q & 1) * workgroups per q + its place in the grid].
+template <int VEC, bool FINAL, bool SCORE = false>
 __global__ __launch_bounds__(RAD_THREADS) void k_radon_level(const float *__restrict__ Sin, const uint16_t *__restrict__ Nin,
                                                              float *__restrict__ Sout, uint16_t *__restrict__ Nout, RadonDev p, int o, int n,
-                                                             const float *__restrict__ sigma, RadonPart *__restrict__ part) {
+                                                             const float *__restrict__ sigma, RadonPart *__restrict__ part,
+                                                             RadonShortPart *__restrict__ spart, long long soff, long long stotal) {
+    static_assert(!SCORE || (VEC == 4 && !FINAL), "only a stored 16-byte level scores short candidates");
     __shared__ float lb[(RAD_Y + RAD_TT) * RAD_LS];
     __shared__ uint16_t lc[(RAD_Y + RAD_TT) * RAD_LS];
     const int tid = threadIdx.x, q = 2 * o + (blockIdx.z & 1), f = blockIdx.z >> 1;
@@ -202,7 +212,8 @@ __global__ __launch_bounds__(RAD_THREADS) void k_radon_level(const float *__rest
         }
         __syncthreads();
         const int tq = tid % per, ry = tid / per, step = RAD_THREADS / per;
-        const float sg = FINAL ? sigma[f] : 0.0f;
+        const float sg = FINAL || SCORE ? sigma[f] : 0.0f;
+        const unsigned need = SCORE ? (unsigned)(n * p.b * p.b) : 0u;
         for (int yy = ry; yy < RAD_Y; yy += step) {
             const int y = yb + yy;
             if (y > R - 1) break;
@@ -230,6 +241,15 @@ __global__ __launch_bounds__(RAD_THREADS) void k_radon_level(const float *__rest
                 const size_t ao = fbase + ((size_t)j * RP + (size_t)(y + P - 1)) * (2 * n) + 2 * (t0 + tq * VEC);
                 RadVec<VEC>::store(Sout + ao, os);
                 RadVec<VEC>::store(Nout + ao, om);
+                if constexpr (SCORE) {
+#pragma unroll
+                    for (int k = 0; k < 2 * VEC; k++) {
+                        const int s = 2 * (t0 + tq * VEC) + k;
+                        const float snr = __fdiv_rn(os[k], __fmul_rn(sg, sqrtf((float)om[k])));
+                        const bool take = om[k] >= need && (bn < 0 || rad_better(snr, 0, s, y, bs, 0, bss, by));
+                        bs = take ? snr : bs; bsum = take ? os[k] : bsum; bss = take ? s : bss; by = take ? y : by; bn = take ? (int)om[k] : bn;
+                    }
+                }
             } else {
 #pragma unroll
                 for (int k = 0; k < 2 * VEC; k++) {
@@ -255,6 +275,25 @@ __global__ __launch_bounds__(RAD_THREADS) void k_radon_level(const float *__rest
             __syncthreads();
         }
         if (tid == 0) part[((size_t)f * 4 + q) * p.part_stride + (size_t)blockIdx.x * gridDim.y + blockIdx.y] = red[0];
+    }
+    if constexpr (SCORE) {
+        __syncthreads();                        // the right strip's tile has been read: its LDS holds the reduction
+        RadonPart *red = (RadonPart *)lb;
+        red[tid].snr = bs; red[tid].sum = bsum; red[tid].s = bss; red[tid].y = by; red[tid].n = bn;
+        __syncthreads();
+        for (int w = RAD_THREADS / 2; w > 0; w >>= 1) {
+            if (tid < w) {
+                const RadonPart x = red[tid + w], m = red[tid];
+                if (x.n >= 0 && (m.n < 0 || rad_better(x.snr, 0, x.s, x.y, m.snr, 0, m.s, m.y))) red[tid] = x;
+            }
+            __syncthreads();
+        }
+        if (tid == 0) {
+            const RadonPart x = red[0];
+            RadonShortPart r;
+            r.snr = x.snr; r.sum = x.sum; r.s = x.s; r.y = x.y; r.n = x.n; r.j = j;
+            spart[(size_t)f * stotal + soff + (size_t)(q & 1) * gridDim.x * gridDim.y + (size_t)blockIdx.x * gridDim.y + blockIdx.y] = r;
+        }
     }
 }
 

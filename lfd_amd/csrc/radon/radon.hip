@@ -14,6 +14,7 @@
 #include "../unit.h"
 #include "k_radon.h"
 #include "k_radon_lines.h"
+#include "k_radon_short.h"
 
 struct lfdmi_radon {
     lfdmi_ctx *ctx = nullptr;   // lfdmi_radon_search only: destroy does not touch the context (it may be gone by then)
@@ -32,6 +33,10 @@ struct lfdmi_radon {
     int *cnt = nullptr;
     RadonLineDev *lnd = nullptr;
     RadonExtDev *ext = nullptr;
+    // lfdmi_radon_search_short only, allocated on its first call: the scoring levels' partial records (the layout for
+    // min_strip = 64, which holds every other) and the frames' short records
+    RadonShortPart *spart = nullptr;
+    RadonShortRec *srec = nullptr;
     int64_t bytes = 0;
 };
 
@@ -110,7 +115,7 @@ extern "C" void lfdmi_radon_destroy(lfdmi_radon *s) {
     DeviceGuard on(s->device);   // the caller's current device stays what it was
     for (void *x : {(void *)s->V, (void *)s->M, (void *)s->S[0], (void *)s->S[1], (void *)s->N[0], (void *)s->N[1], (void *)s->sigma,
                     (void *)s->stage, (void *)s->part, (void *)s->rec, (void *)s->V2, (void *)s->M2, (void *)s->pre, (void *)s->cnt,
-                    (void *)s->lnd, (void *)s->ext})
+                    (void *)s->lnd, (void *)s->ext, (void *)s->spart, (void *)s->srec})
         if (x) hipFree(x);
     delete s;
 }
@@ -156,8 +161,30 @@ template <class T> static void radon_fill(const lfdmi_radon *s, const RadonDev &
     radon_line(p, o.q, o.y0, o.s, o);
 }
 
-// definition steps 3 - 6 of the nf frames in V, M (sigma in s->sigma): their records in s->rec
-static int radon_transform(lfdmi_ctx *ctx, lfdmi_radon *s, const RadonDev &p, const float *V, const uint16_t *M, int nf, hipStream_t st) {
+// where the scoring levels of strip widths min_strip .. P/2 put their partial records (k_radon_short.h): the grids are
+// radon_transform's
+static RadonShortDev radon_short_layout(const RadonDev &p, int min_strip) {
+    RadonShortDev d;
+    memset(&d, 0, sizeof(d));
+    for (int o = 0; o < 2; o++) {
+        const int P = p.P[o], R = p.R[o];
+        for (int lv = std::min(RAD_G, P / 2); 2 * lv < P; lv *= 2) {
+            if (2 * lv < min_strip) continue;
+            const int e = d.ne++;
+            d.L[e] = 2 * lv; d.o[e] = o;
+            d.cnt[e] = ceil_div(R + 2 * lv - 1, RAD_Y) * (P / (2 * RAD_TT));
+            d.off[e] = d.total;
+            d.total += 2LL * d.cnt[e];
+        }
+    }
+    return d;
+}
+
+// definition steps 3 - 6 of the nf frames in V, M (sigma in s->sigma): their records in s->rec.  sd: the short search's mode --
+// the levels it lists score what they store (step 10) and the frames' short records go to s->srec; `last` false then leaves
+// the last level and s->rec out (a peel round of the short search has no use for them)
+static int radon_transform(lfdmi_ctx *ctx, lfdmi_radon *s, const RadonDev &p, const float *V, const uint16_t *M, int nf, hipStream_t st,
+                           const RadonShortDev *sd = nullptr, bool last = true) {
     {
         int gx = 0, gy = 0;
         for (int o = 0; o < 2; o++) {
@@ -173,17 +200,34 @@ static int radon_transform(lfdmi_ctx *ctx, lfdmi_radon *s, const RadonDev &p, co
         int cur = 0, lv = std::min(RAD_G, P / 2);
         for (; 2 * lv < P; lv *= 2, cur ^= 1) {   // (only reached with lv >= RAD_G)
             const dim3 grid(ceil_div(R + 2 * lv - 1, RAD_Y), P / (2 * RAD_TT), nf * 2);
-            k_radon_level<4, false><<<grid, RAD_THREADS, 0, st>>>(s->S[cur], s->N[cur], s->S[cur ^ 1], s->N[cur ^ 1], p, o, lv, nullptr, nullptr);
+            int e = -1;
+            for (int k = 0; sd && k < sd->ne; k++)
+                if (sd->o[k] == o && sd->L[k] == 2 * lv) e = k;
+            if (e >= 0)
+                k_radon_level<4, false, true><<<grid, RAD_THREADS, 0, st>>>(s->S[cur], s->N[cur], s->S[cur ^ 1], s->N[cur ^ 1], p, o, lv, s->sigma,
+                                                                            nullptr, s->spart, sd->off[e], sd->total);
+            else
+                k_radon_level<4, false><<<grid, RAD_THREADS, 0, st>>>(s->S[cur], s->N[cur], s->S[cur ^ 1], s->N[cur ^ 1], p, o, lv, nullptr, nullptr,
+                                                                      nullptr, 0, 0);
             ULAUNCH("k_radon_level");
         }
+        if (!last) continue;
         const int tt = std::min(RAD_TT, lv);
         const dim3 grid(ceil_div(R + P - 1, RAD_Y), P / (2 * tt), nf * 2);
-        if (lv >= RAD_TT) k_radon_level<4, true><<<grid, RAD_THREADS, 0, st>>>(s->S[cur], s->N[cur], nullptr, nullptr, p, o, lv, s->sigma, s->part);
-        else k_radon_level<1, true><<<grid, RAD_THREADS, 0, st>>>(s->S[cur], s->N[cur], nullptr, nullptr, p, o, lv, s->sigma, s->part);
+        if (lv >= RAD_TT)
+            k_radon_level<4, true><<<grid, RAD_THREADS, 0, st>>>(s->S[cur], s->N[cur], nullptr, nullptr, p, o, lv, s->sigma, s->part, nullptr, 0, 0);
+        else
+            k_radon_level<1, true><<<grid, RAD_THREADS, 0, st>>>(s->S[cur], s->N[cur], nullptr, nullptr, p, o, lv, s->sigma, s->part, nullptr, 0, 0);
         ULAUNCH("k_radon_level (last)");
     }
-    k_radon_finish<<<nf, RAD_THREADS, 0, st>>>(s->part, p, s->np[0], s->np[1], s->rec);
-    ULAUNCH("k_radon_finish");
+    if (last) {
+        k_radon_finish<<<nf, RAD_THREADS, 0, st>>>(s->part, p, s->np[0], s->np[1], s->rec);
+        ULAUNCH("k_radon_finish");
+    }
+    if (sd) {
+        k_radon_short_finish<<<nf, RAD_THREADS, 0, st>>>(s->spart, p, *sd, s->srec);
+        ULAUNCH("k_radon_short_finish");
+    }
     return 0;
 }
 
@@ -281,6 +325,20 @@ static int radon_path(int c, int sl, int P) {
     return d;
 }
 
+// what the rounds of both peeling searches need, allocated by the first call of either
+static int radon_rounds_alloc(lfdmi_ctx *ctx, lfdmi_radon *s, int pstride) {
+    if (s->V2) return 0;
+    const size_t F = (size_t)s->max_frames, px = (size_t)s->p.hb * s->p.wb;
+    UHIP(hipMalloc(&s->V2, F * px * sizeof(float)));
+    UHIP(hipMalloc(&s->M2, F * px * sizeof(uint16_t)));
+    UHIP(hipMalloc(&s->pre, F * pstride * sizeof(float)));
+    UHIP(hipMalloc(&s->cnt, F * pstride * sizeof(int)));
+    UHIP(hipMalloc(&s->lnd, F * sizeof(RadonLineDev)));
+    UHIP(hipMalloc(&s->ext, F * sizeof(RadonExtDev)));
+    s->bytes += (int64_t)(F * px * 6 + F * pstride * 8 + F * (sizeof(RadonLineDev) + sizeof(RadonExtDev)));
+    return 0;
+}
+
 extern "C" int lfdmi_radon_search_lines(lfdmi_ctx *ctx, lfdmi_radon *s, const void *frames, int dtype, int n, int loc, const float *sigma,
                                         const lfdmi_radon_lines_params *lp, lfdmi_radon_line *lines, int32_t *n_lines) {
     RadonCall c{ctx, s, "lfdmi_radon_search_lines"};
@@ -297,17 +355,7 @@ extern "C" int lfdmi_radon_search_lines(lfdmi_ctx *ctx, lfdmi_radon *s, const vo
     const int CH = c.CH, K = lq.max_lines;
     const int hw = (int)(((int64_t)lq.peel_halfwidth + p.b - 1) / p.b);
     const int pstride = std::max(p.hb, p.wb) + 1;
-    if ((rc = c.stage())) return rc;
-    if (!s->V2) {
-        const size_t F = (size_t)CH, px = (size_t)p.hb * p.wb;
-        UHIP(hipMalloc(&s->V2, F * px * sizeof(float)));
-        UHIP(hipMalloc(&s->M2, F * px * sizeof(uint16_t)));
-        UHIP(hipMalloc(&s->pre, F * pstride * sizeof(float)));
-        UHIP(hipMalloc(&s->cnt, F * pstride * sizeof(int)));
-        UHIP(hipMalloc(&s->lnd, F * sizeof(RadonLineDev)));
-        UHIP(hipMalloc(&s->ext, F * sizeof(RadonExtDev)));
-        s->bytes += (int64_t)(F * px * 6 + F * pstride * 8 + F * (sizeof(RadonLineDev) + sizeof(RadonExtDev)));
-    }
+    if ((rc = c.stage()) || (rc = radon_rounds_alloc(ctx, s, pstride))) return rc;
     hipStream_t st = c.st;
     memset(lines, 0, (size_t)n * K * sizeof(*lines));
     memset(n_lines, 0, (size_t)n * sizeof(*n_lines));
@@ -381,5 +429,137 @@ extern "C" int lfdmi_radon_search_lines(lfdmi_ctx *ctx, lfdmi_radon *s, const vo
             segments(pending);
         }
     }
+    return 0;
+}
+
+extern "C" void lfdmi_default_radon_short_params(lfdmi_radon_short_params *o) {
+    if (!o) return;
+    memset(o, 0, sizeof(*o));
+    o->min_strip = 64; o->max_lines = 4; o->peel_halfwidth = 8; o->min_seg = 32; o->short_threshold = 8.5f;
+}
+
+// the record of a frame's short candidate as the caller gets it (o zeroed before): the parent line's geometry by step 6
+static void radon_short_fill(const RadonDev &p, const RadonShortRec &r, float threshold, lfdmi_radon_short &o) {
+    o.status = r.status;
+    if (o.status != LFDMI_RADON_OK) return;
+    o.q = r.q; o.y0 = r.y0; o.s = r.s; o.n_pix = r.n_pix;
+    o.sum = r.sum; o.snr = r.snr;
+    o.level = r.level; o.strip = r.strip; o.ys = r.ys; o.ss = r.ss;
+    o.found = o.snr >= threshold;
+    radon_line(p, o.q, o.y0, o.s, o);
+}
+
+extern "C" int lfdmi_radon_search_short(lfdmi_ctx *ctx, lfdmi_radon *s, const void *frames, int dtype, int n, int loc, const float *sigma,
+                                        const lfdmi_radon_short_params *sp, lfdmi_radon_short *lines, int32_t *n_lines,
+                                        lfdmi_radon_result *plain) {
+    RadonCall c{ctx, s, "lfdmi_radon_search_short"};
+    int rc = c.begin();
+    if (rc) return rc;
+    lfdmi_radon_short_params sq;
+    if (sp) sq = *sp; else lfdmi_default_radon_short_params(&sq);
+    const int bb = s->p.b * s->p.b;
+    if (sq.min_strip < 64 || (sq.min_strip & (sq.min_strip - 1)) || sq.max_lines < 1 || sq.max_lines > LFDMI_RADON_MAX_LINES ||
+        sq.peel_halfwidth < 0 || sq.min_seg < 1 || (int64_t)sq.min_seg > (int64_t)sq.min_strip * bb / 2 ||
+        !std::isfinite(sq.short_threshold) || !(sq.short_threshold > 0))
+        return ctx_fail(ctx, LFDMI_ERR_ARG, "radon short params out of range (include/lfdmi.h: lfdmi_radon_short_params)");
+    if ((rc = c.args(frames, lines && n_lines, dtype, n, loc, sigma))) return rc;
+    if (n == 0) return 0;
+    const RadonDev &p = c.p;
+    const std::vector<float> &hsig = c.hsig;
+    const int CH = c.CH, K = sq.max_lines;
+    const int hw = (int)(((int64_t)sq.peel_halfwidth + p.b - 1) / p.b);
+    const int pstride = std::max(p.hb, p.wb) + 1;
+    if ((rc = c.stage()) || (rc = radon_rounds_alloc(ctx, s, pstride))) return rc;
+    {   // (each buffer on its own: a call that failed between the two allocates only what is missing)
+        const size_t F = (size_t)CH, total = (size_t)std::max(1LL, radon_short_layout(p, 64).total);
+        if (!s->spart) {
+            UHIP(hipMalloc(&s->spart, F * total * sizeof(RadonShortPart)));
+            s->bytes += (int64_t)(F * total * sizeof(RadonShortPart));
+        }
+        if (!s->srec) {
+            UHIP(hipMalloc(&s->srec, F * sizeof(RadonShortRec)));
+            s->bytes += (int64_t)(F * sizeof(RadonShortRec));
+        }
+    }
+    const RadonShortDev sd = radon_short_layout(p, sq.min_strip);
+    hipStream_t st = c.st;
+    memset(lines, 0, (size_t)n * K * sizeof(*lines));
+    memset(n_lines, 0, (size_t)n * sizeof(*n_lines));
+    float *Vs[2] = {s->V, s->V2};
+    uint16_t *Ms[2] = {s->M, s->M2};
+    std::vector<RadonShortRec> hrec(CH);
+    std::vector<RadonRec> hplain(plain ? n : 0);
+    // (round k's host buffers are read or written by copies that finish with round k + 1's wait: two of each alternate)
+    std::vector<RadonLineDev> hl[2];
+    std::vector<RadonExtDev> hx[2];
+    std::vector<float> hs[2];
+    std::vector<int> alive, found_frames[2];
+    for (int c0 = 0; c0 < n; c0 += CH) {
+        const int nf = std::min(CH, n - c0);
+        if ((rc = c.chunk(c0, nf))) return rc;
+        alive.resize(nf);
+        for (int a = 0; a < nf; a++) alive[a] = c0 + a;     // slot -> frame
+        int cur = 0, pending = -1;
+        auto segments = [&](int k) {
+            const int b = k & 1;
+            for (size_t e = 0; e < found_frames[b].size(); e++) {
+                lfdmi_radon_short &o = lines[(size_t)found_frames[b][e] * K + k];
+                const RadonExtDev &x = hx[b][e];
+                const int P = p.P[o.q >> 1];
+                o.c1 = x.c1; o.c2 = x.c2; o.seg_n_pix = x.n; o.seg_sum = x.sum; o.seg_snr = x.snr;
+                radon_point(p, o.q, o.c1, o.y0 + radon_path(o.c1, o.s, P), o.ex1, o.ey1);
+                radon_point(p, o.q, o.c2, o.y0 + radon_path(o.c2, o.s, P), o.ex2, o.ey2);
+            }
+        };
+        for (int k = 0; k < K && !alive.empty(); k++) {
+            const int na = (int)alive.size(), b = k & 1;
+            // round 0 runs the last level too: the plain search's record comes with it
+            rc = radon_transform(ctx, s, p, Vs[cur], Ms[cur], na, st, &sd, k == 0);
+            if (rc) return rc;
+            UHIP(hipMemcpyAsync(hrec.data(), s->srec, (size_t)na * sizeof(RadonShortRec), hipMemcpyDeviceToHost, st));
+            if (k == 0 && plain) UHIP(hipMemcpyAsync(hplain.data() + c0, s->rec, (size_t)na * sizeof(RadonRec), hipMemcpyDeviceToHost, st));
+            UHIP(hipStreamSynchronize(st));
+            if (pending >= 0) { segments(pending); pending = -1; }
+            hl[b].clear(); found_frames[b].clear(); hs[b].clear();
+            for (int a = 0; a < na; a++) {
+                lfdmi_radon_short &o = lines[(size_t)alive[a] * K + k];
+                radon_short_fill(p, hrec[a], sq.short_threshold, o);
+                if (!o.found) continue;
+                n_lines[alive[a]] = k + 1;
+                hl[b].push_back(RadonLineDev{a, o.q, o.y0, o.s});
+                found_frames[b].push_back(alive[a]);
+                hs[b].push_back(hsig[alive[a]]);
+            }
+            const int nl = (int)hl[b].size();
+            if (!nl) break;
+            hx[b].resize(nl);
+            UHIP(hipMemcpyAsync(s->lnd, hl[b].data(), (size_t)nl * sizeof(RadonLineDev), hipMemcpyHostToDevice, st));
+            k_radon_extent<<<nl, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, s->sigma, sq.min_seg, s->pre, s->cnt, pstride, s->ext);
+            ULAUNCH("k_radon_extent");
+            UHIP(hipMemcpyAsync(hx[b].data(), s->ext, (size_t)nl * sizeof(RadonExtDev), hipMemcpyDeviceToHost, st));
+            pending = k;
+            if (k + 1 == K) break;
+            if (p.wb % 8 == 0) {
+                const dim3 grid(ceil_div(p.wb, RAD_THREADS * 8), ceil_div(p.hb, RADL_ROWS), nl);
+                k_radon_peel<8><<<grid, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, hw, Vs[cur ^ 1], Ms[cur ^ 1]);
+            } else {
+                const dim3 grid(ceil_div(p.wb, RAD_THREADS), ceil_div(p.hb, RADL_ROWS), nl);
+                k_radon_peel<1><<<grid, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, hw, Vs[cur ^ 1], Ms[cur ^ 1]);
+            }
+            ULAUNCH("k_radon_peel");
+            UHIP(hipMemcpyAsync(s->sigma, hs[b].data(), (size_t)nl * sizeof(float), hipMemcpyHostToDevice, st));
+            alive = found_frames[b];
+            cur ^= 1;
+        }
+        if (pending >= 0) {
+            UHIP(hipStreamSynchronize(st));
+            segments(pending);
+        }
+    }
+    if (plain)
+        for (int i = 0; i < n; i++) {
+            memset(&plain[i], 0, sizeof(plain[i]));
+            radon_fill(s, p, hplain[i], plain[i]);
+        }
     return 0;
 }

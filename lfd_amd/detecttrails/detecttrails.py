@@ -218,6 +218,15 @@ class _SkyStage:
         self._handles = {}
 
 
+class _ShortRecord:
+    """a frame's record of ``_RadonStage`` with ``short``: the record it has without (``base``), its short records [K], their
+    n_lines and [(stack record, row)] per found short candidate (empty without ``prof_out``)"""
+    __slots__ = ("base", "recs", "n_lines", "meas")
+
+    def __init__(self, base, recs, n_lines, meas):
+        self.base, self.recs, self.n_lines, self.meas = base, recs, n_lines, meas
+
+
 class _RadonStage:
     """The faint-trail search behind detection for ``DetectTrails(radon=True)`` (include/lfdmi.h: faint-trail search): a
     ``Radon`` handle per (context, shape), kept while it is large enough, and the radon.txt rows.  ``sigma``: the frames' sky
@@ -226,18 +235,39 @@ class _RadonStage:
     gets a row in ``seg_out`` (radon_segments.txt).  ``prof_out`` (radon_profiles.txt; needs ``lines``): every found line's
     segment is measured where the search left the frames (include/lfdmi.h: stacked cross-sections; ``stack_params``) and a frame's
     record is (records [K], n_lines, [(stack record, row)] per found line); with ``defocus_out`` (radon_defocus.txt) the rows
-    added since the last ``flush`` are fitted in one call, as ``_DefocusTee`` does for profiles.txt."""
+    added since the last ``flush`` are fitted in one call, as ``_DefocusTee`` does for profiles.txt.  ``short``: the fields of
+    lfdmi_radon_short_params (steps 10 - 12 of the definition): every frame is also searched by ``Radon.search_short``, whose
+    plain records serve as the frame's one line when ``lines`` is None; a frame's record is then a ``_ShortRecord`` and every
+    found short candidate gets a row in ``short_out`` (radon_short.txt).  With ``prof_out`` the short segments are measured
+    too, and every row of radon_profiles.txt then ends with its source, ``lines`` or ``short`` (the defocus fit stays with the
+    lines' rows)."""
 
     def __init__(self, out, params, sigma, lines=None, lines_params=None, seg_out=None, prof_out=None, stack_params=None,
-                 defocus_out=None, defocus_params=None):
+                 defocus_out=None, defocus_params=None, short=None, short_out=None):
         from ..radon import as_params
         self.out, self.params, self.sigma, self._handles = out, as_params(params), float(sigma), {}
+        self.short, self.short_out = (dict(short) if short is not None else None), short_out
         self.lines, self.seg_out = lines, seg_out
         self.lines_params = dict(lines_params or {}, max_lines=lines) if lines is not None else None
         self.prof_out, self.stack_params = prof_out, dict(stack_params or {})
         self.defocus_out, self.defocus_params, self.pending = defocus_out, defocus_params, []
 
     def _search(self, handle, frames, **where):
+        if self.short is None:
+            return self._search_lines(handle, frames, **where)
+        srecs, snl, plain = handle.search_short(frames, sigma=self.sigma, plain=True, **self.short, **where)
+        base = plain if self.lines is None else self._search_lines(handle, frames, **where)
+        meas = [[] for _ in range(len(snl))]
+        if self.prof_out is not None:
+            from ..stack import segments_from_radon_lines
+            segs, where_ = segments_from_radon_lines(srecs, snl)
+            if len(segs):
+                srec, rows = handle.ctx.stack_profiles(frames, segs, sigma=self.sigma, **where, **self.stack_params)
+                for (j, _), r, row in zip(where_, srec, rows):
+                    meas[j].append((r, row))
+        return [_ShortRecord(base[j], srecs[j], int(snl[j]), meas[j]) for j in range(len(snl))]
+
+    def _search_lines(self, handle, frames, **where):
         if self.lines is None:
             return handle.search(frames, sigma=self.sigma, **where)
         recs, nl = handle.search_lines(frames, sigma=self.sigma, **self.lines_params, **where)
@@ -284,6 +314,16 @@ class _RadonStage:
     def row(self, key, rec):
         """the rows of one frame's record: the line if it was found; with ``lines``, every found line in peel order"""
         from ..radon import format_row, format_segment_row
+        tag = ""
+        if isinstance(rec, _ShortRecord):
+            from ..radon import format_short_row
+            from ..stack import format_row as format_profile_row
+            tag = " lines"
+            for k in range(rec.n_lines):
+                self.short_out.write(format_short_row(key, k, rec.recs[k]) + "\n")
+            for k, (srec, _) in enumerate(rec.meas):
+                self.prof_out.write(format_profile_row(key, k, srec) + " short\n")
+            rec = rec.base
         if self.lines is None:
             if int(rec["found"]):
                 self.out.write(format_row(key, rec) + "\n")
@@ -295,7 +335,7 @@ class _RadonStage:
         if self.prof_out is not None:
             from ..stack import format_row as format_profile_row
             for k, (srec, prow) in enumerate(rec[2]):
-                self.prof_out.write(format_profile_row(key, k, srec) + "\n")
+                self.prof_out.write(format_profile_row(key, k, srec) + tag + "\n")
                 if self.defocus_out is not None:
                     self.pending.append(((*key, k), srec, prow))
 
@@ -303,6 +343,8 @@ class _RadonStage:
         self.out.flush()
         if self.seg_out is not None:
             self.seg_out.flush()
+        if self.short_out is not None:
+            self.short_out.flush()
         if self.prof_out is not None:
             self.prof_out.flush()
         if self.defocus_out is not None:
@@ -653,6 +695,12 @@ class DetectTrails:
     ``defocus=True`` the rows are fitted too (a bank built for the stack's prof_half / step / wing) and written to
     ``radon_defocus_file`` (default ``<savepath>/radon_defocus.txt``): defocus.txt's columns with the line's index after the
     field.  Rank files and resume treat both like radon_segments.txt; every other output stays byte for byte what it is.
+    ``radon_short=True`` or a dict / ``lfd_amd.radon.RadonShortParams`` (needs ``radon=True``): the frames are also searched
+    for short faint trails on every dyadic level (steps 10 - 12 of the definition) and ``radon_short_file`` (default
+    ``<savepath>/radon_short.txt``) gets one row per found candidate: ``run camcol filter field line level strip snr n_pix ex1
+    ey1 ex2 ey2 seg_snr seg_n_pix``; radon.txt and radon_segments.txt stay what they are without it.  With
+    ``radon_profiles=True`` (then ``radon_lines`` may be None) the short segments are measured too, and every row of
+    radon_profiles.txt ends with its source, ``lines`` or ``short``.
     """
 
     _FILTERS = ('u', 'g', 'r', 'i', 'z')
@@ -691,9 +739,17 @@ class DetectTrails:
         self.radon_profiles = bool(kwargs.get("radon_profiles", False))
         self.radon_profiles_file = kwargs.get("radon_profiles_file", os.path.join(save, "radon_profiles.txt"))
         self.radon_defocus_file = kwargs.get("radon_defocus_file", os.path.join(save, "radon_defocus.txt"))
+        self.radon_short_file = kwargs.get("radon_short_file", os.path.join(save, "radon_short.txt"))
+        self.radon_short = None
+        rs = kwargs.get("radon_short", False)
+        if rs is not False and rs is not None:
+            if not self.radon:
+                raise ValueError("radon_short needs radon=True: it is a mode of the faint-trail search")
+            from ..radon import RadonParams, as_short_params
+            self.radon_short = as_short_params(None if rs is True else rs, RadonParams(**self.radon_params).bin)
         self.stack_params = {}
         if self.radon_profiles:
-            if not self.radon or self.radon_lines is None:
+            if not self.radon or (self.radon_lines is None and self.radon_short is None):
                 raise ValueError("radon_profiles=True needs radon=True and radon_lines=K: the segments it measures are theirs")
             from ..stack import as_params as stack_as_params
             self.stack_params = stack_as_params(kwargs.get("stack_params"))
@@ -855,6 +911,7 @@ class DetectTrails:
                 (open(self.radon_file + suffix, "a") if self.radon else contextlib.nullcontext()) as radon_out, \
                 (open(self.radon_segments_file + suffix, "a") if self.radon and self.radon_lines is not None
                  else contextlib.nullcontext()) as segments_out, \
+                (open(self.radon_short_file + suffix, "a") if self.radon_short is not None else contextlib.nullcontext()) as short_out, \
                 (open(self.radon_profiles_file + suffix, "a") if self.radon_profiles else contextlib.nullcontext()) as rprof_out, \
                 (open(self.radon_defocus_file + suffix, "a") if self.radon_profiles and self.defocus
                  else contextlib.nullcontext()) as rdef_out:
@@ -868,7 +925,8 @@ class DetectTrails:
             if self.radon:
                 sigma = _native.make_sky_params(**self.sky_params).target_sigma if self.normalize else 0.025
                 radon = prof_kw["radon"] = _RadonStage(radon_out, self.radon_params, sigma, self.radon_lines, self.radon_lines_params,
-                                                       segments_out, rprof_out, self.stack_params, rdef_out, self.defocus_params)
+                                                       segments_out, rprof_out, self.stack_params, rdef_out, self.defocus_params,
+                                                       self.radon_short, short_out)
             if fresh:
                 progress.write(header + "\n")
                 progress.flush()

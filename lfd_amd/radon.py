@@ -2,7 +2,9 @@
 that are faint in every pixel but long, which the detector cannot see (include/lfdmi.h: faint-trail search).  ``_native.Radon``
 is the device handle; this module holds the parameters, the host conversion of a working line to the frame (usable without a
 device), a one-call helper and the radon.txt format of ``DetectTrails(radon=True)``; for several lines per frame (steps 7 - 9 of
-the definition): ``RadonLinesParams``, the dyadic path, a segment's end points, ``search_lines`` and the radon_segments.txt format.
+the definition): ``RadonLinesParams``, the dyadic path, a segment's end points, ``search_lines`` and the radon_segments.txt format;
+for short trails, scored on every dyadic level (steps 10 - 12): ``RadonShortParams``, ``search_short`` and the radon_short.txt
+format.
 """
 import dataclasses
 import math
@@ -13,10 +15,13 @@ from . import _native
 
 RADON_DTYPE = _native.RADON_DTYPE
 RADON_LINE_DTYPE = _native.RADON_LINE_DTYPE
+RADON_SHORT_DTYPE = _native.RADON_SHORT_DTYPE
 OK, NO_LINE = _native.RADON_OK, _native.RADON_NO_LINE
 DEFAULT_SIGMA = 0.025
 RADON_COLUMNS = ("run", "camcol", "filter", "field", "x1", "y1", "x2", "y2", "snr", "n_pix")
 SEGMENT_COLUMNS = ("run", "camcol", "filter", "field", "line", "ex1", "ey1", "ex2", "ey2", "seg_snr", "seg_n_pix")
+SHORT_COLUMNS = ("run", "camcol", "filter", "field", "line", "level", "strip", "snr", "n_pix", "ex1", "ey1", "ex2", "ey2", "seg_snr",
+                 "seg_n_pix")
 
 
 @dataclasses.dataclass
@@ -104,6 +109,55 @@ def as_lines_params(params, min_len=None):
     return dict(params)
 
 
+@dataclasses.dataclass
+class RadonShortParams:
+    """lfdmi_radon_short_params with its defaults; ``validate`` applies the library's rules without a device (``bin``: the
+    handle's, which bounds ``min_seg`` by min_strip * bin * bin / 2)."""
+    min_strip: int = 64
+    max_lines: int = 4
+    peel_halfwidth: int = 8
+    min_seg: int = 32
+    short_threshold: float = 8.5
+
+    def as_dict(self):
+        return dataclasses.asdict(self)
+
+    def validate(self, bin=None):
+        for name in ("min_strip", "max_lines", "peel_halfwidth", "min_seg"):
+            if int(getattr(self, name)) != getattr(self, name):
+                raise ValueError(f"{name} must be an integer")
+        if self.min_strip < 64 or self.min_strip & (self.min_strip - 1):
+            raise ValueError("min_strip must be a power of two >= 64")
+        if not 1 <= self.max_lines <= _native.RADON_MAX_LINES:
+            raise ValueError("max_lines must be 1 .. %d" % _native.RADON_MAX_LINES)
+        if self.peel_halfwidth < 0:
+            raise ValueError("peel_halfwidth must be >= 0")
+        if self.min_seg < 1 or (bin is not None and self.min_seg > self.min_strip * bin * bin // 2):
+            raise ValueError("min_seg must be 1 .. min_strip * bin * bin / 2")
+        if not (math.isfinite(self.short_threshold) and self.short_threshold > 0):
+            raise ValueError("short_threshold must be finite and positive")
+        return self
+
+
+def default_short_params():
+    """lfdmi_default_radon_short_params as a RadonShortParams (read from the library: no GPU needed)."""
+    p = _native.make_radon_short_params()
+    return RadonShortParams(**{k: getattr(p, k) for k, _ in _native.RadonShortParamsStruct._fields_ if k != "pad"})
+
+
+def as_short_params(params, bin=None):
+    """None / dict / RadonShortParams -> validated dict of lfdmi_radon_short_params fields"""
+    if params is None:
+        return {}
+    if isinstance(params, RadonShortParams):
+        return params.validate(bin).as_dict()
+    unknown = set(params) - {f.name for f in dataclasses.fields(RadonShortParams)}
+    if unknown:
+        raise TypeError(f"unknown radon short parameter {sorted(unknown)[0]!r}")
+    RadonShortParams(**params).validate(bin)
+    return dict(params)
+
+
 def working_dims(shape, bin):
     """(Hb, Wb, P of orientations 0 and 1, P of orientations 2 and 3)"""
     h, w = int(shape[0]), int(shape[1])
@@ -183,6 +237,19 @@ def search_lines(ctx, frames, sigma=None, **params):
         return r.search_lines(arr, sigma=sigma, **lp)
 
 
+def search_short(ctx, frames, sigma=None, **params):
+    """Search (n, h, w) or (h, w) frames on ``ctx`` for short trails: (RADON_SHORT_DTYPE records [n, max_lines], n_lines [n]).
+    ``params``: fields of RadonParams and of RadonShortParams.  The handle is created and destroyed per call."""
+    snames = {f.name for f in dataclasses.fields(RadonShortParams)}
+    rp = as_params({k: v for k, v in params.items() if k not in snames})
+    sp = as_short_params({k: v for k, v in params.items() if k in snames}, rp.get("bin", RadonParams.bin))
+    arr = frames if _native._is_dev(frames) or isinstance(frames, _native.DeviceFrames) else np.asarray(frames)
+    shp = tuple(arr.shape)
+    n, h, w = (1, *shp) if len(shp) == 2 else shp
+    with _native.Radon(ctx, (h, w), max_frames=max(1, min(n, ctx.max_inflight)), **rp) as r:
+        return r.search_short(arr, sigma=sigma, **sp)
+
+
 def search_frames(ctx, frames, sigma=None, **params):
     """Search (n, h, w) or (h, w) frames on ``ctx``: RADON_DTYPE records, one per frame.  For repeated calls keep a
     ``_native.Radon`` handle instead: this one is created and destroyed per call."""
@@ -232,5 +299,28 @@ def read_segments(path):
             r = {}
             for k, v in zip(SEGMENT_COLUMNS, parts):
                 r[k] = v if k == "filter" else int(v) if k in ("run", "camcol", "field", "line", "seg_n_pix") else float(v)
+            rows.append(r)
+    return rows
+
+
+def format_short_row(meta, line, rec):
+    """One radon_short.txt row: meta = (run, camcol, filter, field), line = the record's place in peel order; floats with repr."""
+    return " ".join(str(v) for v in (*meta, int(line), int(rec["level"]), int(rec["strip"]), repr(float(rec["snr"])), int(rec["n_pix"]),
+                                      repr(float(rec["ex1"])), repr(float(rec["ey1"])), repr(float(rec["ex2"])),
+                                      repr(float(rec["ey2"])), repr(float(rec["seg_snr"])), int(rec["seg_n_pix"])))
+
+
+def read_short(path):
+    """radon_short.txt (rows only, no header line) -> list of dicts keyed by SHORT_COLUMNS."""
+    ints = ("run", "camcol", "field", "line", "level", "strip", "n_pix", "seg_n_pix")
+    rows = []
+    with open(path) as f:
+        for ln in f:
+            parts = ln.split()
+            if not parts:
+                continue
+            r = {}
+            for k, v in zip(SHORT_COLUMNS, parts):
+                r[k] = v if k == "filter" else int(v) if k in ints else float(v)
             rows.append(r)
     return rows

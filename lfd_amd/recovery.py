@@ -1,7 +1,7 @@
 """Injection and recovery: add model trails of known line and brightness to frames, detect, and count what comes back -- the
 detector's efficiency as a function of the trail's peak (include/lfdmi.h: trail injection).
 
-    python -m lfd_amd.recovery --synth K0:N --peaks 0.05,0.1,0.2,5 --out DIR [--detector radon]
+    python -m lfd_amd.recovery --synth K0:N --peaks 0.05,0.1,0.2,5 --out DIR [--detector radon | radon-short] [--length-frac F]
 
 The plan (``draw_trails``), the matching (``match``) and the rows use integer RNG draws and IEEE + - * / sqrt only -- cos and sin
 come from ``cos_sin`` below, a fixed sequence of multiplications and additions -- so every machine draws the same plan and
@@ -64,6 +64,27 @@ def draw_trails(n_frames, shape, seed, peaks, length=None):
         tm = (x0 - plan["rho"] * c) * -s + (y0 - plan["rho"] * s) * c
         plan["t0"], plan["t1"] = tm - 0.5 * float(length), tm + 0.5 * float(length)
     return plan
+
+
+def shorten(plan, shape, frac, seed):
+    """The plan with every trail cut to the fraction ``frac`` of its crossing of the frame, at a random place along it: with
+    (ta, tb) the trail's extent inside the frame, t0 = ta + u (1 - frac) (tb - ta) and t1 = t0 + frac (tb - ta), u = an integer draw / 2^20
+    from a stream of its own (seeded by (seed, 1)), so ``draw_trails`` draws what it always drew.  frac = 1: the plan
+    itself."""
+    frac = float(frac)
+    if not 0.0 < frac <= 1.0:
+        raise ValueError("length_frac must be in (0, 1]")
+    if frac == 1.0:
+        return plan
+    out = np.array(plan, PLAN_DTYPE)
+    u = np.random.default_rng(np.random.PCG64([int(seed), 1])).integers(0, 1 << 20, len(out)).astype(np.float64) / float(1 << 20)
+    for i in range(len(out)):
+        ta, tb = extent(float(out["rho"][i]), float(out["theta"][i]), float(out["t0"][i]), float(out["t1"][i]), shape)
+        if ta > tb:
+            continue
+        out["t0"][i] = ta + u[i] * (1.0 - frac) * (tb - ta)
+        out["t1"][i] = out["t0"][i] + frac * (tb - ta)
+    return out
 
 
 def plan_checksum(plan):
@@ -172,15 +193,16 @@ def radon_records(lines):
 
 
 def run(ctx, frames, cats, rs, trails, tables, table_step, params_bright=None, params_dim=None, subsample=4, profiles=False,
-        k=K_MATCH, detector="hough", radon_params=None, sigma=None):
+        k=K_MATCH, detector="hough", radon_params=None, sigma=None, short_params=None):
     """Copy ``frames`` ((n, h, w) float32 numpy or torch CUDA), inject the plan ``trails`` (tables of peak 1: see
     ``inject.normalise_peak``), run ``detect_batch`` and match: ROW_DTYPE rows, one per trail.  cats: the frames' catalogues
     (a list of dicts, a packed dict or None) and rs their remove_stars parameters; profiles=True also runs ``measure_trails``
     and fills fwhm.  detector="radon": the stars are removed (``remove_stars``) and the faint-trail search
     (include/lfdmi.h: faint-trail search; ``radon_params``, ``sigma``) takes the detector's place; its line is matched by the
-    same rule, with params_bright's houghMethod as the cell."""
-    if detector not in ("hough", "radon"):
-        raise ValueError("detector: 'hough' or 'radon'")
+    same rule, with params_bright's houghMethod as the cell.  detector="radon-short": the short-trail search (steps 10 - 12
+    of that definition; ``short_params``) instead, and the parent line of a frame's first record is matched."""
+    if detector not in ("hough", "radon", "radon-short"):
+        raise ValueError("detector: 'hough', 'radon' or 'radon-short'")
     from .catalogs import pack_catalogs
     from .detecttrails import default_params
     pb, pd, _ = default_params()
@@ -190,12 +212,17 @@ def run(ctx, frames, cats, rs, trails, tables, table_step, params_bright=None, p
     n, h, w = work.shape
     packed = pack_catalogs(list(cats)) if isinstance(cats, (list, tuple)) else cats
     ctx.inject_trails(work, to_inject(trails), np.asarray(tables, np.float32), table_step, subsample=subsample)
-    if detector == "radon":
+    if detector in ("radon", "radon-short"):
         from . import radon as _radon
         if packed is not None:
             ctx.remove_stars(work, packed, rs)
-        with _native.Radon(ctx, (h, w), max_frames=min(n, 16), **_radon.as_params(radon_params)) as search:
-            lines = search.search(work, sigma=sigma)
+        rp = _radon.as_params(radon_params)
+        with _native.Radon(ctx, (h, w), max_frames=min(n, 16), **rp) as search:
+            if detector == "radon":
+                lines = search.search(work, sigma=sigma)
+            else:
+                sp = _radon.as_short_params(short_params, rp.get("bin", _radon.RadonParams.bin))
+                lines = search.search_short(work, sigma=sigma, **sp)[0][:, 0]
         return make_rows(radon_records(lines), trails, pb, pd, (h, w), k=k)
     recs = ctx.detect_batch(work, pb, pd, packed, rs if packed is not None else None)
     measured = None
@@ -273,9 +300,12 @@ def main(argv=None):
     ap.add_argument("--sigma", type=float, default=2.0, help="Gaussian cross-section sigma in px")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--profiles", action="store_true", help="also measure the recovered trails' fwhm")
-    ap.add_argument("--detector", choices=("hough", "radon"), default="hough",
-                    help="hough: the detector (default); radon: the faint-trail search in its place")
-    ap.add_argument("--bin", type=int, default=None, help="--detector radon: lfdmi_radon_params.bin")
+    ap.add_argument("--detector", choices=("hough", "radon", "radon-short"), default="hough",
+                    help="hough: the detector (default); radon: the faint-trail search in its place; radon-short: its "
+                         "short-trail search, matched by the candidate's parent line")
+    ap.add_argument("--bin", type=int, default=None, help="--detector radon / radon-short: lfdmi_radon_params.bin")
+    ap.add_argument("--length-frac", type=float, default=1.0,
+                    help="inject every trail over this fraction of its crossing, at a random place along it (default 1: the whole crossing)")
     a = ap.parse_args(argv)
     k0, n = (int(v) for v in a.synth.split(":"))
     peaks = [float(v) for v in a.peaks.split(",")]
@@ -287,7 +317,7 @@ def main(argv=None):
     pb, pd, prs = default_params()
     rs = _native.make_rs_params("r", **{k: v for k, v in prs.items() if k != "debug"})
     table, step = _inject.gaussian_table(a.sigma)
-    plan = draw_trails(len(keep), frames.shape[1:], a.seed, peaks)
+    plan = shorten(draw_trails(len(keep), frames.shape[1:], a.seed, peaks), frames.shape[1:], a.length_frac, a.seed)
     with _native.Context(0, frames.shape[1], frames.shape[2], 16) as ctx:
         rows = run(ctx, frames, cats, rs, plan, _inject.normalise_peak(table), step, pb, pd, profiles=a.profiles,
                    detector=a.detector, radon_params={"bin": a.bin} if a.bin else None)

@@ -3,11 +3,15 @@ between HIP events, beside the bytes each kernel has to move (the rows a level s
 16-bit counts) and the floor those bytes give at the copy rate the project quotes (4.8 TB/s, DESIGN.md: sky normalisation).
 Writes profiles/radon_probe.json.
 
-    python tools/radon_probe.py [--reps 5] [--frames 256] [--max-frames 16] [--out FILE] [--trace] [--lines K]
+    python tools/radon_probe.py [--reps 5] [--frames 256] [--max-frames 16] [--out FILE] [--trace] [--lines K] [--short]
 
 --lines K  also times lfdmi_radon_search_lines(max_lines=K) on the same frames with one faint streak added to every second
            frame: ms per call and per round (a frame runs one round more than it has found lines, K at the most), beside the
            plain search's time
+
+--short    also times lfdmi_radon_search_short(max_lines=K) in the same run on the same frames and settings (K of --lines,
+           4 without it): ms per call and per frame-round, and the ratio of its frame-round to search_lines' frame-round,
+           which is the yardstick: the scoring levels move the same bytes, so the ratio shows what the scores cost
 
 --trace  one more run per bin under `rocprofv3 --kernel-trace --stats` -> profiles/radon_probe_kernel_stats_bin<b>.csv
 Every GPU step is a child process under its own `timeout`.
@@ -80,6 +84,23 @@ def child(a):
                 lines = {"lines_max": a.lines, "lines_ms_per_call": lmed, "lines_ms_all": lms, "lines_found": int(nl.sum()),
                          "lines_frame_rounds": rounds, "lines_ms_per_frame_round": lmed / rounds,
                          "plain_ms_per_call": float(np.median(ms)), "bytes_with_lines": r.dims()[2]}
+            if a.short:
+                srecs, snl = r.search_short(frames, max_lines=a.lines)    # warm-up: the partial records
+                sms = []
+                for _ in range(a.reps):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    srecs, snl = r.search_short(frames, max_lines=a.lines)
+                    e1.record()
+                    e1.synchronize()
+                    sms.append(e0.elapsed_time(e1))
+                srounds = int(np.minimum(snl + 1, a.lines).sum())
+                smed = float(np.median(sms))
+                lines.update({"short_ms_per_call": smed, "short_ms_all": sms, "short_found": int(snl.sum()),
+                              "short_frame_rounds": srounds, "short_ms_per_frame_round": smed / srounds,
+                              "short_over_lines_per_frame_round": smed / srounds / lines["lines_ms_per_frame_round"],
+                              "short_levels": sorted({int(v) for v in srecs["level"][srecs["status"] == 0]}),
+                              "bytes_with_short": r.dims()[2]})
             kb = kernel_bytes(SHAPE, b)
             total = float(sum(kb.values())) * a.frames
             med = float(np.median(ms))
@@ -107,18 +128,22 @@ def main():
     ap.add_argument("--max-frames", type=int, default=16)
     ap.add_argument("--bin", type=int, default=0)
     ap.add_argument("--lines", type=int, default=0)
+    ap.add_argument("--short", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "radon_probe.json"))
     ap.add_argument("--child", action="store_true")
     a = ap.parse_args()
+    if a.short and not a.lines:
+        a.lines = 4
     if a.child:
         child(a)
         return
-    common = ["--frames", str(a.frames), "--max-frames", str(a.max_frames), "--lines", str(a.lines)]
+    common = ["--frames", str(a.frames), "--max-frames", str(a.max_frames), "--lines", str(a.lines)] + (["--short"] if a.short else [])
     doc = {"tool": "tools/radon_probe.py", "copy_rate_TBps": COPY_RATE / 1e12,
            "runs": run_child(common + ["--reps", str(a.reps)], 500)}
     for r in doc["runs"]:
         print({k: r[k] for k in ("bin", "ms_per_call", "ms_floor_at_4.8_TBps", "x_the_floor", "lines_ms_per_call",
-                                 "lines_ms_per_frame_round", "lines_found") if k in r}, flush=True)
+                                 "lines_ms_per_frame_round", "lines_found", "short_ms_per_call",
+                                 "short_ms_per_frame_round", "short_found", "short_over_lines_per_frame_round") if k in r}, flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(doc, f, indent=1)
