@@ -982,6 +982,83 @@ int lfdmi_stack_profiles(lfdmi_ctx *ctx, const void *frames, int dtype, int n, i
                          int n_seg, const float *sigma, const lfdmi_stack_params *p, lfdmi_stack *out, float *profiles, float *sums,
                          int32_t *counts);
 
+/* ---- source finder ------------------------------------------------------------------------------------------------------------
+ * remove_stars blots the sources a photoObj table lists; a frame that has no such table (a raw exposure, an fpC file, another
+ * survey's frame) gets its catalogue from here: the compact sources of the frame itself, as an lfdmi_catalog the existing
+ * remove_stars path takes unchanged.  The reference has no such step.  The procedure below is the definition;
+ * tests/stars_ref.py restates it in numpy and the device matches it bit for bit: every float32 sum has a fixed order, every
+ * other statistic is a comparison or a maximum.
+ *
+ * Input: frame x of H x W float32 in buffer rows (not flipped: what remove_stars sees), pixel (y, c) = x[y][c].  sigma: the sky
+ * sigma of the frame (NULL: 0.025f for every frame).  A non-finite pixel and a pixel outside the frame count as +0 in every step.
+ * (Frames whose 3 x 3 sums overflow float32 are outside the definition.)
+ *
+ * 1. Smoothing.  h[y][c] = (x[y][c-1] + x[y][c]) + x[y][c+1] and S[y][c] = (h[y-1][c] + h[y][c]) + h[y+1][c], float32, every
+ *    addition rounded.
+ * 2. Candidates.  T = (float)(k_det * 3.0 * (double)sigma): k_det sigmas of S on a flat sky, whose 9 pixels add to 3 sigma.
+ *    Pixel p is a candidate when, over the window |dy| <= sep, |dx| <= sep clipped to the frame, S[p] >= T, S[p] > S[q] for every
+ *    window pixel q before p in raster order and S[p] >= S[q] for every window pixel q after p: a tie goes to the first pixel in
+ *    raster order, and a flat plateau yields only its leading pixels.
+ * 3. Order and cap.  A frame's candidates are numbered in raster order (y, then c); the first max_obj are reported.  The frame
+ *    record carries n_found (all candidates), n_out = min(n_found, max_obj) and the status LFDMI_STARS_OK or
+ *    LFDMI_STARS_TRUNCATED (n_found > max_obj).
+ * 4. Radius.  E = max((float)(edge_frac * (double)S[p]), (float)(k_edge * 3.0 * (double)sigma)).  For r = 1 .. r_max, M_r = the
+ *    maximum of S over the frame's pixels at Chebyshev distance r from p (-inf when there is none).  rad = the smallest r with
+ *    M_r < E; if there is none the candidate is LFDMI_STAR_EXTENDED and rad = 0 (a trail crosses every ring, so its ridge maxima
+ *    end here, and so do bleed columns and galaxies larger than r_max).  LFDMI_STAR_EDGE: the square |d| <= rad is clipped by the
+ *    frame.
+ * 5. Measurement over the square |dy|, |dx| <= rad clipped to the frame (an extended candidate: the peak pixel alone), v = the
+ *    pixel.  Per row, float32, dx ascending from +0: a_y = sum v, b_y = sum (v * (float)dx), each product rounded and then added
+ *    (no FMA).  Then in double, dy ascending from 0: F = sum a_y, MX = sum b_y, MY = sum (double)dy * (double)a_y.  flux =
+ *    (float)F; if F > 0, xc = (float)(px + MX / F) and yc = (float)(py + MY / F), otherwise the peak's x and y.
+ * 6. Record.  lfdmi_star below; s_peak = S[p].
+ * 7. Parameters.  lfdmi_stars_params below.
+ * 8. Catalogue (lfdmi_stars_catalog).  max_obj rows per frame, count = n_out.  A row without LFDMI_STAR_EXTENDED: nobserve =
+ *    ndetect = 1; the five psfmag 0 (under every filter cap, every pair difference 0); the five petro90 = (float)((double)rad *
+ *    pixscale); the five colc = (float)y and the five rowc = (float)x -- remove_stars takes ceil(COLC) on axis 0, so the row goes
+ *    into colc.  With the default params_removestars the blotted square then has half-width int(ceil(rad * 0.396) / 0.396) + 10:
+ *    at least rad + 10 and at most 42, under maxxy = 60 for rad <= 32.  A row with LFDMI_STAR_EXTENDED: nobserve = 0, ndetect = 1,
+ *    so it is never blotted.  Rows past count are zero, but for ndetect = 1.  remove_stars slices img[x-d : x+d] as Python does:
+ *    a start below zero counts from the far edge and the slice is empty, so a source closer than its half-width d (rad + 10 or
+ *    more) to the top or the left edge of the buffer is not blotted -- with this catalogue as with a photoObj one.
+ *
+ * The device reads a frame once per 64 x 16 tile with a halo of sep + 1 (k_stars_detect: 4 H W bytes per frame is the floor), keeps
+ * one bit per pixel, ranks the bits by a scan over the rows (k_stars_rows) and measures one source per workgroup from a
+ * (2 r_max + 3)^2 patch in LDS (k_stars_measure); k_stars_catalog is step 8.  No kernel uses an atomic or a transcendental. */
+#define LFDMI_STARS_MAX_OBJ 1048576
+enum { LFDMI_STARS_OK = 0, LFDMI_STARS_TRUNCATED = 1 };
+enum { LFDMI_STAR_EXTENDED = 1, LFDMI_STAR_EDGE = 2 };
+typedef struct {
+    double k_det;             /* detection threshold in sigmas of S (> 0); default 5 */
+    double k_edge;            /* a source ends where its rings fall below k_edge sigmas of S (> 0); default 3 */
+    double edge_frac;         /* ... or below this share of its peak, whichever is higher (0 .. 1); default 0.02 */
+    int32_t sep;              /* half-width of the local-maximum window (1 .. 8); default 3 */
+    int32_t r_max;            /* largest radius (1 .. 32); default 32 */
+    int32_t max_obj;          /* records per frame (1 .. LFDMI_STARS_MAX_OBJ); default 4096 */
+} lfdmi_stars_params;
+typedef struct {
+    int32_t x, y;             /* the peak: column and row of the buffer */
+    int32_t rad;              /* 1 .. r_max, 0 for an extended candidate */
+    int32_t flags;            /* LFDMI_STAR_* */
+    float s_peak, flux, xc, yc;
+} lfdmi_star;
+typedef struct {
+    int32_t status;           /* LFDMI_STARS_* */
+    int32_t n_found, n_out;
+} lfdmi_stars_frame;
+void lfdmi_default_stars_params(lfdmi_stars_params *out);
+/* frames: n frames of h x w, LFDMI_F32 or LFDMI_F32_BE, loc LFDMI_HOST / LFDMI_HOST_PINNED / LFDMI_DEVICE; only read.  sigma: n
+ * float32 (host), > 0; NULL: 0.025.  p NULL: the defaults.  out_records: n x max_obj records at out_loc (host or device), rows past
+ * n_out zero; frame_records: n records (host).  Out-of-range parameters, a sigma that is not positive: LFDMI_ERR_ARG, and nothing
+ * runs.  The call keeps no state (its device memory comes from the stream's pool and goes back before it returns), refuses while
+ * calls are in flight, runs on the context's stream and waits for it twice per chunk of frames. */
+int lfdmi_find_stars(lfdmi_ctx *ctx, const void *frames, int dtype, int n, int h, int w, int loc, const float *sigma,
+                     const lfdmi_stars_params *p, lfdmi_star *out_records, int out_loc, lfdmi_stars_frame *frame_records);
+/* step 8: fills the arrays cat points at ([n][max_obj][5] / [n][max_obj] / count [n], in host or device memory as cat->loc says;
+ * cat->max_obj == max_obj) from n x max_obj records at rec_loc and the n frame records (host).  n at most 32768. */
+int lfdmi_stars_catalog(lfdmi_ctx *ctx, const lfdmi_star *records, int rec_loc, const lfdmi_stars_frame *frame_records, int n,
+                        int max_obj, double pixscale, const lfdmi_catalog *cat);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,6 +44,7 @@ SYMBOLS = (
     "lfdmi_default_radon_lines_params", "lfdmi_radon_search_lines",
     "lfdmi_default_radon_short_params", "lfdmi_radon_search_short",
     "lfdmi_default_stack_params", "lfdmi_stack_profiles",
+    "lfdmi_default_stars_params", "lfdmi_find_stars", "lfdmi_stars_catalog",
 )
 
 
@@ -276,6 +277,27 @@ def stack_bins(p):
     return 2 * int(round(p.prof_half / p.step)) + 1
 
 
+class StarsParamsStruct(C.Structure):
+    """lfdmi_stars_params (include/lfdmi.h: source finder)."""
+    _fields_ = [("k_det", C.c_double), ("k_edge", C.c_double), ("edge_frac", C.c_double),
+                ("sep", C.c_int32), ("r_max", C.c_int32), ("max_obj", C.c_int32)]
+
+
+# lfdmi_star: one record per source of lfdmi_find_stars; lfdmi_stars_frame: one per frame
+STAR_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("rad", "<i4"), ("flags", "<i4"),
+                       ("s_peak", "<f4"), ("flux", "<f4"), ("xc", "<f4"), ("yc", "<f4")])
+STARS_FRAME_DTYPE = np.dtype([("status", "<i4"), ("n_found", "<i4"), ("n_out", "<i4")])
+STARS_OK, STARS_TRUNCATED = 0, 1
+STAR_EXTENDED, STAR_EDGE = 1, 2
+STARS_MAX_OBJ = 1048576
+CATALOG_KEYS5 = ("ROWC", "COLC", "PSFMAG", "PETROTH90")
+
+
+def make_stars_params(**params):
+    """lfdmi_default_stars_params with the given fields replaced (unknown names raise)."""
+    return _make_params(StarsParamsStruct, "lfdmi_default_stars_params", "stars", params)
+
+
 def make_radon_params(**params):
     """lfdmi_default_radon_params with the given fields replaced (unknown names raise)."""
     return _make_params(RadonParamsStruct, "lfdmi_default_radon_params", "radon", params)
@@ -357,6 +379,11 @@ def lib():
         _lib.lfdmi_default_stack_params.argtypes = [C.c_void_p]
         _lib.lfdmi_stack_profiles.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.lfdmi_default_stars_params.restype = None
+        _lib.lfdmi_default_stars_params.argtypes = [C.c_void_p]
+        _lib.lfdmi_find_stars.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_int, C.c_void_p]
+        _lib.lfdmi_stars_catalog.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p]
     return _lib
 
 
@@ -1081,6 +1108,56 @@ class Context:
         self._chk(self._lib.lfdmi_stack_profiles(self._h, _ptr(frames), code, n, h, w, loc, _ptr(sg), len(sg), _ptr(sig), C.byref(p),
                                                  _ptr(out), _ptr(prof), _ptr(sums), _ptr(cnts)))
         return (out, prof, sums, cnts) if raw else (out, prof)
+
+    # -- source finder (lfdmi_find_stars / lfdmi_stars_catalog) ---------------------------------------------------------------------
+    def find_stars(self, frames, sigma=None, pinned=False, native_device=False, device_out=False, **params):
+        """The compact sources of every frame (include/lfdmi.h: source finder).  frames: what ``stack_profiles`` takes, only read;
+        sigma: None (0.025), a number or one value per frame.  Returns (STAR_DTYPE records [n, max_obj], STARS_FRAME_DTYPE records
+        [n]); with device_out=True the records stay on the device (a torch uint8 tensor [n, max_obj, 32]) for ``stars_catalog``."""
+        frames, code, n, h, w, loc = self._frames(frames, pinned, "find_stars", native_device=native_device)
+        p = make_stars_params(**params)
+        sig = _sigma(sigma, n)
+        frec = np.zeros(n, STARS_FRAME_DTYPE)
+        m = max(1, min(int(p.max_obj), STARS_MAX_OBJ))
+        if device_out:
+            import torch
+            rec = torch.empty((n, m, STAR_DTYPE.itemsize), dtype=torch.uint8, device=f"cuda:{self.device}")   # (the library writes every byte)
+        else:
+            rec = np.zeros((n, m), STAR_DTYPE)
+        self._chk(self._lib.lfdmi_find_stars(self._h, _ptr(frames), code, n, h, w, loc, _ptr(sig), C.byref(p), _ptr(rec),
+                                             DEVICE if device_out else HOST, _ptr(frec)))
+        return rec, frec
+
+    def stars_catalog(self, records, frame_records, pixscale=0.396, device=False):
+        """Step 8 of the source finder: the catalogue dict ``synth.pack_catalogs`` returns (count, ROWC, COLC, PSFMAG, PETROTH90,
+        NOBSERVE, NDETECT), filled on the device from the records of ``find_stars`` (numpy, or its device tensor); device=True:
+        torch CUDA arrays, which ``detect_batch`` and ``remove_stars`` take in place."""
+        frec = np.ascontiguousarray(frame_records, STARS_FRAME_DTYPE).reshape(-1)
+        n = len(frec)
+        if _is_dev(records):
+            m = int(records.shape[1])
+        else:
+            records = np.ascontiguousarray(records, STAR_DTYPE).reshape(n, -1)
+            m = records.shape[1]
+        if device:
+            import torch
+            dev = f"cuda:{self.device}"
+            # (torch.empty: the library writes every row and count on its own stream; a fill kernel on torch's stream would race it)
+            cat = {"count": torch.empty(n, dtype=torch.int32, device=dev)}
+            for k in CATALOG_KEYS5:
+                cat[k] = torch.empty((n, m, 5), dtype=torch.float32, device=dev)
+            for k in ("NOBSERVE", "NDETECT"):
+                cat[k] = torch.empty((n, m), dtype=torch.int32, device=dev)
+        else:
+            cat = {"count": np.zeros(n, np.int32)}
+            for k in CATALOG_KEYS5:
+                cat[k] = np.zeros((n, m, 5), np.float32)
+            for k in ("NOBSERVE", "NDETECT"):
+                cat[k] = np.zeros((n, m), np.int32)
+        c, keep = self._catalog(cat)
+        self._chk(self._lib.lfdmi_stars_catalog(self._h, _ptr(records), DEVICE if _is_dev(records) else HOST, _ptr(frec), n, m,
+                                                float(pixscale), C.byref(c)))
+        return cat
 
     def pinned_buffer(self, nbytes):
         """Page-locked host memory next to this context's GPU (lfdmi_host_alloc) as a ``PinnedBuffer``."""

@@ -62,8 +62,14 @@ class BatchDetector:
     """
 
     def __init__(self, device=0, shape=(1489, 2048), inflight=32, stream=None, lanes=1, caps=None, stage_images=False,
-                 calls_in_flight=1, sky=None):
-        """sky: None, or a dict of lfdmi_sky_params fields ({} = the defaults): ``detect`` / ``submit`` / ``multiscale`` then
+                 calls_in_flight=1, sky=None, stars=None):
+        """stars: None, or a dict of lfdmi_stars_params fields ({} = the defaults): ``detect`` / ``submit`` called without
+        ``catalogs`` then find each frame's compact sources first (include/lfdmi.h: source finder) and hand the device-resident
+        catalogue built from them to the call; after ``sky=`` the normalised buffer is searched, with sigma = target_sigma.
+        ``last_stars`` holds the frame records of the last call.  An explicit ``catalogs=`` wins.  Needs lanes == 1 and
+        calls_in_flight == 1.  Host frames without ``sky=`` are uploaded twice (by the finder, then by the detect call, which
+        blots the caller's array): keep frames on the device where that matters.
+        sky: None, or a dict of lfdmi_sky_params fields ({} = the defaults): ``detect`` / ``submit`` / ``multiscale`` then
         first normalise the frames into a ``Sky`` handle's device buffer (include/lfdmi.h: sky normalisation) and work on that
         buffer, ``measure_trails`` measures it, and ``last_sky`` holds the records of the last call.  Needs lanes == 1 and
         calls_in_flight == 1."""
@@ -72,6 +78,11 @@ class BatchDetector:
         self.calls_in_flight = max(1, int(calls_in_flight))
         if self.calls_in_flight > 1 and self.lanes > 1:
             raise ValueError("calls_in_flight > 1 needs lanes == 1")
+        if stars is not None:                              # (checked before any context exists)
+            if self.lanes != 1 or self.calls_in_flight != 1:
+                raise ValueError("stars= needs lanes == 1 and calls_in_flight == 1")
+            from .stars import as_params as stars_params
+            stars = stars_params(stars)
         per = max(1, inflight // self.lanes)
         self.ctxs = [_native.Context(device, shape[0], shape[1], per, caps=caps) for _ in range(self.lanes * self.calls_in_flight)]
         for c in self.ctxs:  # a batch detector is for throughput: no 8-bit debug images per frame unless asked for
@@ -102,6 +113,25 @@ class BatchDetector:
                 raise ValueError("sky= needs lanes == 1 and calls_in_flight == 1")
             from .sky import as_params
             self.sky = _native.Sky(self.ctx, shape, max_frames=per, **as_params(sky))
+        self.stars, self.last_stars = None, None
+        if stars is not None:
+            self.stars = stars
+            self._stars_sigma = None if self.sky is None else float(_native.make_sky_params(**as_params(sky)).target_sigma)
+
+    # ---- the source finder in front of a call without catalogues (stars=...) ------------------------------------------------------
+    def _finds(self, catalogs, rs):
+        """whether this call's catalogue comes from the finder"""
+        if self.stars is None or catalogs is not None:
+            return False
+        if rs is None:
+            raise ValueError("stars=: the call needs rs (remove_stars' parameters) to blot what the finder finds")
+        return True
+
+    def _found_catalog(self, frames, rs):
+        """(device-resident catalogue of the frames' sources, frame records); the squares use rs.pixscale"""
+        self._drain()
+        rec, frec = self.ctx.find_stars(frames, sigma=self._stars_sigma, device_out=True, **self.stars)
+        return self.ctx.stars_catalog(rec, frec, rs.pixscale, device=True), frec
 
     # ---- sky normalisation in front of every call (sky=...) ------------------------------------------------------------------
     def _drain(self):
@@ -148,6 +178,8 @@ class BatchDetector:
     def _in_turn(self, method, args):
         if self.sky is not None:
             raise RuntimeError("detect_async / multiscale_async are not routed through sky=: use detect / submit")
+        if self.stars is not None:
+            raise RuntimeError("detect_async / multiscale_async are not routed through stars=: use detect / submit")
         if self._turn_pool is None:
             raise RuntimeError("BatchDetector(calls_in_flight=1): use detect / multiscale")
         i = self._turn
@@ -202,7 +234,11 @@ class BatchDetector:
                 raise ValueError("submit with sky=: at most `inflight` frames per call (the handle's buffer)")
             buf, self.last_sky = self._normalized(frames, 0, frames.shape[0], pinned=pinned)
             self._sky_src = frames
+            if self._finds(catalogs, rs):
+                catalogs, self.last_stars = self._found_catalog(buf, rs)
             return self._submit_ctx().detect_batch_begin(buf, params_bright, params_dim, catalogs, rs)
+        if self._finds(catalogs, rs):
+            catalogs, self.last_stars = self._found_catalog(frames, rs)
         return self._submit_ctx().detect_batch_begin(frames, params_bright, params_dim, catalogs, rs, pinned=pinned)
 
     def submit_multiscale(self, frames, params, rhos, dim=True, flip=True, after_bright=False):
@@ -274,9 +310,22 @@ class BatchDetector:
         """frames: (n, h, w) float32, numpy (staged through the library) or a torch CUDA tensor
         (used in place; must be complete on the device before the call when lanes > 1).
         catalogs: dict from synth.pack_catalogs (numpy or torch CUDA tensors)."""
+        find = self._finds(catalogs, rs)
         if self.sky is not None:
-            return np.concatenate(self._sky_chunks(frames, lambda buf, a, b: self.ctx.detect_batch(
-                buf, params_bright, params_dim, self._slice_cat(catalogs, a, b), rs)))
+            found = []
+
+            def call(buf, a, b):
+                cat = self._slice_cat(catalogs, a, b)
+                if find:
+                    cat, frec = self._found_catalog(buf, rs)
+                    found.append(frec)
+                return self.ctx.detect_batch(buf, params_bright, params_dim, cat, rs)
+            out = np.concatenate(self._sky_chunks(frames, call))
+            if find:
+                self.last_stars = np.concatenate(found)
+            return out
+        if find:
+            catalogs, self.last_stars = self._found_catalog(frames, rs)
         if self.lanes == 1:
             if self._turn_pool is not None and self._busy():
                 return self.detect_async(frames, params_bright, params_dim, catalogs, rs).result()

@@ -218,6 +218,39 @@ class _SkyStage:
         self._handles = {}
 
 
+class _StarsStage:
+    """The source finder in front of detection for ``DetectTrails(find_stars=True)`` (include/lfdmi.h: source finder): each
+    chunk's catalogue comes from the frames themselves (after the sky normalisation when that is on), and stars.txt gets a row
+    per frame.  ``sigma``: the frames' sky sigma (target_sigma of the sky normalisation when that ran, else 0.025)."""
+
+    def __init__(self, out, params, sigma):
+        from ..stars import as_params
+        self.out, self.params, self.sigma = out, as_params(params), float(sigma)
+
+    def batch(self, ctx, frames, pixscale, **where):
+        """the frames where the detect call will read them -> (device-resident catalogue, [(frame record, n_extended)])"""
+        rec, frec = ctx.find_stars(frames, sigma=self.sigma, device_out=True, **where, **self.params)
+        import torch
+        n_ext = (rec.view(torch.int32).reshape(len(frec), -1, 8)[:, :, 3] & _native.STAR_EXTENDED).sum(1).cpu().numpy()
+        return ctx.stars_catalog(rec, frec, pixscale, device=True), [(frec[j], int(n_ext[j])) for j in range(len(frec))]
+
+    def one(self, img, pixscale):
+        """one host frame -> (its catalogue as the per-frame dict of columns, (frame record, n_extended))"""
+        from ..stars import n_extended, to_catalog
+        with use_context(*img.shape) as ctx:
+            rec, frec = ctx.find_stars(img, sigma=self.sigma, **self.params)
+        cat = to_catalog(rec, frec, pixscale)
+        k = int(cat["count"][0])
+        return {key: v[0, :k] for key, v in cat.items() if key != "count"}, (frec[0], int(n_extended(rec, frec)[0]))
+
+    def row(self, key, frec, n_ext):
+        from ..stars import format_row
+        self.out.write(format_row(key, frec, n_ext) + "\n")
+
+    def flush(self):
+        self.out.flush()
+
+
 class _ShortRecord:
     """a frame's record of ``_RadonStage`` with ``short``: the record it has without (``base``), its short records [K], their
     n_lines and [(stack record, row)] per found short candidate (empty without ``prof_out``)"""
@@ -366,7 +399,7 @@ class _RadonStage:
         self._handles = {}
 
 
-def _load_frame(run, camcol, filter, field):
+def _load_frame(run, camcol, filter, field, catalog=True):
     """Frame image (float32, C-contiguous), results-row head, photoObj columns; raises like the
     reference when neither the .fits nor the .fits.bz2 exists (detecttrails.py:81-87)."""
     path = sdssfiles.filename("frame", run=run, camcol=camcol, field=field, filter=filter)
@@ -378,7 +411,7 @@ def _load_frame(run, camcol, filter, field):
     img, h = fitslite.read_image(path)
     img = _np.ascontiguousarray(img, dtype=_np.float32)
     head = " ".join(str(x) for x in (run, camcol, filter, field, *(h[k] for k in _HEADER_KEYS)))
-    cat = read_photoObj_arrays(sdssfiles.filename("photoObj", run=run, camcol=camcol, field=field))
+    cat = read_photoObj_arrays(sdssfiles.filename("photoObj", run=run, camcol=camcol, field=field)) if catalog else None
     return img, head, cat
 
 
@@ -434,8 +467,10 @@ class _Chunk:
     ``rlines[i]`` the faint-trail record of a frame without a detection (``radon``: a ``_RadonStage``), or its exception.  A new
     per-frame product gets a slot here, a step in ``_run_group`` and ``_run_frame``, and its row in ``_emit``."""
 
-    def __init__(self, n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon=None):
-        self.results, self.errors, self.profiles, self.sky, self.radon = results, errors, profiles, sky, radon
+    def __init__(self, n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon=None,
+                 stars=None):
+        self.results, self.errors, self.profiles, self.sky, self.radon, self.stars = results, errors, profiles, sky, radon, stars
+        self.strecs = [None] * n                      # (frame record, n_extended) of the source finder (``stars``: a ``_StarsStage``)
         self.params_bright, self.params_dim, self.params_removestars = params_bright, params_dim, params_removestars
         self.trail_params = trail_params or {}
         self.debug = params_bright.get("debug") or params_dim.get("debug")
@@ -450,6 +485,8 @@ def _run_frame(c, i, filter, frame):
         img, cat = frame()
         if c.sky is not None:
             img, c.srecs[i] = c.sky.one(img)
+        if c.stars is not None:
+            cat, c.strecs[i] = c.stars.one(img, c.params_removestars["pixscale"])
         c.rows[i] = process_frame_arrays(img, cat, filter, c.params_bright, c.params_dim, c.params_removestars)
         if c.profiles is not None and c.rows[i][0]:
             try:
@@ -484,6 +521,10 @@ def _run_group(c, idx, filter, shape, inflight, source, second, detect_kw=None, 
                 for j, i in enumerate(idx):
                     c.srecs[i] = srecs[j]
                 detect_kw = measure_kw = {}
+            if c.stars is not None:                   # the chunk's catalogue: the sources of the frames the detect call reads
+                packed, strecs = c.stars.batch(ctx, frames, rs.pixscale, **detect_kw)
+                for j, i in enumerate(idx):
+                    c.strecs[i] = strecs[j]
             recs = ctx.detect_batch(frames, c.params_bright, c.params_dim, packed, rs, **detect_kw)
             c.gpu_s += time.perf_counter() - t0
             if c.profiles is not None:
@@ -520,6 +561,8 @@ def _emit(c, i, key, head, shape):
     the header to take them from) or the errors entry; then the profiles row or the measurement's errors entry."""
     if c.srecs[i] is not None:
         c.sky.row(key, c.srecs[i])
+    if c.strecs[i] is not None:
+        c.stars.row(key, *c.strecs[i])
     try:
         row = c.rows[i]
         if isinstance(row, Exception):
@@ -549,18 +592,20 @@ def _emit(c, i, key, head, shape):
 
 
 def process_field(results, errors, run, camcol, filter, field, params_bright, params_dim,
-                  params_removestars, profiles=None, trail_params=None, sky=None, radon=None):
+                  params_removestars, profiles=None, trail_params=None, sky=None, radon=None, stars=None):
     """One frame end to end (reference: detecttrails.py:30-143): locate the frame (or its .bz2),
     read image + header + photoObj, detect, append ``run camcol filter field tai crpix1 crpix2
     crval1 crval2 cd11 cd12 cd21 cd22 x1 y1 x2 y2`` to ``results``; every exception is logged
     to ``errors`` (ids, 3-frame traceback, message) and swallowed.  ``profiles``: the sink (``add(key, trail, profile)``) the
     frame's trail profile goes to when it has a detection.  ``sky``: a ``_SkyStage``; the frame is normalised first and its
     sky.txt row written (detection and profile then refer to the normalised frame).  ``radon``: a ``_RadonStage``; a frame
-    without a detection is searched for a faint trail and a line that is found gets its radon.txt row."""
-    c = _Chunk(1, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon)
+    without a detection is searched for a faint trail and a line that is found gets its radon.txt row.  ``stars``: a
+    ``_StarsStage``; the photoObj file is not opened, the catalogue is what the source finder finds in the frame (after the
+    normalisation, if on), and the frame's stars.txt row is written."""
+    c = _Chunk(1, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon, stars)
     head = None
     try:
-        img, head, cat = _load_frame(run, camcol, filter, field)
+        img, head, cat = _load_frame(run, camcol, filter, field, catalog=stars is None)
     except Exception as e:  # noqa: BLE001
         c.rows[0] = e
     else:
@@ -601,7 +646,7 @@ def process_fields_batched(results, errors, ids, params_bright, params_dim, para
 
 
 def process_loaded(results, errors, loaded, params_bright, params_dim, params_removestars, profiles=None, trail_params=None, sky=None,
-                   radon=None):
+                   radon=None, stars=None):
     """process_fields_batched for a chunk the loader has read (``loader.Loaded``): the frames that sit in pinned memory go to
     the GPU as contiguous same-filter slices of that memory with the matching rows of the padded catalogue arrays (no copy
     of a frame on the host, no per-frame Python), the others take the per-frame path; rows and errors entries come out in
@@ -609,11 +654,13 @@ def process_loaded(results, errors, loaded, params_bright, params_dim, params_re
     ``_SkyStage``: every slice is normalised into the handle's device buffer first (the pinned big-endian slots go in as they
     are), detection and measurement run on that buffer, and one sky.txt row per normalised frame is written, in the caller's
     order, ahead of the frame's results row.  ``radon``: a ``_RadonStage``: after each slice's detection call its frames without
-    a detection are searched where that call left them, and the lines found get their radon.txt rows."""
+    a detection are searched where that call left them, and the lines found get their radon.txt rows.  ``stars``: a
+    ``_StarsStage``: every slice's catalogue is built on the device from the frames the detect call is about to read (the
+    loader's catalogue rows are not used), and one stars.txt row per frame is written after its sky row."""
     import time
     t_in = time.perf_counter()
     n = len(loaded.keys)
-    c = _Chunk(n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon)
+    c = _Chunk(n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon, stars)
     by_slot = {}
     for i in range(n):
         if loaded.error[i] is not None:
@@ -679,6 +726,12 @@ class DetectTrails:
     ``<savepath>/sky.txt``) gets one row per frame that loaded: ``run camcol filter field status sky sigma gain n_empty``,
     written ahead of the chunk's progress marks; rank files, resume and ``Jobs`` treat it like results.txt.  Profiles and
     defocus fits then refer to the normalised frame: flux = value / gain + sky.
+    ``find_stars=True`` (default off): for frames that have no photoObj table.  The loader does not open photoObj files; each
+    chunk's remove_stars catalogue is what the source finder finds in its frames (include/lfdmi.h: source finder;
+    ``stars_params``: dict or ``lfd_amd.stars.StarsParams``), after the normalisation when that is on (sigma ``target_sigma``,
+    otherwise 0.025).  ``stars_file`` (default ``<savepath>/stars.txt``) gets one row per frame that loaded: ``run camcol
+    filter field status n_found n_out n_extended``; rank files, resume and ``Jobs`` treat it like sky.txt.  Every other output of
+    a run without ``find_stars`` stays byte for byte what it is.
     ``radon=True`` (default off): after each chunk's detection call the frames WITHOUT a detection are searched for a trail that
     is faint in every pixel but long (include/lfdmi.h: faint-trail search; ``radon_params``: dict or
     ``lfd_amd.radon.RadonParams``), with the sky sigma ``target_sigma`` under ``normalize=True`` and 0.025 otherwise.  A line
@@ -724,6 +777,10 @@ class DetectTrails:
         self.sky_params = as_params(kwargs.get("sky_params"))
         if self.normalize:
             _native.make_sky_params(**self.sky_params)          # (unknown names raise here, not per frame)
+        self.find_stars = bool(kwargs.get("find_stars", False))
+        self.stars_file = kwargs.get("stars_file", os.path.join(save, "stars.txt"))
+        from ..stars import as_params as stars_as_params
+        self.stars_params = stars_as_params(kwargs.get("stars_params"))    # (out-of-range values raise here, not per frame)
         self.radon = bool(kwargs.get("radon", False))
         self.radon_file = kwargs.get("radon_file", os.path.join(save, "radon.txt"))
         from ..radon import as_params as radon_as_params
@@ -908,6 +965,7 @@ class DetectTrails:
                 (open(self.profiles + suffix, "a") if self.trail_profiles else contextlib.nullcontext()) as profiles, \
                 (open(self.defocus_file + suffix, "a") if self.defocus else contextlib.nullcontext()) as defocus_out, \
                 (open(self.sky_file + suffix, "a") if self.normalize else contextlib.nullcontext()) as sky_out, \
+                (open(self.stars_file + suffix, "a") if self.find_stars else contextlib.nullcontext()) as stars_out, \
                 (open(self.radon_file + suffix, "a") if self.radon else contextlib.nullcontext()) as radon_out, \
                 (open(self.radon_segments_file + suffix, "a") if self.radon and self.radon_lines is not None
                  else contextlib.nullcontext()) as segments_out, \
@@ -921,6 +979,10 @@ class DetectTrails:
             sky = _SkyStage(sky_out, self.sky_params) if self.normalize else None
             if sky is not None:
                 prof_kw["sky"] = sky
+            stars = None
+            if self.find_stars:
+                sigma = _native.make_sky_params(**self.sky_params).target_sigma if self.normalize else 0.025
+                stars = prof_kw["stars"] = _StarsStage(stars_out, self.stars_params, sigma)
             radon = None
             if self.radon:
                 sigma = _native.make_sky_params(**self.sky_params).target_sigma if self.normalize else 0.025
@@ -938,6 +1000,8 @@ class DetectTrails:
                     profiles.flush()
                 if sky is not None:
                     sky.flush()
+                if stars is not None:
+                    stars.flush()
                 if radon is not None:
                     radon.flush()
                 progress.write("".join("%s %s %s %s\n" % tuple(k) for k in done_keys))
@@ -969,7 +1033,7 @@ class DetectTrails:
             # decoders side by side: one chunk's Huffman stage overlaps the other's inverse BWT, loader.FrameLoader)
             depth = max(1, min(int(os.environ.get("LFD_LOADER_DEPTH", 2 if compressed else 1)), len(chunks)))
             with use_context(*shape, inflight=slots) as ctx:
-                loader = FrameLoader(ctx, shape, slots, loader_threads, depth=depth, expect_bz2=compressed)
+                loader = FrameLoader(ctx, shape, slots, loader_threads, depth=depth, expect_bz2=compressed, catalogs=not self.find_stars)
             self.last_stats.update(chunk_frames=slots, setup_s=time.perf_counter() - t_start)
             try:
                 trace = os.environ.get("LFD_LOADER_TRACE") == "1"

@@ -115,7 +115,9 @@ class Loaded:
 class FrameLoader:
     """``threads`` native reader threads, two pinned buffers of ``slots`` frames of ``shape`` (allocated through ``ctx``)."""
 
-    def __init__(self, ctx, shape, slots, threads=None, max_obj=MAX_OBJ, depth=1, expect_bz2=False):
+    def __init__(self, ctx, shape, slots, threads=None, max_obj=MAX_OBJ, depth=1, expect_bz2=False, catalogs=True):
+        """catalogs=False: no photoObj file is opened; every frame's catalogue is empty (the source finder supplies one)"""
+        self.catalogs = bool(catalogs)
         self.shape = tuple(shape)
         self.slots = int(slots)
         self.max_obj = int(max_obj)
@@ -438,11 +440,14 @@ class FrameLoader:
             rc = self.lib.lfdmi_fits_read_frames(_paths(fpaths), n, h, w, P(raw), self.threads, P(fstat), P(hdrs), HDR_CAP, P(hlen))
             if rc:
                 raise _native.NativeError(rc, "lfdmi_fits_read_frames")
-        rc = self.lib.lfdmi_fits_read_photoobj(_paths(ppaths), n, self.max_obj, P(cats["ROWC"]), P(cats["COLC"]), P(cats["PSFMAG"]),
-                                               P(cats["PETROTH90"]), P(cats["NOBSERVE"]), P(cats["NDETECT"]), P(cats["count"]),
-                                               self.threads, P(pstat))
-        if rc:
-            raise _native.NativeError(rc, "lfdmi_fits_read_photoobj")
+        if not self.catalogs:
+            cats["count"][:] = 0
+        else:
+            rc = self.lib.lfdmi_fits_read_photoobj(_paths(ppaths), n, self.max_obj, P(cats["ROWC"]), P(cats["COLC"]), P(cats["PSFMAG"]),
+                                                   P(cats["PETROTH90"]), P(cats["NOBSERVE"]), P(cats["NDETECT"]), P(cats["count"]),
+                                                   self.threads, P(pstat))
+            if rc:
+                raise _native.NativeError(rc, "lfdmi_fits_read_photoobj")
         futs = []
         on_device = set()
         if self.bz2_device:

@@ -84,3 +84,22 @@ def remove_stars(img, _run, _camcol, _filter, _field, defaultxy, filter_caps, ma
     cat = read_photoObj_arrays(sdssfiles.filename("photoObj", run=_run, camcol=_camcol, field=_field))
     return remove_stars_arrays(img, cat, _filter, defaultxy, filter_caps, maxxy, pixscale, magcount,
                                maxmagdiff, debug)
+
+
+def remove_stars_found(img, _filter, defaultxy=20, filter_caps=None, maxxy=60, pixscale=0.396, magcount=3, maxmagdiff=3,
+                       debug=False, sigma=None, stars_params=None):
+    """remove_stars for a frame without a photoObj file: the device finds the frame's compact sources (include/lfdmi.h: source
+    finder) and blots them through the same ``Context.remove_stars`` the catalogue path takes.  ``img``: one float32 C-contiguous
+    frame (numpy or torch CUDA), blotted in place and returned; sigma: its sky sigma (None: 0.025); stars_params: None, a dict or
+    a ``StarsParams``.  The keyword defaults are params_removestars'."""
+    from ..stars import as_params
+    if getattr(img, "ndim", 2) != 2:
+        raise ValueError("remove_stars expects one 2-d frame")
+    if not _native._is_dev(img) and (img.dtype != np.float32 or not img.flags.c_contiguous):
+        raise ValueError("remove_stars_found needs a float32 C-contiguous frame")
+    caps = filter_caps or {'u': 22.0, 'g': 22.2, 'r': 22.2, 'i': 21.3, 'z': 20.5}
+    rs = _native.make_rs_params(_filter, defaultxy, caps, maxxy, pixscale, magcount, maxmagdiff)
+    with use_context(*tuple(img.shape)) as ctx:
+        rec, frec = ctx.find_stars(img, sigma=sigma, device_out=True, **as_params(stars_params))
+        ctx.remove_stars(img, ctx.stars_catalog(rec, frec, pixscale, device=True), rs)
+    return img
