@@ -712,6 +712,73 @@ typedef struct {
 int lfdmi_inject_trails(lfdmi_ctx *ctx, void *frames, int dtype, int n, int h, int w, int loc, const lfdmi_inject_trail *trails,
                         int n_trails, const float *tables, int n_tables, int table_len, double table_step, int subsample);
 
+/* ---- trail masks ------------------------------------------------------------------------------------------------------------
+ * lfdmi_mask_trails turns segments into pixels: every pixel of a frame whose centre lies inside a segment's band gets the
+ * segment's bits in a mask plane and, optionally, a fill value in the frame.  It is what the next program asks for first:
+ * photometry that skips the streak, a co-add that rejects it, a second search that must not find the same trail again.  The
+ * segments are the ones every measurement ends in (lfdmi_trail.x1 .. y2 and lfdmi_stack.x1 .. y2 with their fwhm,
+ * lfdmi_radon_line.ex1 .. ey2, a results row).  A pixel filled with +0 or NaN is invalid to the faint-trail search and to the
+ * stacked cross-sections by their own step 1, as a pixel remove_stars blotted is, so a filled mask composes with them without a
+ * new rule.  The reference has no such step.  The procedure below is the definition; tests/mask_ref.py restates it in numpy and
+ * the device reproduces it byte for byte: membership is a fixed sequence of double operations and comparisons, and every other
+ * result is an OR or an exact integer count, so nothing depends on the order in which the device works.
+ *
+ * 1. Coordinates are the detection records': x = column, y = row of the flipped frame, so pixel (x, y) is buffer row H-1-y.  The
+ *    mask plane is n x h x w uint8 in buffer-row order, laid out exactly like the frames.
+ * 2. Geometry of a segment (x1, y1) - (x2, y2), on the host in double, each operation rounded, no contraction:
+ *        dx = x2 - x1;  dy = y2 - y1;  L = sqrt(dx*dx + dy*dy);  e = (dx / L, dy / L);  nrm = (-e.y, e.x).
+ *    The segment is LFDMI_MASK_BAD_SEGMENT when an end point is not finite, a coordinate exceeds 1e6 in magnitude, L == 0,
+ *    half is negative or not finite, or cap is NaN or negative.  A bad segment masks nothing and has n_pix = 0.  cap = +inf:
+ *    the whole line.
+ * 3. Membership of the pixel centre (x, y), x = 0 .. w-1, y = 0 .. h-1: in double, left to right, no contraction,
+ *        u = ((double)x - x1) * nrm.x + ((double)y - y1) * nrm.y
+ *        t = ((double)x - x1) * e.x + ((double)y - y1) * e.y
+ *        inside iff fabs(u) <= half && t >= -cap && t <= L + cap            (L + cap: one addition, on the host).
+ *    The device evaluates no transcendental function and no division.
+ * 4. Mask.  Every inside pixel gets mask |= bits; OR does not depend on order, so crossing segments need no rule.  clear != 0:
+ *    the call zeroes the n planes first; otherwise it ORs onto what the caller passed.  mask may be NULL (fill only).
+ * 5. Fill (fill_mode).  LFDMI_MASK_FILL_NONE: the frames are not touched and may be NULL.  _ZERO: every pixel inside at least one
+ *    segment becomes +0.0f.  _NAN: the quiet NaN 0x7fc00000.  _VALUE: (float)fill of the lowest-index segment of that frame that
+ *    contains the pixel.  A pixel inside no segment is not written: its bits stay, -0 and NaN payloads included.
+ * 6. Statistics, exact integers.  stats[i] = {status, n_pix}: n_pix = the pixels of the segment's frame inside segment i (a pixel
+ *    two segments share counts for both); status LFDMI_MASK_OK, LFDMI_MASK_BAD_SEGMENT, or LFDMI_MASK_EMPTY for a good segment
+ *    with n_pix = 0.  frame_counts[f] = the pixels of frame f inside at least one segment of this call.
+ *
+ * The device culls 64 x 16 pixel tiles against every segment's band (|u| <= half and t in [-cap, L + cap], widened by the tile's
+ * half extent along the normal and along the line; k_mask_cull) and launches only over the surviving (frame, tile) pairs
+ * (k_mask_render): a thread owns its pixels, so neither the image nor the mask sees an atomic, and a pixel inside no segment
+ * causes no write.  The counts are one integer atomicAdd per wave and segment.  There is no cap on the segments of a frame. */
+enum { LFDMI_MASK_OK = 0, LFDMI_MASK_BAD_SEGMENT = 1, LFDMI_MASK_EMPTY = 2 };
+enum { LFDMI_MASK_FILL_NONE = 0, LFDMI_MASK_FILL_ZERO = 1, LFDMI_MASK_FILL_NAN = 2, LFDMI_MASK_FILL_VALUE = 3 };
+typedef struct {
+    int32_t frame;            /* 0 .. n-1 */
+    uint8_t bits;             /* ORed into the mask bytes of its pixels; not 0 */
+    uint8_t pad[3];
+    double x1, y1, x2, y2;    /* flipped frame, as lfdmi_trail.x1 .. y2, lfdmi_radon_line.ex1 .. ey2 or a results row */
+    double half;              /* half-width of the band in px (>= 0, finite) */
+    double cap;               /* how far the band reaches past either end point in px (>= 0; +inf: the whole line) */
+    double fill;              /* LFDMI_MASK_FILL_VALUE: the value of its pixels */
+} lfdmi_mask_segment;
+typedef struct {
+    int32_t fill_mode;        /* LFDMI_MASK_FILL_*; default LFDMI_MASK_FILL_NONE */
+    int32_t clear;            /* != 0: the mask planes are zeroed first; default 1 */
+} lfdmi_mask_params;
+typedef struct {
+    int32_t status;           /* LFDMI_MASK_* */
+    int32_t n_pix;
+} lfdmi_mask_stat;
+void lfdmi_default_mask_params(lfdmi_mask_params *out);
+/* frames: n frames of h x w float32 at loc; needed only with a fill, which takes LFDMI_F32 and refuses LFDMI_F32_BE.  loc
+ * LFDMI_DEVICE: filled in place; LFDMI_HOST / LFDMI_HOST_PINNED: the frames that carry a segment are uploaded, filled and copied
+ * back, the others are neither copied nor written.  segs: n_seg records (host), any number per frame.  params NULL: the defaults.
+ * mask: n x h x w uint8 at mask_loc (handled as the frames are), or NULL.  stats: n_seg records, frame_counts: n int32 (host;
+ * either may be NULL).  LFDMI_ERR_ARG, and no pixel or mask byte is touched: a frame outside [0, n), bits == 0, a bad fill_mode,
+ * a fill without frames, neither mask nor fill, NULL segs with n_seg > 0, h * w > 1e9.  The call keeps no state (its device memory
+ * comes from the stream's pool and goes back before it returns), refuses while calls are in flight, runs on the context's
+ * stream and waits for it once, at its end. */
+int lfdmi_mask_trails(lfdmi_ctx *ctx, void *frames, int dtype, int n, int h, int w, int loc, const lfdmi_mask_segment *segs, int n_seg,
+                      const lfdmi_mask_params *params, uint8_t *mask, int mask_loc, lfdmi_mask_stat *stats, int32_t *frame_counts);
+
 /* ---- faint-trail search -----------------------------------------------------------------------------------------------------
  * The detector finds a trail whose pixels survive the 8-bit conversion; lfdmi_radon_search finds one that is faint in every
  * pixel but long: it sums the frame along every line of a dyadic family (the fast Radon transform of Goetz and Druckmueller /

@@ -40,6 +40,7 @@ SYMBOLS = (
     "lfdmi_defocus_bank_read", "lfdmi_fit_defocus",
     "lfdmi_default_sky_params", "lfdmi_sky_create", "lfdmi_sky_destroy", "lfdmi_sky_dims", "lfdmi_sky_frames", "lfdmi_sky_normalize",
     "lfdmi_inject_trails",
+    "lfdmi_default_mask_params", "lfdmi_mask_trails",
     "lfdmi_default_radon_params", "lfdmi_radon_create", "lfdmi_radon_destroy", "lfdmi_radon_dims", "lfdmi_radon_search",
     "lfdmi_default_radon_lines_params", "lfdmi_radon_search_lines",
     "lfdmi_default_radon_short_params", "lfdmi_radon_search_short",
@@ -186,6 +187,41 @@ def make_sky_params(**params):
 INJECT_DTYPE = np.dtype([("frame", "<i4"), ("table", "<i4"), ("rho", "<f8"), ("theta", "<f8"), ("t0", "<f8"), ("t1", "<f8"),
                          ("amplitude", "<f8")])
 INJECT_MAX_TABLE = 4097
+
+
+class MaskSegment(C.Structure):
+    """lfdmi_mask_segment: one record per segment of lfdmi_mask_trails (include/lfdmi.h: trail masks)."""
+    _fields_ = [("frame", C.c_int32), ("bits", C.c_uint8), ("pad", C.c_uint8 * 3),
+                ("x1", C.c_double), ("y1", C.c_double), ("x2", C.c_double), ("y2", C.c_double),
+                ("half", C.c_double), ("cap", C.c_double), ("fill", C.c_double)]
+
+
+class MaskParamsStruct(C.Structure):
+    """lfdmi_mask_params (include/lfdmi.h: trail masks)."""
+    _fields_ = [("fill_mode", C.c_int32), ("clear", C.c_int32)]
+
+
+MASK_SEGMENT_DTYPE = np.dtype([("frame", "<i4"), ("bits", "u1"), ("pad", "u1", (3,)), ("x1", "<f8"), ("y1", "<f8"), ("x2", "<f8"),
+                               ("y2", "<f8"), ("half", "<f8"), ("cap", "<f8"), ("fill", "<f8")])
+# lfdmi_mask_stat: one record per segment
+MASK_STAT_DTYPE = np.dtype([("status", "<i4"), ("n_pix", "<i4")])
+MASK_OK, MASK_BAD_SEGMENT, MASK_EMPTY = 0, 1, 2
+MASK_FILL_NONE, MASK_FILL_ZERO, MASK_FILL_NAN, MASK_FILL_VALUE = 0, 1, 2, 3
+MASK_FILLS = {"none": MASK_FILL_NONE, "zero": MASK_FILL_ZERO, "nan": MASK_FILL_NAN, "value": MASK_FILL_VALUE}
+
+
+def _mask_fill(k, v):
+    if k == "fill_mode" and isinstance(v, str):
+        try:
+            return MASK_FILLS[v.lower()]
+        except KeyError:
+            raise ValueError(f"fill must be one of {sorted(MASK_FILLS)}, not {v!r}") from None
+    return int(v)
+
+
+def make_mask_params(**params):
+    """lfdmi_default_mask_params with the given fields replaced (unknown names raise; fill_mode also by name)."""
+    return _make_params(MaskParamsStruct, "lfdmi_default_mask_params", "mask", params, _mask_fill)
 
 
 class RadonParamsStruct(C.Structure):
@@ -360,6 +396,10 @@ def lib():
                                              C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.lfdmi_inject_trails.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                              C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int]
+        _lib.lfdmi_default_mask_params.restype = None
+        _lib.lfdmi_default_mask_params.argtypes = [C.c_void_p]
+        _lib.lfdmi_mask_trails.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                           C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         _lib.lfdmi_default_radon_params.restype = None
         _lib.lfdmi_default_radon_params.argtypes = [C.c_void_p]
         _lib.lfdmi_radon_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
@@ -1088,6 +1128,61 @@ class Context:
         self._chk(self._lib.lfdmi_inject_trails(self._h, _ptr(fr), code, n, h, w, loc, _ptr(tr), len(tr), _ptr(tab), tab.shape[0],
                                                 tab.shape[1], C.c_double(float(table_step)), int(subsample)))
         return frames
+
+    # -- trail masks (lfdmi_mask_trails) ------------------------------------------------------------------------------------------
+    def mask_trails(self, frames, segments, shape=None, mask=None, fill="none", clear=True, pinned=False):
+        """Flag, and optionally fill, the pixels of every segment's band (include/lfdmi.h: trail masks).  frames: float32 (n, h, w)
+        or (h, w) as ``inject_trails`` takes them, filled in place (a torch CUDA tensor where it is); None with fill="none", when
+        ``shape`` = (n, h, w) or (h, w) or the mask gives the size.  segments: MASK_SEGMENT_DTYPE records (or anything
+        ``np.asarray`` turns into them), coordinates of the flipped frame.  mask: None (a new uint8 plane set, on the device when
+        the frames are), False (fill only), or a uint8 array / torch CUDA tensor of the frames' shape, which stays where it is and
+        is ORed onto unless ``clear``.  fill: "none", "zero", "nan" or "value".  ``pinned=True``: the host arrays live in
+        ``PinnedBuffer`` memory.  Returns (mask or None, MASK_STAT_DTYPE records [n_seg], int32 counts per frame [n])."""
+        p = make_mask_params(fill_mode=fill, clear=int(bool(clear)))
+        fr, code, loc, sq = None, F32, HOST, False
+        if frames is not None:
+            if p.fill_mode != MASK_FILL_NONE and not _is_dev(frames) and not (
+                    isinstance(frames, np.ndarray) and frames.flags.c_contiguous and frames.flags.writeable):
+                raise ValueError("mask_trails fills a writable C-contiguous array (it is modified in place)")
+            fr, code, n, h, w, loc = self._frames(frames, pinned, "mask_trails")
+            sq = len(tuple(fr.shape)) == 2
+        elif shape is not None:
+            shp = tuple(int(v) for v in shape)
+            sq = len(shp) == 2
+            n, h, w = (1, *shp) if sq else shp
+        elif mask is not None and mask is not False:
+            shp = tuple(mask.shape)
+            sq = len(shp) == 2
+            n, h, w = (1, *shp) if sq else shp
+        else:
+            raise ValueError("mask_trails needs frames, a shape or a mask")
+        own = mask is None                                 # (an array made here is pageable, whatever ``pinned`` says of the caller's)
+        if mask is None:
+            if _is_dev(fr):
+                import torch
+                mask = torch.empty((h, w) if sq else (n, h, w), dtype=torch.uint8, device=fr.device)   # (the library clears it)
+            else:
+                mask = np.zeros((h, w) if sq else (n, h, w), np.uint8)
+            p.clear = 1
+        elif mask is False:
+            mask = None
+        else:
+            if tuple(mask.shape) not in ((n, h, w), (h, w) if n == 1 else None):
+                raise ValueError(f"mask of shape {tuple(mask.shape)} for frames of shape {(n, h, w)}")
+            if str(mask.dtype).replace("torch.", "") != "uint8":
+                raise TypeError("mask_trails needs a uint8 mask")
+            if _is_dev(mask):
+                if not mask.is_contiguous():
+                    raise ValueError("device tensors must be contiguous")
+            elif not (isinstance(mask, np.ndarray) and mask.flags.c_contiguous and mask.flags.writeable):
+                raise ValueError("mask_trails needs a writable C-contiguous mask (it is written in place)")
+        mloc = DEVICE if _is_dev(mask) else (HOST_PINNED if pinned and not own else HOST)
+        sg = np.ascontiguousarray(segments, MASK_SEGMENT_DTYPE).reshape(-1)
+        stats = np.zeros(len(sg), MASK_STAT_DTYPE)
+        counts = np.zeros(n, np.int32)
+        self._chk(self._lib.lfdmi_mask_trails(self._h, _ptr(fr), code, n, h, w, loc, _ptr(sg), len(sg), C.byref(p), _ptr(mask), mloc,
+                                              _ptr(stats), _ptr(counts)))
+        return mask, stats, counts
 
     # -- stacked cross-sections (lfdmi_stack_profiles) ----------------------------------------------------------------------------
     def stack_profiles(self, frames, segments, sigma=None, pinned=False, native_device=False, raw=False, **params):

@@ -399,6 +399,63 @@ class _RadonStage:
         self._handles = {}
 
 
+class _MaskStage:
+    """The trail masks behind the measurements for ``DetectTrails(trail_masks=True)`` (include/lfdmi.h: trail masks): one
+    masks.txt row per results.txt row (source ``detect``) and, with ``radon_lines``, per found faint line (source ``radon``),
+    and with ``mask_dir`` the frame's packed plane.  ``half_params``: keywords of ``masks.half_width``.  A frame's segments are
+    flagged in one mask-only call on the shared context when its rows are written."""
+
+    def __init__(self, out, half_params=None, mask_dir=None):
+        self.out, self.half_params, self.mask_dir = out, dict(half_params or {}), mask_dir
+        if mask_dir is not None:
+            os.makedirs(mask_dir, exist_ok=True)
+
+    def detect_segment(self, res, meas):
+        """(x1, y1, x2, y2, half) of a detected frame: the refined extent and the fwhm of its trail record where the measurement
+        is OK, else the results row's points (far off the image: the whole line) and the default half-width"""
+        from ..masks import half_width
+        if isinstance(meas, tuple) and int(meas[0]["status"]) == _native.TRAIL_OK:
+            t = meas[0]
+            return (float(t["x1"]), float(t["y1"]), float(t["x2"]), float(t["y2"]), half_width(float(t["fwhm"]), **self.half_params))
+        fwhm = float(meas[0]["fwhm"]) if isinstance(meas, tuple) else float("nan")
+        return (float(res["x1"]), float(res["y1"]), float(res["x2"]), float(res["y2"]), half_width(fwhm, **self.half_params))
+
+    def radon_segments(self, line):
+        """[(x1, y1, x2, y2, half)] of a frame's found faint lines (a ``_RadonStage`` record with ``lines``), in peel order; the
+        half-width from the stacked cross-section's fwhm where that was measured and is OK"""
+        from ..masks import half_width
+        if isinstance(line, _ShortRecord):
+            line = line.base
+        if not isinstance(line, tuple):
+            return []
+        recs, nl = line[:2]
+        out = []
+        for k in range(nl):
+            fwhm = float("nan")
+            if len(line) > 2 and k < len(line[2]) and int(line[2][k][0]["status"]) == _native.STACK_OK:
+                fwhm = float(line[2][k][0]["fwhm"])
+            r = recs[k]
+            out.append((float(r["ex1"]), float(r["ey1"]), float(r["ex2"]), float(r["ey2"]), half_width(fwhm, **self.half_params)))
+        return out
+
+    def rows(self, key, shape, source, segs):
+        """flags ``segs`` on one plane of ``shape`` and writes their rows (and the plane)"""
+        from .. import masks
+        if not segs:
+            return
+        sg = masks.segments([(0, *s) for s in segs])
+        with use_context(*shape) as ctx:
+            mask, stats, _ = ctx.mask_trails(None, sg, shape=tuple(shape))
+        for k, s in enumerate(sg):
+            self.out.write(masks.format_row(key, source, k, s, stats[k]["n_pix"]) + "\n")
+        if self.mask_dir is not None:
+            bits, shp = masks.pack(mask)
+            _np.savez(os.path.join(self.mask_dir, "mask-%s-%s-%s-%s.npz" % tuple(key)), bits=bits, shape=_np.array(shp, _np.int64))
+
+    def flush(self):
+        self.out.flush()
+
+
 def _load_frame(run, camcol, filter, field, catalog=True):
     """Frame image (float32, C-contiguous), results-row head, photoObj columns; raises like the
     reference when neither the .fits nor the .fits.bz2 exists (detecttrails.py:81-87)."""
@@ -468,8 +525,10 @@ class _Chunk:
     per-frame product gets a slot here, a step in ``_run_group`` and ``_run_frame``, and its row in ``_emit``."""
 
     def __init__(self, n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon=None,
-                 stars=None):
+                 stars=None, masks=None):
         self.results, self.errors, self.profiles, self.sky, self.radon, self.stars = results, errors, profiles, sky, radon, stars
+        self.masks = masks                            # a ``_MaskStage``: its rows are made in ``_emit``, from the slots below
+        self.shapes = [None] * n                      # the shape of a frame that ran on its own
         self.strecs = [None] * n                      # (frame record, n_extended) of the source finder (``stars``: a ``_StarsStage``)
         self.params_bright, self.params_dim, self.params_removestars = params_bright, params_dim, params_removestars
         self.trail_params = trail_params or {}
@@ -483,6 +542,7 @@ def _run_frame(c, i, filter, frame):
     trail measurement of a detected frame."""
     try:
         img, cat = frame()
+        c.shapes[i] = tuple(img.shape)
         if c.sky is not None:
             img, c.srecs[i] = c.sky.one(img)
         if c.stars is not None:
@@ -580,6 +640,15 @@ def _emit(c, i, key, head, shape):
         _log_error(c.errors, key, line, c.debug)
     elif line is not None:
         c.radon.row(key, line)
+    if c.masks is not None:                           # (after the rows above, which it does not touch)
+        try:
+            shp = c.shapes[i] or tuple(shape)           # (a frame that ran on its own may differ from the chunk's shape)
+            if detection:
+                c.masks.rows(key, shp, "detect", [c.masks.detect_segment(res, c.meas[i])])
+            elif line is not None and not isinstance(line, Exception):
+                c.masks.rows(key, shp, "radon", c.masks.radon_segments(line))
+        except Exception as e:  # noqa: BLE001
+            _log_error(c.errors, key, e, c.debug)
     if not detection or c.profiles is None:
         return
     try:                                              # (results.txt is written before, untouched)
@@ -592,7 +661,7 @@ def _emit(c, i, key, head, shape):
 
 
 def process_field(results, errors, run, camcol, filter, field, params_bright, params_dim,
-                  params_removestars, profiles=None, trail_params=None, sky=None, radon=None, stars=None):
+                  params_removestars, profiles=None, trail_params=None, sky=None, radon=None, stars=None, masks=None):
     """One frame end to end (reference: detecttrails.py:30-143): locate the frame (or its .bz2),
     read image + header + photoObj, detect, append ``run camcol filter field tai crpix1 crpix2
     crval1 crval2 cd11 cd12 cd21 cd22 x1 y1 x2 y2`` to ``results``; every exception is logged
@@ -601,8 +670,9 @@ def process_field(results, errors, run, camcol, filter, field, params_bright, pa
     sky.txt row written (detection and profile then refer to the normalised frame).  ``radon``: a ``_RadonStage``; a frame
     without a detection is searched for a faint trail and a line that is found gets its radon.txt row.  ``stars``: a
     ``_StarsStage``; the photoObj file is not opened, the catalogue is what the source finder finds in the frame (after the
-    normalisation, if on), and the frame's stars.txt row is written."""
-    c = _Chunk(1, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon, stars)
+    normalisation, if on), and the frame's stars.txt row is written.  ``masks``: a ``_MaskStage``; a results row, and every found
+    faint line of ``radon`` with lines, gets its masks.txt row."""
+    c = _Chunk(1, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon, stars, masks)
     head = None
     try:
         img, head, cat = _load_frame(run, camcol, filter, field, catalog=stars is None)
@@ -646,7 +716,7 @@ def process_fields_batched(results, errors, ids, params_bright, params_dim, para
 
 
 def process_loaded(results, errors, loaded, params_bright, params_dim, params_removestars, profiles=None, trail_params=None, sky=None,
-                   radon=None, stars=None):
+                   radon=None, stars=None, masks=None):
     """process_fields_batched for a chunk the loader has read (``loader.Loaded``): the frames that sit in pinned memory go to
     the GPU as contiguous same-filter slices of that memory with the matching rows of the padded catalogue arrays (no copy
     of a frame on the host, no per-frame Python), the others take the per-frame path; rows and errors entries come out in
@@ -656,11 +726,12 @@ def process_loaded(results, errors, loaded, params_bright, params_dim, params_re
     order, ahead of the frame's results row.  ``radon``: a ``_RadonStage``: after each slice's detection call its frames without
     a detection are searched where that call left them, and the lines found get their radon.txt rows.  ``stars``: a
     ``_StarsStage``: every slice's catalogue is built on the device from the frames the detect call is about to read (the
-    loader's catalogue rows are not used), and one stars.txt row per frame is written after its sky row."""
+    loader's catalogue rows are not used), and one stars.txt row per frame is written after its sky row.  ``masks``: a
+    ``_MaskStage``, as in ``process_field``."""
     import time
     t_in = time.perf_counter()
     n = len(loaded.keys)
-    c = _Chunk(n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon, stars)
+    c = _Chunk(n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon, stars, masks)
     by_slot = {}
     for i in range(n):
         if loaded.error[i] is not None:
@@ -754,6 +825,16 @@ class DetectTrails:
     ey1 ex2 ey2 seg_snr seg_n_pix``; radon.txt and radon_segments.txt stay what they are without it.  With
     ``radon_profiles=True`` (then ``radon_lines`` may be None) the short segments are measured too, and every row of
     radon_profiles.txt ends with its source, ``lines`` or ``short``.
+    ``trail_masks=True`` (default off): every results.txt row gets one row in ``masks_file`` (default ``<savepath>/masks.txt``),
+    in the same order: ``run camcol filter field source line x1 y1 x2 y2 half n_pix`` with source ``detect`` -- the band of
+    half-width ``half`` around the segment, flagged by ``lfdmi_mask_trails`` (include/lfdmi.h: trail masks; cap 0), and the
+    number of the frame's pixels in it.  With ``trail_profiles=True`` the segment is the trail's refined extent and ``half``
+    comes from its fwhm (``lfd_amd.masks.half_width``; ``mask_params``: dict of its keywords k_fwhm, min_half, grow,
+    default_half); without a measurement it is the results row's line and the default half-width.  With ``radon_lines=K`` every
+    found faint line also gets a row, source ``radon``, its segment ex1 .. ey2, ``half`` from ``radon_profiles``' fwhm when that
+    is on.  ``mask_dir``: each masked frame's plane is written there as ``mask-<run>-<camcol>-<filter>-<field>.npz`` (``bits``,
+    ``shape``: ``masks.pack``).  Rank files, resume and ``Jobs`` treat masks.txt like profiles.txt; every other output stays
+    byte for byte what it is.
     """
 
     _FILTERS = ('u', 'g', 'r', 'i', 'z')
@@ -810,6 +891,13 @@ class DetectTrails:
                 raise ValueError("radon_profiles=True needs radon=True and radon_lines=K: the segments it measures are theirs")
             from ..stack import as_params as stack_as_params
             self.stack_params = stack_as_params(kwargs.get("stack_params"))
+        self.trail_masks = bool(kwargs.get("trail_masks", False))
+        self.masks_file = kwargs.get("masks_file", os.path.join(save, "masks.txt"))
+        self.mask_dir = kwargs.get("mask_dir")
+        self.mask_params = dict(kwargs.get("mask_params") or {})
+        if self.trail_masks:
+            from ..masks import half_width
+            half_width(1.0, **self.mask_params)                  # (unknown names raise here, not per frame)
         if self.trail_profiles:
             _native.make_trail_params(**self.trail_params)      # (unknown names raise here, not per frame)
         if self.defocus:
@@ -972,7 +1060,8 @@ class DetectTrails:
                 (open(self.radon_short_file + suffix, "a") if self.radon_short is not None else contextlib.nullcontext()) as short_out, \
                 (open(self.radon_profiles_file + suffix, "a") if self.radon_profiles else contextlib.nullcontext()) as rprof_out, \
                 (open(self.radon_defocus_file + suffix, "a") if self.radon_profiles and self.defocus
-                 else contextlib.nullcontext()) as rdef_out:
+                 else contextlib.nullcontext()) as rdef_out, \
+                (open(self.masks_file + suffix, "a") if self.trail_masks else contextlib.nullcontext()) as masks_out:
             if self.trail_profiles:
                 profiles = _DefocusTee(profiles, defocus_out, self.defocus_params, self.trail_params)
             prof_kw = {"profiles": profiles, "trail_params": self.trail_params} if self.trail_profiles else {}
@@ -989,6 +1078,9 @@ class DetectTrails:
                 radon = prof_kw["radon"] = _RadonStage(radon_out, self.radon_params, sigma, self.radon_lines, self.radon_lines_params,
                                                        segments_out, rprof_out, self.stack_params, rdef_out, self.defocus_params,
                                                        self.radon_short, short_out)
+            masks = None
+            if self.trail_masks:
+                masks = prof_kw["masks"] = _MaskStage(masks_out, self.mask_params, self.mask_dir)
             if fresh:
                 progress.write(header + "\n")
                 progress.flush()
@@ -1004,6 +1096,8 @@ class DetectTrails:
                     stars.flush()
                 if radon is not None:
                     radon.flush()
+                if masks is not None:
+                    masks.flush()
                 progress.write("".join("%s %s %s %s\n" % tuple(k) for k in done_keys))
                 progress.flush()
 
