@@ -779,6 +779,106 @@ void lfdmi_default_mask_params(lfdmi_mask_params *out);
 int lfdmi_mask_trails(lfdmi_ctx *ctx, void *frames, int dtype, int n, int h, int w, int loc, const lfdmi_mask_segment *segs, int n_seg,
                       const lfdmi_mask_params *params, uint8_t *mask, int mask_loc, lfdmi_mask_stat *stats, int32_t *frame_counts);
 
+/* ---- light curves -----------------------------------------------------------------------------------------------------------
+ * lfdmi_light_curves measures how the brightness changes along a trail: the segment is cut into sections of sec_len px and
+ * every section gets the mean of its core band above the mean of its sky bands.  Every other unit collapses the along-track
+ * direction on purpose, to beat the noise; this one answers what an observer asks next: a meteor flares and fades, a tumbling
+ * body glints, a trail whose rate drops to zero part-way was cut by the shutter or the chip's edge.  The segments are the ones
+ * every measurement ends in, with the half-width of the trail masks.  The reference has no such step.  The procedure below is
+ * the definition; tests/lc_ref.py restates it in numpy and the device reproduces it in every integer and every bit of every
+ * double: a pixel enters every sum as a fixed-point integer, so the sums are integer sums and nothing depends on the order in
+ * which the device works, and every double is made on the host by a fixed sequence of rounded operations.
+ *
+ * 1. Pixels.  Coordinates are the detection records': x = column, y = row of the flipped frame, so pixel (x, y) is buffer row
+ *    H-1-y.  A pixel is valid when it is finite, not +-0 (what remove_stars or a mask fill blotted), |v| <= clip (a float32
+ *    comparison) and, with a mask plane (n x h x w uint8, laid out as lfdmi_mask_trails writes it), (mask & skip_bits) == 0:
+ *    this is how other trails, unblotted stars and bleed columns are kept out.  Its value enters every sum as the integer
+ *        q = llrint((double)v * 1073741824.0)                              (2^30; the product is exact; ties to even).
+ *    |q| <= 2^40 and a section holds fewer than 2^20 pixels at the limits below, so no int64 sum overflows.
+ * 2. Geometry of a segment (x1, y1) - (x2, y2), on the host in double, each operation rounded, no contraction, exactly as step 2
+ *    of the trail masks:
+ *        dx = x2 - x1;  dy = y2 - y1;  L = sqrt(dx*dx + dy*dy);  e = (dx / L, dy / L);  nrm = (-e.y, e.x).
+ *    The segment is LFDMI_LC_BAD_SEGMENT when an end point is not finite, a coordinate exceeds 1e6 in magnitude, L == 0, half is
+ *    not finite or <= 0, bg_in or bg_out is NaN, bg_in < half, bg_out < bg_in or bg_out > LFDMI_LC_MAX_BG.
+ *        inv = 1.0 / sec_len;   n_sec = max(1, (int)ceil(L * inv)).
+ *    n_sec > max_sections_per_seg: LFDMI_LC_TOO_LONG.  (A results row's end points lie about 1000 px off the frame: 125 sections
+ *    at the default sec_len.)
+ * 3. Membership of the pixel centre (x, y), x = 0 .. w-1, y = 0 .. h-1: u and t exactly as step 3 of the trail masks,
+ *        u = ((double)x - x1) * nrm.x + ((double)y - y1) * nrm.y
+ *        t = ((double)x - x1) * e.x + ((double)y - y1) * e.y               (double, left to right, no contraction).
+ *    The pixel takes part iff t >= 0 && t <= L; its section is j = min((int)floor(t * inv), n_sec - 1).  It is core iff
+ *    fabs(u) <= half; otherwise sky iff fabs(u) >= bg_in && fabs(u) <= bg_out (both sides of the trail pooled).
+ * 4. Sums, five exact integers per (segment, section): n_geom = the core pixels inside the frame, valid or not; n_core and n_sky
+ *    = the valid core and sky pixels; Q_core and Q_sky = the sums of their q.  Integer addition has no order, so crossing
+ *    segments, shared tiles and atomics need no rule.
+ * 5. Section record j, on the host in double, each operation rounded, left to right.  t0 = j * sec_len, t1 = min((j + 1) *
+ *    sec_len, L).  status LFDMI_LC_SEC_EMPTY when n_geom == 0; else LFDMI_LC_SEC_LOW when n_core < min_core or n_sky < min_sky;
+ *    in both the doubles below are NaN and the integers are kept.  Else LFDMI_LC_SEC_OK and, with s_core = (double)Q_core *
+ *    2^-30 and s_sky likewise, sigma = the frame's sky sigma:
+ *        mean = s_core / n_core;  bkg = s_sky / n_sky;  sb = mean - bkg;  flux = sb * n_core;
+ *        flux_err = sigma * sqrt(n_core + n_core * n_core / n_sky);
+ *        rate = sb * (2.0 * half)        (the flux per px of trail length; invalid core pixels are taken at the section's mean);
+ *        rate_err = sigma * sqrt(1.0 / n_core + 1.0 / n_sky) * (2.0 * half);
+ *        coverage = n_core / n_geom.
+ *    The rows j >= n_sec of a segment, and every row of a bad segment, are zero bytes.
+ * 6. Segment record.  status LFDMI_LC_OK, LFDMI_LC_BAD_SEGMENT, LFDMI_LC_TOO_LONG, or LFDMI_LC_EMPTY for a good segment without
+ *    an OK section.  Over the OK sections, j ascending: n_ok, first_ok, last_ok;
+ *        mean_rate = (sum of n_core_j * rate_j) / (sum of n_core_j);   mean_rate_err = 1.0 / sqrt(sum of 1.0 / (rate_err_j *
+ *        rate_err_j));   chi2 = sum of d * d with d = (rate_j - mean_rate) / rate_err_j;   dof = n_ok - 1;
+ *        peak_section = the j of the largest rate (ties: the lowest j), peak_rate its rate;
+ *        length = sum of (t1_j - t0_j);   flux = mean_rate * length;   flux_err = mean_rate_err * length.
+ *    An EMPTY record keeps n_sec, has n_ok = 0, dof = -1, first_ok = last_ok = peak_section = -1 and NaN doubles; a BAD_SEGMENT or
+ *    TOO_LONG record has NaN doubles and zero integers.
+ * No transcendental function appears anywhere in a record (magnitudes are made in Python: lfd_amd/lightcurve.py).
+ *
+ * The device follows the trail masks: it culls 64 x 16 pixel tiles against every segment's outer band (|u| <= bg_out, t in
+ * [0, L], widened by the tile's half extent; k_lc_cull) and runs persistent blocks over the surviving (frame, tile) pairs
+ * (k_lc_render).  A thread loads its pixels once, tests them and converts them to q; the sums of a tile go through a table in
+ * LDS (integer atomics, after the lanes of a wave that share a section have added up) and from there to memory with one integer
+ * atomicAdd per non-zero entry.  There is no float sum and no float atomic on the device. */
+#define LFDMI_LC_MAX_SECTIONS 1024     /* largest max_sections_per_seg */
+#define LFDMI_LC_MAX_BG 64.0           /* largest bg_out in px */
+enum { LFDMI_LC_OK = 0, LFDMI_LC_BAD_SEGMENT = 1, LFDMI_LC_TOO_LONG = 2, LFDMI_LC_EMPTY = 3 };
+enum { LFDMI_LC_SEC_OK = 0, LFDMI_LC_SEC_LOW = 1, LFDMI_LC_SEC_EMPTY = 2 };
+typedef struct {
+    int32_t frame;            /* 0 .. n-1 */
+    int32_t pad;
+    double x1, y1, x2, y2;    /* flipped frame, as lfdmi_mask_segment */
+    double half;              /* the core band: |u| <= half (> 0, finite) */
+    double bg_in, bg_out;     /* the sky bands: bg_in <= |u| <= bg_out (half <= bg_in <= bg_out <= LFDMI_LC_MAX_BG) */
+} lfdmi_lc_segment;
+typedef struct {
+    double sec_len;           /* section length in px (8 .. 4096); default 32 */
+    float clip;               /* a pixel above clip in magnitude is invalid (finite, 0 < clip <= 1024); default 0.125 */
+    int32_t min_core;         /* valid core pixels an OK section needs (>= 1); default 32 */
+    int32_t min_sky;          /* and valid sky pixels (>= 1); default 32 */
+} lfdmi_lc_params;
+typedef struct {
+    int32_t status;           /* LFDMI_LC_SEC_* */
+    int32_t n_geom, n_core, n_sky;
+    int64_t q_core, q_sky;    /* Q_core, Q_sky of step 4 */
+    double t0, t1;            /* the section along the segment, px from (x1, y1) */
+    double mean, bkg, sb, flux, flux_err, rate, rate_err, coverage;
+} lfdmi_lc_section;
+typedef struct {
+    int32_t status;           /* LFDMI_LC_* */
+    int32_t n_sec, n_ok, first_ok, last_ok, peak_section, dof;
+    int32_t pad;
+    double mean_rate, mean_rate_err, chi2, peak_rate, length, flux, flux_err;
+} lfdmi_lc;
+void lfdmi_default_lc_params(lfdmi_lc_params *out);
+/* frames: n frames of h x w, LFDMI_F32 or LFDMI_F32_BE, at loc (LFDMI_HOST / LFDMI_HOST_PINNED: the frames that carry a good
+ * segment are staged on the device as lfdmi_stack_profiles stages them); only read.  mask: NULL, or n x h x w uint8 at the same
+ * loc; skip_bits 0 .. 255.  segs: n_seg records (host), any number per frame.  sigma: NULL (0.025 for every frame) or n positive
+ * finite values.  p NULL: the defaults.  out: n_seg records; sections: n_seg x max_sections_per_seg records (host),
+ * max_sections_per_seg 1 .. LFDMI_LC_MAX_SECTIONS.  LFDMI_ERR_ARG, and no output is touched: a bad dtype or loc, n or n_seg < 0,
+ * h or w outside 1 .. 65536 or h * w > 1e9, a NULL argument that is needed, a bad max_sections_per_seg or skip_bits, parameters
+ * out of range, a frame outside [0, n), a bad sigma.  The call keeps no state (its device memory comes from the stream's pool
+ * and goes back before it returns), refuses while calls are in flight, runs on the context's stream and waits for it once. */
+int lfdmi_light_curves(lfdmi_ctx *ctx, const void *frames, int dtype, int n, int h, int w, int loc, const uint8_t *mask, int skip_bits,
+                       const lfdmi_lc_segment *segs, int n_seg, const float *sigma, const lfdmi_lc_params *p, lfdmi_lc *out,
+                       lfdmi_lc_section *sections, int max_sections_per_seg);
+
 /* ---- faint-trail search -----------------------------------------------------------------------------------------------------
  * The detector finds a trail whose pixels survive the 8-bit conversion; lfdmi_radon_search finds one that is faint in every
  * pixel but long: it sums the frame along every line of a dyadic family (the fast Radon transform of Goetz and Druckmueller /

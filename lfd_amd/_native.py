@@ -41,6 +41,7 @@ SYMBOLS = (
     "lfdmi_default_sky_params", "lfdmi_sky_create", "lfdmi_sky_destroy", "lfdmi_sky_dims", "lfdmi_sky_frames", "lfdmi_sky_normalize",
     "lfdmi_inject_trails",
     "lfdmi_default_mask_params", "lfdmi_mask_trails",
+    "lfdmi_default_lc_params", "lfdmi_light_curves",
     "lfdmi_default_radon_params", "lfdmi_radon_create", "lfdmi_radon_destroy", "lfdmi_radon_dims", "lfdmi_radon_search",
     "lfdmi_default_radon_lines_params", "lfdmi_radon_search_lines",
     "lfdmi_default_radon_short_params", "lfdmi_radon_search_short",
@@ -224,6 +225,34 @@ def make_mask_params(**params):
     return _make_params(MaskParamsStruct, "lfdmi_default_mask_params", "mask", params, _mask_fill)
 
 
+class LcParamsStruct(C.Structure):
+    """lfdmi_lc_params (include/lfdmi.h: light curves)."""
+    _fields_ = [("sec_len", C.c_double), ("clip", C.c_float), ("min_core", C.c_int32), ("min_sky", C.c_int32)]
+
+
+LC_PARAMS = LcParamsStruct
+# lfdmi_lc_segment: one record per segment of lfdmi_light_curves; lfdmi_lc: its result; lfdmi_lc_section: one per section
+LC_SEGMENT_DTYPE = np.dtype([("frame", "<i4"), ("pad", "<i4"), ("x1", "<f8"), ("y1", "<f8"), ("x2", "<f8"), ("y2", "<f8"),
+                             ("half", "<f8"), ("bg_in", "<f8"), ("bg_out", "<f8")])
+LC_DTYPE = np.dtype([("status", "<i4"), ("n_sec", "<i4"), ("n_ok", "<i4"), ("first_ok", "<i4"), ("last_ok", "<i4"),
+                     ("peak_section", "<i4"), ("dof", "<i4"), ("pad", "<i4"),
+                     ("mean_rate", "<f8"), ("mean_rate_err", "<f8"), ("chi2", "<f8"), ("peak_rate", "<f8"), ("length", "<f8"),
+                     ("flux", "<f8"), ("flux_err", "<f8")])
+LC_SECTION_DTYPE = np.dtype([("status", "<i4"), ("n_geom", "<i4"), ("n_core", "<i4"), ("n_sky", "<i4"),
+                             ("q_core", "<i8"), ("q_sky", "<i8"), ("t0", "<f8"), ("t1", "<f8"),
+                             ("mean", "<f8"), ("bkg", "<f8"), ("sb", "<f8"), ("flux", "<f8"), ("flux_err", "<f8"),
+                             ("rate", "<f8"), ("rate_err", "<f8"), ("coverage", "<f8")])
+LC_OK, LC_BAD_SEGMENT, LC_TOO_LONG, LC_EMPTY = 0, 1, 2, 3
+LC_SEC_OK, LC_SEC_LOW, LC_SEC_EMPTY = 0, 1, 2
+LC_MAX_SECTIONS = 1024
+LC_MAX_BG = 64.0
+
+
+def make_lc_params(**params):
+    """lfdmi_default_lc_params with the given fields replaced (unknown names raise)."""
+    return _make_params(LcParamsStruct, "lfdmi_default_lc_params", "light curve", params)
+
+
 class RadonParamsStruct(C.Structure):
     """lfdmi_radon_params (include/lfdmi.h: faint-trail search)."""
     _fields_ = [("bin", C.c_int32), ("min_len", C.c_int32), ("clip", C.c_float), ("threshold", C.c_float)]
@@ -400,6 +429,10 @@ def lib():
         _lib.lfdmi_default_mask_params.argtypes = [C.c_void_p]
         _lib.lfdmi_mask_trails.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        _lib.lfdmi_default_lc_params.restype = None
+        _lib.lfdmi_default_lc_params.argtypes = [C.c_void_p]
+        _lib.lfdmi_light_curves.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                            C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         _lib.lfdmi_default_radon_params.restype = None
         _lib.lfdmi_default_radon_params.argtypes = [C.c_void_p]
         _lib.lfdmi_radon_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
@@ -1183,6 +1216,41 @@ class Context:
         self._chk(self._lib.lfdmi_mask_trails(self._h, _ptr(fr), code, n, h, w, loc, _ptr(sg), len(sg), C.byref(p), _ptr(mask), mloc,
                                               _ptr(stats), _ptr(counts)))
         return mask, stats, counts
+
+    # -- light curves (lfdmi_light_curves) ----------------------------------------------------------------------------------------
+    def light_curves(self, frames, segs, mask=None, skip_bits=0, sigma=None, max_sections=256, pinned=False, native_device=False,
+                     **params):
+        """The brightness along every segment in sections (include/lfdmi.h: light curves).  frames: what ``stack_profiles`` takes
+        ('<f4' or '>f4' numpy, torch CUDA float32, ``DeviceFrames``), only read; segs: LC_SEGMENT_DTYPE records (or anything
+        ``np.asarray`` turns into them), coordinates of the flipped frame; mask: None or the uint8 planes of ``mask_trails`` where
+        the frames are (numpy with host frames, a torch CUDA tensor with device frames), a pixel with ``mask & skip_bits`` is
+        left out; sigma: None (0.025), a number or n values; params: fields of lfdmi_lc_params.  Returns (LC_DTYPE records
+        [n_seg], LC_SECTION_DTYPE records [n_seg, max_sections])."""
+        frames, code, n, h, w, loc = self._frames(frames, pinned, "light_curves", native_device=native_device)
+        sg = np.ascontiguousarray(segs, LC_SEGMENT_DTYPE).reshape(-1)
+        p = make_lc_params(**params)
+        sig = _sigma(sigma, n)
+        m = int(max_sections)
+        if not 1 <= m <= LC_MAX_SECTIONS:
+            raise ValueError(f"max_sections: 1 .. {LC_MAX_SECTIONS}")
+        if mask is not None:
+            shp = tuple(mask.shape)
+            if shp != (n, h, w) and not (n == 1 and shp == (h, w)):      # (one frame may come with a 2-d plane)
+                raise ValueError(f"mask of shape {shp} for frames of shape {(n, h, w)}")
+            if str(mask.dtype).replace("torch.", "") != "uint8":
+                raise TypeError("light_curves needs a uint8 mask")
+            if _is_dev(mask) != (loc == DEVICE):
+                raise ValueError("light_curves needs the mask where the frames are")
+            if _is_dev(mask):
+                if not mask.is_contiguous():
+                    raise ValueError("device tensors must be contiguous")
+            else:
+                mask = np.ascontiguousarray(mask)
+        out = np.zeros(len(sg), LC_DTYPE)
+        sec = np.zeros((len(sg), m), LC_SECTION_DTYPE)
+        self._chk(self._lib.lfdmi_light_curves(self._h, _ptr(frames), code, n, h, w, loc, _ptr(mask), int(skip_bits), _ptr(sg), len(sg),
+                                               _ptr(sig), C.byref(p), _ptr(out), _ptr(sec), m))
+        return out, sec
 
     # -- stacked cross-sections (lfdmi_stack_profiles) ----------------------------------------------------------------------------
     def stack_profiles(self, frames, segments, sigma=None, pinned=False, native_device=False, raw=False, **params):

@@ -276,9 +276,10 @@ class _RadonStage:
     lines' rows)."""
 
     def __init__(self, out, params, sigma, lines=None, lines_params=None, seg_out=None, prof_out=None, stack_params=None,
-                 defocus_out=None, defocus_params=None, short=None, short_out=None):
+                 defocus_out=None, defocus_params=None, short=None, short_out=None, lc=None):
         from ..radon import as_params
         self.out, self.params, self.sigma, self._handles = out, as_params(params), float(sigma), {}
+        self.lc, self.last_lc = lc, {}                # an ``_LcStage``; {position: [(record, sections)]} of the last ``batch`` / ``one``
         self.short, self.short_out = (dict(short) if short is not None else None), short_out
         self.lines, self.seg_out = lines, seg_out
         self.lines_params = dict(lines_params or {}, max_lines=lines) if lines is not None else None
@@ -286,6 +287,18 @@ class _RadonStage:
         self.defocus_out, self.defocus_params, self.pending = defocus_out, defocus_params, []
 
     def _search(self, handle, frames, **where):
+        """the records of a run of frames; with ``lc`` the found lines' light curves too, measured here, where the search and the
+        stacked cross-sections left the frames (``_lc_part``: one list per frame)"""
+        recs = self._search_all(handle, frames, **where)
+        self._lc_part = None
+        if self.lc is not None and self.lines is not None:
+            try:
+                self._lc_part = self.lc.radon(handle.ctx, frames, recs, **where)
+            except Exception as e:  # noqa: BLE001 - the frames' errors entries; their radon rows stay
+                self._lc_part = [e] * len(recs)
+        return recs
+
+    def _search_all(self, handle, frames, **where):
         if self.short is None:
             return self._search_lines(handle, frames, **where)
         srecs, snl, plain = handle.search_short(frames, sigma=self.sigma, plain=True, **self.short, **where)
@@ -327,6 +340,7 @@ class _RadonStage:
     def batch(self, ctx, frames, shape, todo, **where):
         """the frames ``todo`` (ascending positions in ``frames``), searched in runs of neighbours -> {position: record}"""
         out, k = {}, 0
+        self.last_lc = {}
         while k < len(todo):
             m = k
             while m + 1 < len(todo) and todo[m + 1] == todo[m] + 1:
@@ -335,6 +349,8 @@ class _RadonStage:
             part = frames.slice(a, b) if isinstance(frames, _native.DeviceFrames) else frames[a:b]
             recs = self._search(self._handle(ctx, shape, min(b - a, 16)), part, **where)
             out.update(zip(range(a, b), recs))
+            if self._lc_part is not None:
+                self.last_lc.update(zip(range(a, b), self._lc_part))
             k = m + 1
         return out
 
@@ -342,7 +358,9 @@ class _RadonStage:
         """one host frame -> its record"""
         img = _np.ascontiguousarray(img, _np.float32)
         with use_context(*img.shape) as ctx:
-            return self._search(self._handle(ctx, img.shape, 1), img)[0]
+            rec = self._search(self._handle(ctx, img.shape, 1), img)[0]
+        self.last_lc = {0: self._lc_part[0]} if self._lc_part is not None else {}
+        return rec
 
     def row(self, key, rec):
         """the rows of one frame's record: the line if it was found; with ``lines``, every found line in peel order"""
@@ -456,6 +474,54 @@ class _MaskStage:
         self.out.flush()
 
 
+class _LcStage:
+    """The light curves behind the measurements for ``DetectTrails(light_curves=True)`` (include/lfdmi.h: light curves): every
+    results.txt row (source ``detect``) and, with ``radon_lines``, every found faint line (source ``radon``) is measured in
+    sections where its frames are still alive -- beside ``measure_trails`` and beside ``stack_profiles``, on the buffer those
+    read -- and kept in the chunk's slot until ``_emit`` writes one lightcurves.txt row per section that is not EMPTY and one
+    lightcurve_summary.txt row per segment.  The segments are the trail masks' (``_MaskStage.detect_segment`` /
+    ``radon_segments`` with ``half_params``), with the sky bands of ``lightcurve.segments``.  ``sigma``: the frames' sky sigma."""
+
+    def __init__(self, out, summary_out, params, sigma, half_params=None, max_sections=256):
+        from ..lightcurve import as_params
+        self.out, self.summary_out, self.params, self.sigma = out, summary_out, as_params(params), float(sigma)
+        self.max_sections = int(max_sections)
+        self.segs = _MaskStage(None, half_params)       # (the half-width rule and the segments of a record stay in one place)
+
+    def measure(self, ctx, frames, rows, **where):
+        """(frame, x1, y1, x2, y2, half) rows on ``frames`` -> [(record, its sections)] in the rows' order"""
+        from .. import lightcurve
+        if not rows:
+            return []
+        rec, sec = ctx.light_curves(frames, lightcurve.segments(rows), sigma=self.sigma, max_sections=self.max_sections, **where,
+                                    **self.params)
+        return [(rec[k], sec[k]) for k in range(len(rows))]
+
+    def radon(self, ctx, frames, lines, **where):
+        """a run of frames and their ``_RadonStage`` records -> per frame the [(record, sections)] of its found lines"""
+        rows, owner = [], []
+        for j, line in enumerate(lines):
+            for s in self.segs.radon_segments(line):
+                rows.append((j, *s))
+                owner.append(j)
+        out = [[] for _ in lines]
+        for j, item in zip(owner, self.measure(ctx, frames, rows, **where)):
+            out[j].append(item)
+        return out
+
+    def rows(self, key, source, items):
+        from .. import lightcurve
+        for k, (rec, sec) in enumerate(items):
+            text = lightcurve.format_rows(key, source, k, rec, sec)
+            if text:
+                self.out.write("\n".join(text) + "\n")
+            self.summary_out.write(lightcurve.format_summary_row(key, source, k, rec) + "\n")
+
+    def flush(self):
+        self.out.flush()
+        self.summary_out.flush()
+
+
 def _load_frame(run, camcol, filter, field, catalog=True):
     """Frame image (float32, C-contiguous), results-row head, photoObj columns; raises like the
     reference when neither the .fits nor the .fits.bz2 exists (detecttrails.py:81-87)."""
@@ -525,9 +591,11 @@ class _Chunk:
     per-frame product gets a slot here, a step in ``_run_group`` and ``_run_frame``, and its row in ``_emit``."""
 
     def __init__(self, n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon=None,
-                 stars=None, masks=None):
+                 stars=None, masks=None, lc=None):
         self.results, self.errors, self.profiles, self.sky, self.radon, self.stars = results, errors, profiles, sky, radon, stars
         self.masks = masks                            # a ``_MaskStage``: its rows are made in ``_emit``, from the slots below
+        self.lc = lc                                  # a ``_LcStage``; ``lcs[i]``: (source, [(record, sections)]) or the exception
+        self.lcs = [None] * n
         self.shapes = [None] * n                      # the shape of a frame that ran on its own
         self.strecs = [None] * n                      # (frame record, n_extended) of the source finder (``stars``: a ``_StarsStage``)
         self.params_bright, self.params_dim, self.params_removestars = params_bright, params_dim, params_removestars
@@ -540,6 +608,7 @@ class _Chunk:
 def _run_frame(c, i, filter, frame):
     """Frame i on its own, under its own try: ``frame()`` -> (float32 img, cat); sky normalisation if on, detection, and the
     trail measurement of a detected frame."""
+    c.lcs[i] = None
     try:
         img, cat = frame()
         c.shapes[i] = tuple(img.shape)
@@ -553,9 +622,19 @@ def _run_frame(c, i, filter, frame):
                 c.meas[i] = measure_trail(img, c.rows[i][2], cat, filter, c.params_removestars, **c.trail_params)
             except Exception as e:  # noqa: BLE001
                 c.meas[i] = e
+        if c.lc is not None and c.rows[i][0]:
+            try:
+                fr = _np.ascontiguousarray(img, _np.float32)
+                with use_context(*fr.shape) as ctx:
+                    c.lcs[i] = ("detect", c.lc.measure(ctx, fr, [(0, *c.lc.segs.detect_segment(c.rows[i][1], c.meas[i]))]))
+            except Exception as e:  # noqa: BLE001
+                c.lcs[i] = e
         if c.radon is not None and not c.rows[i][0]:
             try:
                 c.rlines[i] = c.radon.one(img)
+                if 0 in c.radon.last_lc:
+                    lc = c.radon.last_lc[0]
+                    c.lcs[i] = lc if isinstance(lc, Exception) else ("radon", lc)
             except Exception as e:  # noqa: BLE001
                 c.rlines[i] = e
     except Exception as e:  # noqa: BLE001 - the reference swallows everything per frame
@@ -595,11 +674,22 @@ def _run_group(c, idx, filter, shape, inflight, source, second, detect_kw=None, 
                 except Exception as e:  # noqa: BLE001
                     for i in idx:
                         c.meas[i] = e
+            if c.lc is not None:                      # the detected frames, on the buffer the measurement read
+                found = [j for j, r in enumerate(recs) if not int(r["status"]) and int(r["found"])]
+                try:
+                    rows = [(j, *c.lc.segs.detect_segment(_detection(recs[j], shape)[1], c.meas[idx[j]])) for j in found]
+                    for j, item in zip(found, c.lc.measure(ctx, frames, rows, **measure_kw)):
+                        c.lcs[idx[j]] = ("detect", [item])
+                except Exception as e:  # noqa: BLE001
+                    for j in found:
+                        c.lcs[idx[j]] = e
             if c.radon is not None:                   # the frames without a detection, where the detect call left them
                 todo = [j for j, r in enumerate(recs) if not int(r["status"]) and not int(r["found"])]
                 try:
                     for j, line in c.radon.batch(ctx, frames, shape, todo, **measure_kw).items():
                         c.rlines[idx[j]] = line
+                    for j, lc in c.radon.last_lc.items():
+                        c.lcs[idx[j]] = lc if isinstance(lc, Exception) else ("radon", lc)
                 except Exception as e:  # noqa: BLE001
                     for j in todo:
                         c.rlines[idx[j]] = e
@@ -649,6 +739,11 @@ def _emit(c, i, key, head, shape):
                 c.masks.rows(key, shp, "radon", c.masks.radon_segments(line))
         except Exception as e:  # noqa: BLE001
             _log_error(c.errors, key, e, c.debug)
+    if c.lc is not None and c.lcs[i] is not None:     # (after the rows it belongs to)
+        if isinstance(c.lcs[i], Exception):
+            _log_error(c.errors, key, c.lcs[i], c.debug)
+        elif c.lcs[i][1]:
+            c.lc.rows(key, *c.lcs[i])
     if not detection or c.profiles is None:
         return
     try:                                              # (results.txt is written before, untouched)
@@ -661,7 +756,7 @@ def _emit(c, i, key, head, shape):
 
 
 def process_field(results, errors, run, camcol, filter, field, params_bright, params_dim,
-                  params_removestars, profiles=None, trail_params=None, sky=None, radon=None, stars=None, masks=None):
+                  params_removestars, profiles=None, trail_params=None, sky=None, radon=None, stars=None, masks=None, lc=None):
     """One frame end to end (reference: detecttrails.py:30-143): locate the frame (or its .bz2),
     read image + header + photoObj, detect, append ``run camcol filter field tai crpix1 crpix2
     crval1 crval2 cd11 cd12 cd21 cd22 x1 y1 x2 y2`` to ``results``; every exception is logged
@@ -672,7 +767,7 @@ def process_field(results, errors, run, camcol, filter, field, params_bright, pa
     ``_StarsStage``; the photoObj file is not opened, the catalogue is what the source finder finds in the frame (after the
     normalisation, if on), and the frame's stars.txt row is written.  ``masks``: a ``_MaskStage``; a results row, and every found
     faint line of ``radon`` with lines, gets its masks.txt row."""
-    c = _Chunk(1, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon, stars, masks)
+    c = _Chunk(1, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon, stars, masks, lc)
     head = None
     try:
         img, head, cat = _load_frame(run, camcol, filter, field, catalog=stars is None)
@@ -716,7 +811,7 @@ def process_fields_batched(results, errors, ids, params_bright, params_dim, para
 
 
 def process_loaded(results, errors, loaded, params_bright, params_dim, params_removestars, profiles=None, trail_params=None, sky=None,
-                   radon=None, stars=None, masks=None):
+                   radon=None, stars=None, masks=None, lc=None):
     """process_fields_batched for a chunk the loader has read (``loader.Loaded``): the frames that sit in pinned memory go to
     the GPU as contiguous same-filter slices of that memory with the matching rows of the padded catalogue arrays (no copy
     of a frame on the host, no per-frame Python), the others take the per-frame path; rows and errors entries come out in
@@ -731,7 +826,7 @@ def process_loaded(results, errors, loaded, params_bright, params_dim, params_re
     import time
     t_in = time.perf_counter()
     n = len(loaded.keys)
-    c = _Chunk(n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon, stars, masks)
+    c = _Chunk(n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon, stars, masks, lc)
     by_slot = {}
     for i in range(n):
         if loaded.error[i] is not None:
@@ -835,6 +930,15 @@ class DetectTrails:
     is on.  ``mask_dir``: each masked frame's plane is written there as ``mask-<run>-<camcol>-<filter>-<field>.npz`` (``bits``,
     ``shape``: ``masks.pack``).  Rank files, resume and ``Jobs`` treat masks.txt like profiles.txt; every other output stays
     byte for byte what it is.
+    ``light_curves=True`` (default off): every results.txt row and, with ``radon_lines=K``, every found faint line is measured in
+    sections along its segment (include/lfdmi.h: light curves; ``lc_params``: dict of lfdmi_lc_params fields) -- the segment and
+    half-width of ``trail_masks`` (``mask_params``), the sky bands of ``lfd_amd.lightcurve.segments`` -- where its frame is still
+    on the device.  ``lightcurves_file`` (default ``<savepath>/lightcurves.txt``) gets one row per section that is not EMPTY:
+    ``run camcol filter field source line section t0 t1 n_geom n_core n_sky bkg flux flux_err rate rate_err status``;
+    ``lightcurve_summary_file`` (default ``<savepath>/lightcurve_summary.txt``) one row per segment: ``run camcol filter field
+    source line status n_sec n_ok mean_rate mean_rate_err chi2 dof peak_section peak_rate length flux flux_err``.  The default
+    ``clip`` (0.125) is the faint-trail units' star cut; a bright trail needs ``lc_params={"clip": ...}`` above its peak.  Rank files,
+    resume and ``Jobs`` treat both like masks.txt; every other output stays byte for byte what it is.
     """
 
     _FILTERS = ('u', 'g', 'r', 'i', 'z')
@@ -898,6 +1002,15 @@ class DetectTrails:
         if self.trail_masks:
             from ..masks import half_width
             half_width(1.0, **self.mask_params)                  # (unknown names raise here, not per frame)
+        self.light_curves = bool(kwargs.get("light_curves", False))
+        self.lightcurves_file = kwargs.get("lightcurves_file", os.path.join(save, "lightcurves.txt"))
+        self.lightcurve_summary_file = kwargs.get("lightcurve_summary_file", os.path.join(save, "lightcurve_summary.txt"))
+        self.lc_params = dict(kwargs.get("lc_params") or {})
+        if self.light_curves:
+            from ..lightcurve import as_params as lc_as_params
+            from ..masks import half_width
+            lc_as_params(self.lc_params)                         # (unknown names and bad values raise here, not per frame)
+            half_width(1.0, **self.mask_params)
         if self.trail_profiles:
             _native.make_trail_params(**self.trail_params)      # (unknown names raise here, not per frame)
         if self.defocus:
@@ -1061,7 +1174,9 @@ class DetectTrails:
                 (open(self.radon_profiles_file + suffix, "a") if self.radon_profiles else contextlib.nullcontext()) as rprof_out, \
                 (open(self.radon_defocus_file + suffix, "a") if self.radon_profiles and self.defocus
                  else contextlib.nullcontext()) as rdef_out, \
-                (open(self.masks_file + suffix, "a") if self.trail_masks else contextlib.nullcontext()) as masks_out:
+                (open(self.masks_file + suffix, "a") if self.trail_masks else contextlib.nullcontext()) as masks_out, \
+                (open(self.lightcurves_file + suffix, "a") if self.light_curves else contextlib.nullcontext()) as lc_out, \
+                (open(self.lightcurve_summary_file + suffix, "a") if self.light_curves else contextlib.nullcontext()) as lcsum_out:
             if self.trail_profiles:
                 profiles = _DefocusTee(profiles, defocus_out, self.defocus_params, self.trail_params)
             prof_kw = {"profiles": profiles, "trail_params": self.trail_params} if self.trail_profiles else {}
@@ -1072,12 +1187,16 @@ class DetectTrails:
             if self.find_stars:
                 sigma = _native.make_sky_params(**self.sky_params).target_sigma if self.normalize else 0.025
                 stars = prof_kw["stars"] = _StarsStage(stars_out, self.stars_params, sigma)
+            lc = None
+            if self.light_curves:
+                sigma = _native.make_sky_params(**self.sky_params).target_sigma if self.normalize else 0.025
+                lc = prof_kw["lc"] = _LcStage(lc_out, lcsum_out, self.lc_params, sigma, self.mask_params)
             radon = None
             if self.radon:
                 sigma = _native.make_sky_params(**self.sky_params).target_sigma if self.normalize else 0.025
                 radon = prof_kw["radon"] = _RadonStage(radon_out, self.radon_params, sigma, self.radon_lines, self.radon_lines_params,
                                                        segments_out, rprof_out, self.stack_params, rdef_out, self.defocus_params,
-                                                       self.radon_short, short_out)
+                                                       self.radon_short, short_out, lc)
             masks = None
             if self.trail_masks:
                 masks = prof_kw["masks"] = _MaskStage(masks_out, self.mask_params, self.mask_dir)
@@ -1098,6 +1217,8 @@ class DetectTrails:
                     radon.flush()
                 if masks is not None:
                     masks.flush()
+                if lc is not None:
+                    lc.flush()
                 progress.write("".join("%s %s %s %s\n" % tuple(k) for k in done_keys))
                 progress.flush()
 
