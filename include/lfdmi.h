@@ -960,7 +960,35 @@ int lfdmi_light_curves(lfdmi_ctx *ctx, const void *frames, int dtype, int n, int
  *    max_lines.
  *    short_threshold defaults to 8.5: the noise-only 372 x 512 frames of step 5's figures peak at 4.6 - 5.81 (bin 1) and
  *    4.18 - 5.05 (bin 2) over all their levels, and 1.4 times the largest is 8.13 (the plain search keeps 8 / 5.33 = 1.5; a
- *    whole frame has 16 times the lines of these crops). */
+ *    whole frame has 16 times the lines of these crops).
+ *
+ * lfdmi_radon_search_wide finds a faint trail that is wide.  A line of step 5 is one binned cell wide; a defocused meteor trail
+ * is 13 px and more, so a one-cell line collects a fraction of its flux and all of the line's noise.  Lines (y, s), (y+1, s),
+ * .. (y+k-1, s) of one orientation follow the same dyadic path shifted by whole rows: they share no pixel, and together they are
+ * a band k cells tall whose sum and count are the sums of k neighbouring entries of the last level.  The band slides one row at
+ * a time.  tests/radon_wide_ref.py restates steps 13 - 16.
+ * 13. Bands.  For orientation q, B_1 = S_q and C_1 = N_q (step 4).  For k = 1, 2, 4, .. while 2k <= max_width:
+ *        B_2k[y][s] = B_k[y][s] + B_k[y+k][s]          (one float32 addition; C_2k the same sum in integers)
+ *    A row above R-1 reads +0 / 0.  Entry (k, q, s, y), y in [-(P-1), R-1], is the band of lines y .. y+k-1 of slope s.
+ *    max_width is a power of two from 1 to 16, in binned cells.
+ * 14. Score.  A band is a candidate when C_k >= k * min_len.  Its score is B_k / (sigma * sqrtf((float)C_k)) with step 5's three
+ *    roundings (C_k is at most 16 * 65535 < 2^24: the conversion is exact).  The frame's band is the candidate of largest score;
+ *    ties go to the lowest (k, q, s, y).  No candidate: LFDMI_RADON_NO_LINE, as in step 6.  found = snr >= wide_threshold.
+ *    wide_threshold defaults to 8: the noise-only 372 x 512 frames of step 5's figures (sixteen seeds) peak, per width 1, 2, 4,
+ *    8, 16, at 5.33, 5.02, 4.91, 4.88, 4.51 (bin 1) and 4.92, 4.65, 4.79, 4.34, 4.13 (bin 2): neighbouring bands of one
+ *    slope share most of their pixels, so a wider band adds few independent entries, and no width raises the ceiling of
+ *    width 1, which is the plain search's; its threshold of 8 (1.5 times the largest) carries over.
+ * 15. Record.  width = k and y0 is the band's lowest line.  x1 .. theta are step 6's mapping of the working points
+ *    (0, y0 + (k-1)/2.0) and (P-1, y0 + s + (k-1)/2.0), the band's centre line (double, on the host).
+ *    width_px = (double)(k * bin) * ((double)(P-1) / sqrt((double)((P-1) (P-1) + s s))): k cells across the column axis times
+ *    the cosine of the angle between the line and that axis.  n_pix, sum and snr are the band's.
+ * 16. Rounds and extent.  Step 8's rounds and step 9's extent with the band in place of the line.  The peel blots the cells
+ *    with y0 + d(c) - hw <= r <= y0 + d(c) + k-1 + hw.  In the extent, a_c is the value of cell (y0 + d(c), c) (+0 where the row
+ *    does not exist), to which the cells of rows +1 .. +k-1 of that column are added in ascending row order, one float32
+ *    addition each, +0 for a row that does not exist; m_c is the same sum in integers, so min_seg counts the band's pixels.
+ *    ex1 .. ey2 are the working points (c1, y0 + d(c1) + (k-1)/2.0) and (c2, y0 + d(c2) + (k-1)/2.0): the segment's ends on
+ *    the centre line.  At k = 1 both are steps 8 and 9 as written: with max_width = 1 every record's fields equal
+ *    lfdmi_radon_search_lines' bit for bit (its threshold then is wide_threshold). */
 enum { LFDMI_RADON_OK = 0, LFDMI_RADON_NO_LINE = 1 };
 #define LFDMI_RADON_MAX_LINES 8
 typedef struct {
@@ -1053,6 +1081,40 @@ void lfdmi_default_radon_short_params(lfdmi_radon_short_params *out);
 int lfdmi_radon_search_short(lfdmi_ctx *ctx, lfdmi_radon *radon, const void *frames, int dtype, int n, int loc, const float *sigma,
                              const lfdmi_radon_short_params *sp, lfdmi_radon_short *lines, int32_t *n_lines,
                              lfdmi_radon_result *plain);
+#define LFDMI_RADON_MAX_WIDTH 16
+typedef struct {
+    int32_t max_width;        /* the widest band scored, in binned cells: a power of two, 1 .. LFDMI_RADON_MAX_WIDTH; default 8 */
+    int32_t max_lines;        /* records per frame at most, 1 .. LFDMI_RADON_MAX_LINES; default 4 */
+    int32_t peel_halfwidth;   /* half-width in pixels blotted beyond a found band's two edges (>= 0); default 8 */
+    int32_t min_seg;          /* valid pixels a segment of the band needs, 1 .. the handle's min_len; default 64 */
+    float wide_threshold;     /* found = snr >= wide_threshold; finite and > 0; default 8 (step 14) */
+    int32_t pad;
+} lfdmi_radon_wide_params;
+typedef struct {
+    int32_t status;       /* as in lfdmi_radon_line, down to ey2: y0 is the band's lowest line, x1 .. theta and ex1 .. ey2 lie on */
+    int32_t found;        /* its centre line (steps 15, 16), n_pix, sum and snr are the band's, found = snr >= wide_threshold */
+    int32_t q, y0, s;
+    int32_t n_pix;
+    float sum, snr;
+    double x1, y1, x2, y2, rho, theta;
+    int32_t c1, c2;
+    int32_t seg_n_pix;
+    int32_t pad;
+    float seg_sum, seg_snr;
+    double ex1, ey1, ex2, ey2;
+    int32_t width, pad2;  /* k: the band's width in binned cells */
+    double width_px;      /* its width across the line in pixels (step 15) */
+} lfdmi_radon_wide;
+void lfdmi_default_radon_wide_params(lfdmi_radon_wide_params *out);
+/* lfdmi_radon_search with steps 13 - 16: frames, dtype, n, loc and sigma as there.  wp NULL: the defaults.  lines, n_lines and
+ * plain as in lfdmi_radon_search_short: the width-1 pass of round 0 is exactly step 5, and its best is kept beside the overall
+ * one.  Out-of-range parameters: LFDMI_ERR_ARG, and nothing runs.  On its first call the handle allocates what
+ * lfdmi_radon_search_lines' first call does (if it has not) and the band kernel's partial records; lfdmi_radon_dims counts them
+ * from then on.  The frames are only read; the call refuses while calls are in flight, runs on the context's stream and waits
+ * for it once per round of each chunk. */
+int lfdmi_radon_search_wide(lfdmi_ctx *ctx, lfdmi_radon *radon, const void *frames, int dtype, int n, int loc, const float *sigma,
+                            const lfdmi_radon_wide_params *wp, lfdmi_radon_wide *lines, int32_t *n_lines,
+                            lfdmi_radon_result *plain);
 
 /* ---- stacked cross-sections -------------------------------------------------------------------------------------------------
  * lfdmi_measure_trails needs every 64-position piece of a trail to stand 5 sigma on its own; a trail of the faint-trail search

@@ -45,6 +45,7 @@ SYMBOLS = (
     "lfdmi_default_radon_params", "lfdmi_radon_create", "lfdmi_radon_destroy", "lfdmi_radon_dims", "lfdmi_radon_search",
     "lfdmi_default_radon_lines_params", "lfdmi_radon_search_lines",
     "lfdmi_default_radon_short_params", "lfdmi_radon_search_short",
+    "lfdmi_default_radon_wide_params", "lfdmi_radon_search_wide",
     "lfdmi_default_stack_params", "lfdmi_stack_profiles",
     "lfdmi_default_stars_params", "lfdmi_find_stars", "lfdmi_stars_catalog",
 )
@@ -313,6 +314,26 @@ def make_radon_short_params(**params):
     return _make_params(RadonShortParamsStruct, "lfdmi_default_radon_short_params", "radon short", params)
 
 
+class RadonWideParamsStruct(C.Structure):
+    """lfdmi_radon_wide_params (include/lfdmi.h: faint-trail search, steps 13 - 16)."""
+    _fields_ = [("max_width", C.c_int32), ("max_lines", C.c_int32), ("peel_halfwidth", C.c_int32), ("min_seg", C.c_int32),
+                ("wide_threshold", C.c_float), ("pad", C.c_int32)]
+
+
+class RadonWide(C.Structure):
+    """lfdmi_radon_wide: one record per frame and round of lfdmi_radon_search_wide."""
+    _fields_ = RadonLine._fields_ + [("width", C.c_int32), ("pad2", C.c_int32), ("width_px", C.c_double)]
+
+
+RADON_WIDE_DTYPE = np.dtype(RADON_LINE_DTYPE.descr + [("width", "<i4"), ("pad2", "<i4"), ("width_px", "<f8")])
+RADON_MAX_WIDTH = 16
+
+
+def make_radon_wide_params(**params):
+    """lfdmi_default_radon_wide_params with the given fields replaced (unknown names raise)."""
+    return _make_params(RadonWideParamsStruct, "lfdmi_default_radon_wide_params", "radon wide", params)
+
+
 class StackParamsStruct(C.Structure):
     """lfdmi_stack_params (include/lfdmi.h: stacked cross-sections)."""
     _fields_ = [("wing", C.c_int32), ("n_iter", C.c_int32), ("min_cols", C.c_int32), ("clip", C.c_float),
@@ -446,6 +467,10 @@ def lib():
                                                   C.c_void_p, C.c_void_p]
         _lib.lfdmi_default_radon_short_params.restype = None
         _lib.lfdmi_default_radon_short_params.argtypes = [C.c_void_p]
+        _lib.lfdmi_default_radon_wide_params.restype = None
+        _lib.lfdmi_default_radon_wide_params.argtypes = [C.c_void_p]
+        _lib.lfdmi_radon_search_wide.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.lfdmi_radon_search_short.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.lfdmi_default_stack_params.restype = None
@@ -1490,4 +1515,23 @@ class Radon(_Handle):
         pl = np.zeros(n, RADON_DTYPE) if plain else None
         ctx._chk(self._lib.lfdmi_radon_search_short(ctx._h, r, _ptr(frames), code, n, loc, _ptr(sg), C.byref(sp), _ptr(res),
                                                     _ptr(nl), _ptr(pl)))
+        return (res, nl, pl) if plain else (res, nl)
+
+    def search_wide(self, frames, sigma=None, plain=False, pinned=False, native_device=False, **params):
+        """Wide trails: bands of 1, 2, 4, .. ``max_width`` neighbouring lines of the last level scored as one, the best band's
+        centre line, width and extent, and peeling rounds as in ``search_lines`` (include/lfdmi.h: faint-trail search, steps
+        13 - 16); frames and sigma as in ``search``, ``params`` the fields of lfdmi_radon_wide_params.  Returns
+        (RADON_WIDE_DTYPE records [n, max_lines], n_lines [n]) and, with ``plain``, a third item: the RADON_DTYPE records
+        ``search`` returns for these frames.  The first call allocates the rounds' buffers and the partial records;
+        ``dims()`` counts them from then on."""
+        r, ctx = self._open(), self.ctx
+        wp = make_radon_wide_params(**params)
+        frames, code, n, h, w, loc = self._frames(frames, pinned, "Radon.search_wide", native_device=native_device)
+        sg = _sigma(sigma, n)
+        k = max(1, min(int(wp.max_lines), RADON_MAX_LINES))      # (out of range: the library refuses before it writes)
+        res = np.zeros((n, k), RADON_WIDE_DTYPE)
+        nl = np.zeros(n, np.int32)
+        pl = np.zeros(n, RADON_DTYPE) if plain else None
+        ctx._chk(self._lib.lfdmi_radon_search_wide(ctx._h, r, _ptr(frames), code, n, loc, _ptr(sg), C.byref(wp), _ptr(res),
+                                                   _ptr(nl), _ptr(pl)))
         return (res, nl, pl) if plain else (res, nl)

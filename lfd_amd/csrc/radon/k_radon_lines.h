@@ -39,15 +39,18 @@ __device__ __forceinline__ size_t rad_cell(const RadonDev &p, int q, int r, int 
     return (size_t)c * p.wb + (p.wb - 1 - r);
 }
 
-// pre / cnt: pstride = max(Hb, Wb) + 1 values per line
+// pre / cnt: pstride = max(Hb, Wb) + 1 values per line.  width: NULL, or each line's band width k (step 16): a_c, m_c then sum
+// the cells of rows y0 + d(c) .. y0 + d(c) + k-1, rows ascending
 __global__ __launch_bounds__(RAD_THREADS) void k_radon_extent(const float *__restrict__ V, const uint16_t *__restrict__ M, RadonDev p,
                                                               const RadonLineDev *__restrict__ ln, const float *__restrict__ sigma,
-                                                              int min_seg, float *pre, int *cnt, int pstride, RadonExtDev *__restrict__ ext) {
+                                                              int min_seg, float *pre, int *cnt, int pstride, RadonExtDev *__restrict__ ext,
+                                                              const int *__restrict__ width) {
     __shared__ float ta[RADL_TILE];
     __shared__ int tm[RADL_TILE];
     __shared__ RadonExtDev red[RAD_THREADS];
     const int tid = threadIdx.x;
     const RadonLineDev L = ln[blockIdx.x];
+    const int wk = width ? width[blockIdx.x] : 1;
     const int o = L.q >> 1, R = p.R[o], C = p.C[o], P = p.P[o];
     const float *Vf = V + (size_t)L.slot * p.hb * p.wb;
     const uint16_t *Mf = M + (size_t)L.slot * p.hb * p.wb;
@@ -66,6 +69,17 @@ __global__ __launch_bounds__(RAD_THREADS) void k_radon_extent(const float *__res
                 const size_t a = rad_cell(p, L.q, r, c);
                 v = Vf[a];
                 m = Mf[a];
+            }
+            for (int u = 1; u < wk; u++) {
+                float v2 = 0.0f;
+                int m2 = 0;
+                if (r + u >= 0 && r + u < R) {
+                    const size_t a = rad_cell(p, L.q, r + u, c);
+                    v2 = Vf[a];
+                    m2 = Mf[a];
+                }
+                v = v + v2;
+                m += m2;
             }
             ta[e] = v;
             tm[e] = m;
@@ -158,17 +172,20 @@ template <> struct RadCell<1> {
 };
 
 // Slot blockIdx.z of the output = slot ln[blockIdx.z].slot of the input without the band of half-width hw cells around the line.
+// width: NULL, or each line's band width k (step 16): the blot then reaches hw cells beyond lines y0 and y0 + k-1.
 // VEC = 8 needs Wb a multiple of 8 (then every row of V starts on 16 bytes and every row of M too); VEC = 1 takes any Wb.
 template <int VEC>
 __global__ __launch_bounds__(RAD_THREADS) void k_radon_peel(const float *__restrict__ Vin, const uint16_t *__restrict__ Min, RadonDev p,
                                                             const RadonLineDev *__restrict__ ln, int hw, float *__restrict__ Vout,
-                                                            uint16_t *__restrict__ Mout) {
+                                                            uint16_t *__restrict__ Mout, const int *__restrict__ width) {
     __shared__ int cc[RAD_THREADS * VEC];   // q = 0, 1: the band's centre row of V in each column of the tile
     __shared__ int cr[RADL_ROWS];           // q = 2, 3: the band's centre column of V in each row of the tile
     const int tid = threadIdx.x;
     const RadonLineDev L = ln[blockIdx.z];
     const int i0 = (int)blockIdx.x * RAD_THREADS * VEC, j0 = (int)blockIdx.y * RADL_ROWS;
     const int P = p.P[L.q >> 1];
+    // (the band's further lines lie at higher working rows: below in V for the flipped orientations 1 and 3)
+    const int more = hw + (width ? width[blockIdx.z] : 1) - 1, lo = L.q & 1 ? -more : -hw, hi = L.q & 1 ? hw : more;
     if (L.q < 2) {
         for (int e = tid; e < RAD_THREADS * VEC; e += RAD_THREADS) {
             const int r = L.y0 + rad_path(i0 + e, L.s, P);
@@ -203,7 +220,7 @@ __global__ __launch_bounds__(RAD_THREADS) void k_radon_peel(const float *__restr
 #pragma unroll
         for (int k = 0; k < VEC; k++) {
             const int dist = byrow ? i + k - ctr : j - ctrs[k];
-            const bool blot = dist >= -hw && dist <= hw;
+            const bool blot = dist >= lo && dist <= hi;
             v[k] = blot ? 0.0f : v[k];
             m[k] = blot ? 0u : m[k];
         }

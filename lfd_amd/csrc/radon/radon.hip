@@ -15,6 +15,7 @@
 #include "k_radon.h"
 #include "k_radon_lines.h"
 #include "k_radon_short.h"
+#include "k_radon_wide.h"
 
 struct lfdmi_radon {
     lfdmi_ctx *ctx = nullptr;   // lfdmi_radon_search only: destroy does not touch the context (it may be gone by then)
@@ -37,6 +38,12 @@ struct lfdmi_radon {
     // min_strip = 64, which holds every other) and the frames' short records
     RadonShortPart *spart = nullptr;
     RadonShortRec *srec = nullptr;
+    // lfdmi_radon_search_wide only, allocated on its first call: k_radon_wide's partial records (two per workgroup), the
+    // frames' band records and the found bands' widths
+    int nwp[2] = {0, 0}, wstride = 0;
+    RadonWidePart *wpart = nullptr;
+    RadonWideRec *wrec = nullptr;
+    int *wid = nullptr;
     int64_t bytes = 0;
 };
 
@@ -87,7 +94,9 @@ extern "C" int lfdmi_radon_create(lfdmi_ctx *ctx, int h, int w, int max_frames, 
     for (int o = 0; o < 2; o++) {
         const int n = p.P[o] / 2, tt = std::min(RAD_TT, n);
         s->np[o] = ceil_div(p.R[o] + p.P[o] - 1, RAD_Y) * (p.P[o] / (2 * tt));
+        s->nwp[o] = ceil_div(p.R[o] + p.P[o] - 1, RADW_Y) * (p.P[o] / std::min(RADW_S, p.P[o]));
     }
+    s->wstride = std::max(s->nwp[0], s->nwp[1]);
     p.part_stride = std::max(s->np[0], s->np[1]);
     auto run = [&]() -> int {
         const size_t F = (size_t)max_frames, px = (size_t)hb * wb, E = (size_t)p.frame_elems;
@@ -115,7 +124,7 @@ extern "C" void lfdmi_radon_destroy(lfdmi_radon *s) {
     DeviceGuard on(s->device);   // the caller's current device stays what it was
     for (void *x : {(void *)s->V, (void *)s->M, (void *)s->S[0], (void *)s->S[1], (void *)s->N[0], (void *)s->N[1], (void *)s->sigma,
                     (void *)s->stage, (void *)s->part, (void *)s->rec, (void *)s->V2, (void *)s->M2, (void *)s->pre, (void *)s->cnt,
-                    (void *)s->lnd, (void *)s->ext, (void *)s->spart, (void *)s->srec})
+                    (void *)s->lnd, (void *)s->ext, (void *)s->spart, (void *)s->srec, (void *)s->wpart, (void *)s->wrec, (void *)s->wid})
         if (x) hipFree(x);
     delete s;
 }
@@ -182,9 +191,11 @@ static RadonShortDev radon_short_layout(const RadonDev &p, int min_strip) {
 
 // definition steps 3 - 6 of the nf frames in V, M (sigma in s->sigma): their records in s->rec.  sd: the short search's mode --
 // the levels it lists score what they store (step 10) and the frames' short records go to s->srec; `last` false then leaves
-// the last level and s->rec out (a peel round of the short search has no use for them)
+// the last level and s->rec out (a peel round of the short search has no use for them).  max_width > 0: the wide search's mode --
+// the last level is stored by the non-scoring instance into the plane set that does not hold its input, k_radon_wide scores
+// its bands (steps 13, 14), and k_radon_wide_finish writes the frames' band records to s->wrec and the plain ones to s->rec
 static int radon_transform(lfdmi_ctx *ctx, lfdmi_radon *s, const RadonDev &p, const float *V, const uint16_t *M, int nf, hipStream_t st,
-                           const RadonShortDev *sd = nullptr, bool last = true) {
+                           const RadonShortDev *sd = nullptr, bool last = true, int max_width = 0) {
     {
         int gx = 0, gy = 0;
         for (int o = 0; o < 2; o++) {
@@ -214,13 +225,30 @@ static int radon_transform(lfdmi_ctx *ctx, lfdmi_radon *s, const RadonDev &p, co
         if (!last) continue;
         const int tt = std::min(RAD_TT, lv);
         const dim3 grid(ceil_div(R + P - 1, RAD_Y), P / (2 * tt), nf * 2);
+        if (max_width > 0) {
+            // (a level n writes rows -(2n-1) .. R-1 of width 2n: the last one fills its whole (R + P - 1) x P plane, [y][s])
+            if (lv >= RAD_TT)
+                k_radon_level<4, false><<<grid, RAD_THREADS, 0, st>>>(s->S[cur], s->N[cur], s->S[cur ^ 1], s->N[cur ^ 1], p, o, lv, nullptr, nullptr,
+                                                                      nullptr, 0, 0);
+            else
+                k_radon_level<1, false><<<grid, RAD_THREADS, 0, st>>>(s->S[cur], s->N[cur], s->S[cur ^ 1], s->N[cur ^ 1], p, o, lv, nullptr, nullptr,
+                                                                      nullptr, 0, 0);
+            ULAUNCH("k_radon_level (last, stored)");
+            const dim3 wgrid(ceil_div(R + P - 1, RADW_Y), P / std::min(RADW_S, P), nf * 2);
+            k_radon_wide<<<wgrid, RAD_THREADS, 0, st>>>(s->S[cur ^ 1], s->N[cur ^ 1], p, o, max_width, s->sigma, s->wpart, s->wstride);
+            ULAUNCH("k_radon_wide");
+            continue;
+        }
         if (lv >= RAD_TT)
             k_radon_level<4, true><<<grid, RAD_THREADS, 0, st>>>(s->S[cur], s->N[cur], nullptr, nullptr, p, o, lv, s->sigma, s->part, nullptr, 0, 0);
         else
             k_radon_level<1, true><<<grid, RAD_THREADS, 0, st>>>(s->S[cur], s->N[cur], nullptr, nullptr, p, o, lv, s->sigma, s->part, nullptr, 0, 0);
         ULAUNCH("k_radon_level (last)");
     }
-    if (last) {
+    if (last && max_width > 0) {
+        k_radon_wide_finish<<<nf, RAD_THREADS, 0, st>>>(s->wpart, s->wstride, s->nwp[0], s->nwp[1], s->wrec, s->rec);
+        ULAUNCH("k_radon_wide_finish");
+    } else if (last) {
         k_radon_finish<<<nf, RAD_THREADS, 0, st>>>(s->part, p, s->np[0], s->np[1], s->rec);
         ULAUNCH("k_radon_finish");
     }
@@ -406,7 +434,7 @@ extern "C" int lfdmi_radon_search_lines(lfdmi_ctx *ctx, lfdmi_radon *s, const vo
             if (!nl) break;
             hx[b].resize(nl);
             UHIP(hipMemcpyAsync(s->lnd, hl[b].data(), (size_t)nl * sizeof(RadonLineDev), hipMemcpyHostToDevice, st));
-            k_radon_extent<<<nl, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, s->sigma, lq.min_seg, s->pre, s->cnt, pstride, s->ext);
+            k_radon_extent<<<nl, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, s->sigma, lq.min_seg, s->pre, s->cnt, pstride, s->ext, nullptr);
             ULAUNCH("k_radon_extent");
             UHIP(hipMemcpyAsync(hx[b].data(), s->ext, (size_t)nl * sizeof(RadonExtDev), hipMemcpyDeviceToHost, st));
             pending = k;
@@ -414,10 +442,10 @@ extern "C" int lfdmi_radon_search_lines(lfdmi_ctx *ctx, lfdmi_radon *s, const vo
             // the found frames go on: slot e of the other set is the frame of line e
             if (p.wb % 8 == 0) {
                 const dim3 grid(ceil_div(p.wb, RAD_THREADS * 8), ceil_div(p.hb, RADL_ROWS), nl);
-                k_radon_peel<8><<<grid, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, hw, Vs[cur ^ 1], Ms[cur ^ 1]);
+                k_radon_peel<8><<<grid, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, hw, Vs[cur ^ 1], Ms[cur ^ 1], nullptr);
             } else {
                 const dim3 grid(ceil_div(p.wb, RAD_THREADS), ceil_div(p.hb, RADL_ROWS), nl);
-                k_radon_peel<1><<<grid, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, hw, Vs[cur ^ 1], Ms[cur ^ 1]);
+                k_radon_peel<1><<<grid, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, hw, Vs[cur ^ 1], Ms[cur ^ 1], nullptr);
             }
             ULAUNCH("k_radon_peel");
             UHIP(hipMemcpyAsync(s->sigma, hs[b].data(), (size_t)nl * sizeof(float), hipMemcpyHostToDevice, st));
@@ -534,17 +562,183 @@ extern "C" int lfdmi_radon_search_short(lfdmi_ctx *ctx, lfdmi_radon *s, const vo
             if (!nl) break;
             hx[b].resize(nl);
             UHIP(hipMemcpyAsync(s->lnd, hl[b].data(), (size_t)nl * sizeof(RadonLineDev), hipMemcpyHostToDevice, st));
-            k_radon_extent<<<nl, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, s->sigma, sq.min_seg, s->pre, s->cnt, pstride, s->ext);
+            k_radon_extent<<<nl, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, s->sigma, sq.min_seg, s->pre, s->cnt, pstride, s->ext, nullptr);
             ULAUNCH("k_radon_extent");
             UHIP(hipMemcpyAsync(hx[b].data(), s->ext, (size_t)nl * sizeof(RadonExtDev), hipMemcpyDeviceToHost, st));
             pending = k;
             if (k + 1 == K) break;
             if (p.wb % 8 == 0) {
                 const dim3 grid(ceil_div(p.wb, RAD_THREADS * 8), ceil_div(p.hb, RADL_ROWS), nl);
-                k_radon_peel<8><<<grid, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, hw, Vs[cur ^ 1], Ms[cur ^ 1]);
+                k_radon_peel<8><<<grid, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, hw, Vs[cur ^ 1], Ms[cur ^ 1], nullptr);
             } else {
                 const dim3 grid(ceil_div(p.wb, RAD_THREADS), ceil_div(p.hb, RADL_ROWS), nl);
-                k_radon_peel<1><<<grid, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, hw, Vs[cur ^ 1], Ms[cur ^ 1]);
+                k_radon_peel<1><<<grid, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, hw, Vs[cur ^ 1], Ms[cur ^ 1], nullptr);
+            }
+            ULAUNCH("k_radon_peel");
+            UHIP(hipMemcpyAsync(s->sigma, hs[b].data(), (size_t)nl * sizeof(float), hipMemcpyHostToDevice, st));
+            alive = found_frames[b];
+            cur ^= 1;
+        }
+        if (pending >= 0) {
+            UHIP(hipStreamSynchronize(st));
+            segments(pending);
+        }
+    }
+    if (plain)
+        for (int i = 0; i < n; i++) {
+            memset(&plain[i], 0, sizeof(plain[i]));
+            radon_fill(s, p, hplain[i], plain[i]);
+        }
+    return 0;
+}
+
+extern "C" void lfdmi_default_radon_wide_params(lfdmi_radon_wide_params *o) {
+    if (!o) return;
+    memset(o, 0, sizeof(*o));
+    o->max_width = 8; o->max_lines = 4; o->peel_halfwidth = 8; o->min_seg = 64; o->wide_threshold = 8.0f;
+}
+
+// radon_point for a working row between two cells (a band's centre line, steps 15 and 16)
+static void radon_point_mid(const RadonDev &p, int q, int c, double r, double &x, double &y) {
+    double i, j;
+    if (q == 0) { i = c; j = r; }
+    else if (q == 1) { i = c; j = (double)(p.hb - 1) - r; }
+    else if (q == 2) { i = r; j = c; }
+    else { i = (double)(p.wb - 1) - r; j = c; }
+    x = (double)p.b * i + (double)(p.b - 1) / 2.0;
+    y = (double)p.b * j + (double)(p.b - 1) / 2.0;
+}
+
+// the record of a frame's best band as the caller gets it (o zeroed before): steps 14 and 15
+static void radon_wide_fill(const RadonDev &p, const RadonWideRec &r, float threshold, lfdmi_radon_wide &o) {
+    o.status = r.status;
+    if (o.status != LFDMI_RADON_OK) return;
+    o.q = r.q; o.y0 = r.y0; o.s = r.s; o.n_pix = r.n_pix;
+    o.sum = r.sum; o.snr = r.snr;
+    o.width = r.k;
+    o.found = o.snr >= threshold;
+    const int P = p.P[o.q >> 1];
+    const double mid = (double)(o.width - 1) / 2.0;
+    radon_point_mid(p, o.q, 0, (double)o.y0 + mid, o.x1, o.y1);
+    radon_point_mid(p, o.q, P - 1, (double)(o.y0 + o.s) + mid, o.x2, o.y2);
+    double theta = atan2(-(o.x2 - o.x1), o.y2 - o.y1);
+    const double pi = 3.141592653589793;
+    if (theta < 0.0) theta += pi;
+    if (theta >= pi) theta -= pi;
+    o.theta = theta;
+    o.rho = o.x1 * cos(theta) + o.y1 * sin(theta);
+    const long long run = P - 1, rise = o.s;
+    o.width_px = (double)(o.width * p.b) * ((double)run / sqrt((double)(run * run + rise * rise)));
+}
+
+extern "C" int lfdmi_radon_search_wide(lfdmi_ctx *ctx, lfdmi_radon *s, const void *frames, int dtype, int n, int loc, const float *sigma,
+                                       const lfdmi_radon_wide_params *wp, lfdmi_radon_wide *lines, int32_t *n_lines,
+                                       lfdmi_radon_result *plain) {
+    RadonCall c{ctx, s, "lfdmi_radon_search_wide"};
+    int rc = c.begin();
+    if (rc) return rc;
+    lfdmi_radon_wide_params wq;
+    if (wp) wq = *wp; else lfdmi_default_radon_wide_params(&wq);
+    if (wq.max_width < 1 || wq.max_width > LFDMI_RADON_MAX_WIDTH || (wq.max_width & (wq.max_width - 1)) || wq.max_lines < 1 ||
+        wq.max_lines > LFDMI_RADON_MAX_LINES || wq.peel_halfwidth < 0 || wq.min_seg < 1 || wq.min_seg > s->par.min_len ||
+        !std::isfinite(wq.wide_threshold) || !(wq.wide_threshold > 0))
+        return ctx_fail(ctx, LFDMI_ERR_ARG, "radon wide params out of range (include/lfdmi.h: lfdmi_radon_wide_params)");
+    if ((rc = c.args(frames, lines && n_lines, dtype, n, loc, sigma))) return rc;
+    if (n == 0) return 0;
+    const RadonDev &p = c.p;
+    const std::vector<float> &hsig = c.hsig;
+    const int CH = c.CH, K = wq.max_lines;
+    const int hw = (int)(((int64_t)wq.peel_halfwidth + p.b - 1) / p.b);
+    const int pstride = std::max(p.hb, p.wb) + 1;
+    if ((rc = c.stage()) || (rc = radon_rounds_alloc(ctx, s, pstride))) return rc;
+    {   // (each buffer on its own: a call that failed between two allocates only what is missing)
+        const size_t F = (size_t)CH, np = (size_t)4 * s->wstride * 2;
+        // (into a local first: a failed hipMalloc must leave the handle's pointer null for the next call and for destroy)
+        if (!s->wpart) {
+            void *m = nullptr;
+            UHIP(hipMalloc(&m, F * np * sizeof(RadonWidePart)));
+            s->wpart = (RadonWidePart *)m;
+            s->bytes += (int64_t)(F * np * sizeof(RadonWidePart));
+        }
+        if (!s->wrec) {
+            void *m = nullptr;
+            UHIP(hipMalloc(&m, F * sizeof(RadonWideRec)));
+            s->wrec = (RadonWideRec *)m;
+            s->bytes += (int64_t)(F * sizeof(RadonWideRec));
+        }
+        if (!s->wid) {
+            void *m = nullptr;
+            UHIP(hipMalloc(&m, F * sizeof(int)));
+            s->wid = (int *)m;
+            s->bytes += (int64_t)(F * sizeof(int));
+        }
+    }
+    hipStream_t st = c.st;
+    memset(lines, 0, (size_t)n * K * sizeof(*lines));
+    memset(n_lines, 0, (size_t)n * sizeof(*n_lines));
+    float *Vs[2] = {s->V, s->V2};
+    uint16_t *Ms[2] = {s->M, s->M2};
+    std::vector<RadonWideRec> hrec(CH);
+    std::vector<RadonRec> hplain(plain ? n : 0);
+    // (round k's host buffers are read or written by copies that finish with round k + 1's wait: two of each alternate)
+    std::vector<RadonLineDev> hl[2];
+    std::vector<RadonExtDev> hx[2];
+    std::vector<float> hs[2];
+    std::vector<int> alive, found_frames[2], hwid[2];
+    for (int c0 = 0; c0 < n; c0 += CH) {
+        const int nf = std::min(CH, n - c0);
+        if ((rc = c.chunk(c0, nf))) return rc;
+        alive.resize(nf);
+        for (int a = 0; a < nf; a++) alive[a] = c0 + a;     // slot -> frame
+        int cur = 0, pending = -1;
+        auto segments = [&](int k) {
+            const int b = k & 1;
+            for (size_t e = 0; e < found_frames[b].size(); e++) {
+                lfdmi_radon_wide &o = lines[(size_t)found_frames[b][e] * K + k];
+                const RadonExtDev &x = hx[b][e];
+                const int P = p.P[o.q >> 1];
+                const double mid = (double)(o.width - 1) / 2.0;
+                o.c1 = x.c1; o.c2 = x.c2; o.seg_n_pix = x.n; o.seg_sum = x.sum; o.seg_snr = x.snr;
+                radon_point_mid(p, o.q, o.c1, (double)(o.y0 + radon_path(o.c1, o.s, P)) + mid, o.ex1, o.ey1);
+                radon_point_mid(p, o.q, o.c2, (double)(o.y0 + radon_path(o.c2, o.s, P)) + mid, o.ex2, o.ey2);
+            }
+        };
+        for (int k = 0; k < K && !alive.empty(); k++) {
+            const int na = (int)alive.size(), b = k & 1;
+            rc = radon_transform(ctx, s, p, Vs[cur], Ms[cur], na, st, nullptr, true, wq.max_width);
+            if (rc) return rc;
+            UHIP(hipMemcpyAsync(hrec.data(), s->wrec, (size_t)na * sizeof(RadonWideRec), hipMemcpyDeviceToHost, st));
+            // round 0's width-1 pass is step 5: the plain search's record comes with it
+            if (k == 0 && plain) UHIP(hipMemcpyAsync(hplain.data() + c0, s->rec, (size_t)na * sizeof(RadonRec), hipMemcpyDeviceToHost, st));
+            UHIP(hipStreamSynchronize(st));
+            if (pending >= 0) { segments(pending); pending = -1; }
+            hl[b].clear(); found_frames[b].clear(); hs[b].clear(); hwid[b].clear();
+            for (int a = 0; a < na; a++) {
+                lfdmi_radon_wide &o = lines[(size_t)alive[a] * K + k];
+                radon_wide_fill(p, hrec[a], wq.wide_threshold, o);
+                if (!o.found) continue;
+                n_lines[alive[a]] = k + 1;
+                hl[b].push_back(RadonLineDev{a, o.q, o.y0, o.s});
+                hwid[b].push_back(o.width);
+                found_frames[b].push_back(alive[a]);
+                hs[b].push_back(hsig[alive[a]]);
+            }
+            const int nl = (int)hl[b].size();
+            if (!nl) break;
+            hx[b].resize(nl);
+            UHIP(hipMemcpyAsync(s->lnd, hl[b].data(), (size_t)nl * sizeof(RadonLineDev), hipMemcpyHostToDevice, st));
+            UHIP(hipMemcpyAsync(s->wid, hwid[b].data(), (size_t)nl * sizeof(int), hipMemcpyHostToDevice, st));
+            k_radon_extent<<<nl, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, s->sigma, wq.min_seg, s->pre, s->cnt, pstride, s->ext, s->wid);
+            ULAUNCH("k_radon_extent");
+            UHIP(hipMemcpyAsync(hx[b].data(), s->ext, (size_t)nl * sizeof(RadonExtDev), hipMemcpyDeviceToHost, st));
+            pending = k;
+            if (k + 1 == K) break;
+            if (p.wb % 8 == 0) {
+                const dim3 grid(ceil_div(p.wb, RAD_THREADS * 8), ceil_div(p.hb, RADL_ROWS), nl);
+                k_radon_peel<8><<<grid, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, hw, Vs[cur ^ 1], Ms[cur ^ 1], s->wid);
+            } else {
+                const dim3 grid(ceil_div(p.wb, RAD_THREADS), ceil_div(p.hb, RADL_ROWS), nl);
+                k_radon_peel<1><<<grid, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, hw, Vs[cur ^ 1], Ms[cur ^ 1], s->wid);
             }
             ULAUNCH("k_radon_peel");
             UHIP(hipMemcpyAsync(s->sigma, hs[b].data(), (size_t)nl * sizeof(float), hipMemcpyHostToDevice, st));

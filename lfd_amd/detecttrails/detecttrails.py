@@ -260,6 +260,15 @@ class _ShortRecord:
         self.base, self.recs, self.n_lines, self.meas = base, recs, n_lines, meas
 
 
+class _WideRecord:
+    """a frame's record of ``_RadonStage`` with ``wide``: the record it has without (``base``; a ``_ShortRecord`` with
+    ``short``), its band records [K], their n_lines and [(stack record, row)] per found band (empty without ``prof_out``)"""
+    __slots__ = ("base", "recs", "n_lines", "meas")
+
+    def __init__(self, base, recs, n_lines, meas):
+        self.base, self.recs, self.n_lines, self.meas = base, recs, n_lines, meas
+
+
 class _RadonStage:
     """The faint-trail search behind detection for ``DetectTrails(radon=True)`` (include/lfdmi.h: faint-trail search): a
     ``Radon`` handle per (context, shape), kept while it is large enough, and the radon.txt rows.  ``sigma``: the frames' sky
@@ -273,12 +282,17 @@ class _RadonStage:
     plain records serve as the frame's one line when ``lines`` is None; a frame's record is then a ``_ShortRecord`` and every
     found short candidate gets a row in ``short_out`` (radon_short.txt).  With ``prof_out`` the short segments are measured
     too, and every row of radon_profiles.txt then ends with its source, ``lines`` or ``short`` (the defocus fit stays with the
-    lines' rows)."""
+    lines' rows).  ``wide``: the fields of lfdmi_radon_wide_params (steps 13 - 16): every frame is also searched by
+    ``Radon.search_wide``, whose plain records serve as the frame's one line when ``lines`` and ``short`` are None; a frame's
+    record is then a ``_WideRecord`` around the record it had, and every found band gets a row in ``wide_out``
+    (radon_wide.txt).  With ``prof_out`` the bands' centre-line segments are measured too, their rows end with ``wide`` and
+    the lines' rows with ``lines``."""
 
     def __init__(self, out, params, sigma, lines=None, lines_params=None, seg_out=None, prof_out=None, stack_params=None,
-                 defocus_out=None, defocus_params=None, short=None, short_out=None, lc=None):
+                 defocus_out=None, defocus_params=None, short=None, short_out=None, lc=None, wide=None, wide_out=None):
         from ..radon import as_params
         self.out, self.params, self.sigma, self._handles = out, as_params(params), float(sigma), {}
+        self.wide, self.wide_out = (dict(wide) if wide is not None else None), wide_out
         self.lc, self.last_lc = lc, {}                # an ``_LcStage``; {position: [(record, sections)]} of the last ``batch`` / ``one``
         self.short, self.short_out = (dict(short) if short is not None else None), short_out
         self.lines, self.seg_out = lines, seg_out
@@ -299,8 +313,24 @@ class _RadonStage:
         return recs
 
     def _search_all(self, handle, frames, **where):
+        if self.wide is None:
+            return self._search_short(handle, frames, None, **where)
+        wrecs, wnl, plain = handle.search_wide(frames, sigma=self.sigma, plain=True, **self.wide, **where)
+        base = self._search_short(handle, frames, plain, **where)
+        meas = [[] for _ in range(len(wnl))]
+        if self.prof_out is not None:
+            from ..stack import segments_from_radon_wide
+            segs, where_ = segments_from_radon_wide(wrecs, wnl)
+            if len(segs):
+                srec, rows = handle.ctx.stack_profiles(frames, segs, sigma=self.sigma, **where, **self.stack_params)
+                for (j, _), r, row in zip(where_, srec, rows):
+                    meas[j].append((r, row))
+        return [_WideRecord(base[j], wrecs[j], int(wnl[j]), meas[j]) for j in range(len(wnl))]
+
+    def _search_short(self, handle, frames, plain, **where):
+        """the records without ``wide``; plain: the wide call's plain records, which save the plain search its transform"""
         if self.short is None:
-            return self._search_lines(handle, frames, **where)
+            return plain if plain is not None and self.lines is None else self._search_lines(handle, frames, **where)
         srecs, snl, plain = handle.search_short(frames, sigma=self.sigma, plain=True, **self.short, **where)
         base = plain if self.lines is None else self._search_lines(handle, frames, **where)
         meas = [[] for _ in range(len(snl))]
@@ -366,6 +396,15 @@ class _RadonStage:
         """the rows of one frame's record: the line if it was found; with ``lines``, every found line in peel order"""
         from ..radon import format_row, format_segment_row
         tag = ""
+        if isinstance(rec, _WideRecord):
+            from ..radon import format_wide_row
+            from ..stack import format_row as format_profile_row
+            tag = " lines"
+            for k in range(rec.n_lines):
+                self.wide_out.write(format_wide_row(key, k, rec.recs[k]) + "\n")
+            for k, (srec, _) in enumerate(rec.meas):
+                self.prof_out.write(format_profile_row(key, k, srec) + " wide\n")
+            rec = rec.base
         if isinstance(rec, _ShortRecord):
             from ..radon import format_short_row
             from ..stack import format_row as format_profile_row
@@ -396,6 +435,8 @@ class _RadonStage:
             self.seg_out.flush()
         if self.short_out is not None:
             self.short_out.flush()
+        if self.wide_out is not None:
+            self.wide_out.flush()
         if self.prof_out is not None:
             self.prof_out.flush()
         if self.defocus_out is not None:
@@ -442,7 +483,7 @@ class _MaskStage:
         """[(x1, y1, x2, y2, half)] of a frame's found faint lines (a ``_RadonStage`` record with ``lines``), in peel order; the
         half-width from the stacked cross-section's fwhm where that was measured and is OK"""
         from ..masks import half_width
-        if isinstance(line, _ShortRecord):
+        while isinstance(line, (_ShortRecord, _WideRecord)):
             line = line.base
         if not isinstance(line, tuple):
             return []
@@ -920,6 +961,13 @@ class DetectTrails:
     ey1 ex2 ey2 seg_snr seg_n_pix``; radon.txt and radon_segments.txt stay what they are without it.  With
     ``radon_profiles=True`` (then ``radon_lines`` may be None) the short segments are measured too, and every row of
     radon_profiles.txt ends with its source, ``lines`` or ``short``.
+    ``radon_wide=True`` or a dict / ``lfd_amd.radon.RadonWideParams`` (needs ``radon=True``): the frames are also searched for
+    wide faint trails by scoring sliding bands of the last level's lines (steps 13 - 16 of the definition) and
+    ``radon_wide_file`` (default ``<savepath>/radon_wide.txt``) gets one row per found band: ``run camcol filter field line
+    width width_px snr n_pix ex1 ey1 ex2 ey2 seg_snr seg_n_pix``; rank files and resume treat it like radon_short.txt and
+    every other output stays what it is without it.  With ``radon_lines=None`` and no ``radon_short`` the wide call's plain
+    records are the frame's one line, which saves a transform.  With ``radon_profiles=True`` the bands' segments are measured
+    too and their rows end with ``wide``.
     ``trail_masks=True`` (default off): every results.txt row gets one row in ``masks_file`` (default ``<savepath>/masks.txt``),
     in the same order: ``run camcol filter field source line x1 y1 x2 y2 half n_pix`` with source ``detect`` -- the band of
     half-width ``half`` around the segment, flagged by ``lfdmi_mask_trails`` (include/lfdmi.h: trail masks; cap 0), and the
@@ -989,9 +1037,17 @@ class DetectTrails:
                 raise ValueError("radon_short needs radon=True: it is a mode of the faint-trail search")
             from ..radon import RadonParams, as_short_params
             self.radon_short = as_short_params(None if rs is True else rs, RadonParams(**self.radon_params).bin)
+        self.radon_wide_file = kwargs.get("radon_wide_file", os.path.join(save, "radon_wide.txt"))
+        self.radon_wide = None
+        rw = kwargs.get("radon_wide", False)
+        if rw is not False and rw is not None:
+            if not self.radon:
+                raise ValueError("radon_wide needs radon=True: it is a mode of the faint-trail search")
+            from ..radon import RadonParams, as_wide_params
+            self.radon_wide = as_wide_params(None if rw is True else rw, RadonParams(**self.radon_params).min_len)
         self.stack_params = {}
         if self.radon_profiles:
-            if not self.radon or (self.radon_lines is None and self.radon_short is None):
+            if not self.radon or (self.radon_lines is None and self.radon_short is None and self.radon_wide is None):
                 raise ValueError("radon_profiles=True needs radon=True and radon_lines=K: the segments it measures are theirs")
             from ..stack import as_params as stack_as_params
             self.stack_params = stack_as_params(kwargs.get("stack_params"))
@@ -1171,6 +1227,7 @@ class DetectTrails:
                 (open(self.radon_segments_file + suffix, "a") if self.radon and self.radon_lines is not None
                  else contextlib.nullcontext()) as segments_out, \
                 (open(self.radon_short_file + suffix, "a") if self.radon_short is not None else contextlib.nullcontext()) as short_out, \
+                (open(self.radon_wide_file + suffix, "a") if self.radon_wide is not None else contextlib.nullcontext()) as wide_out, \
                 (open(self.radon_profiles_file + suffix, "a") if self.radon_profiles else contextlib.nullcontext()) as rprof_out, \
                 (open(self.radon_defocus_file + suffix, "a") if self.radon_profiles and self.defocus
                  else contextlib.nullcontext()) as rdef_out, \
@@ -1196,7 +1253,7 @@ class DetectTrails:
                 sigma = _native.make_sky_params(**self.sky_params).target_sigma if self.normalize else 0.025
                 radon = prof_kw["radon"] = _RadonStage(radon_out, self.radon_params, sigma, self.radon_lines, self.radon_lines_params,
                                                        segments_out, rprof_out, self.stack_params, rdef_out, self.defocus_params,
-                                                       self.radon_short, short_out, lc)
+                                                       self.radon_short, short_out, lc, self.radon_wide, wide_out)
             masks = None
             if self.trail_masks:
                 masks = prof_kw["masks"] = _MaskStage(masks_out, self.mask_params, self.mask_dir)

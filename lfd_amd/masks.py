@@ -82,6 +82,22 @@ def segments_from_radon_lines(lines, n_lines, fwhm=None, bits=1, cap=0.0, fill=0
     return segments(rows, bits, cap, fill), where
 
 
+def segments_from_radon_wide(lines, n_lines, bits=1, cap=0.0, fill=0.0):
+    """The found bands of ``Radon.search_wide`` (records [n, K], n_lines [n]) -> (SEGMENT_DTYPE records, (frame, line) of each):
+    every found band's segment ex1 .. ey2 on its centre line, frames ascending, peel order within a frame, with
+    half = width_px / 2 + 2: the band itself and two pixels beyond either edge."""
+    lines = np.asarray(lines)
+    if lines.ndim == 1:
+        lines = lines[None]
+    rows, where = [], []
+    for i, nl in enumerate(np.asarray(n_lines).reshape(-1)):
+        for k in range(int(nl)):
+            r = lines[i, k]
+            rows.append((i, r["ex1"], r["ey1"], r["ex2"], r["ey2"], float(r["width_px"]) / 2.0 + 2.0))
+            where.append((i, k))
+    return segments(rows, bits, cap, fill), where
+
+
 def segments_from_results(rows, frames=None, fwhm=None, bits=1, cap=0.0, fill=0.0, **half_kw):
     """Results rows (dicts or records with x1 y1 x2 y2: ``results.read_results``, or detection records with found != 0) ->
     SEGMENT_DTYPE records, one per row.  The end points of a results row lie far off the image by construction (the Hough line

@@ -4,7 +4,8 @@ is the device handle; this module holds the parameters, the host conversion of a
 device), a one-call helper and the radon.txt format of ``DetectTrails(radon=True)``; for several lines per frame (steps 7 - 9 of
 the definition): ``RadonLinesParams``, the dyadic path, a segment's end points, ``search_lines`` and the radon_segments.txt format;
 for short trails, scored on every dyadic level (steps 10 - 12): ``RadonShortParams``, ``search_short`` and the radon_short.txt
-format.
+format; for wide trails, scored as sliding bands of neighbouring lines (steps 13 - 16): ``RadonWideParams``, ``search_wide``
+and the radon_wide.txt format.
 """
 import dataclasses
 import math
@@ -16,12 +17,15 @@ from . import _native
 RADON_DTYPE = _native.RADON_DTYPE
 RADON_LINE_DTYPE = _native.RADON_LINE_DTYPE
 RADON_SHORT_DTYPE = _native.RADON_SHORT_DTYPE
+RADON_WIDE_DTYPE = _native.RADON_WIDE_DTYPE
 OK, NO_LINE = _native.RADON_OK, _native.RADON_NO_LINE
 DEFAULT_SIGMA = 0.025
 RADON_COLUMNS = ("run", "camcol", "filter", "field", "x1", "y1", "x2", "y2", "snr", "n_pix")
 SEGMENT_COLUMNS = ("run", "camcol", "filter", "field", "line", "ex1", "ey1", "ex2", "ey2", "seg_snr", "seg_n_pix")
 SHORT_COLUMNS = ("run", "camcol", "filter", "field", "line", "level", "strip", "snr", "n_pix", "ex1", "ey1", "ex2", "ey2", "seg_snr",
                  "seg_n_pix")
+WIDE_COLUMNS = ("run", "camcol", "filter", "field", "line", "width", "width_px", "snr", "n_pix", "ex1", "ey1", "ex2", "ey2", "seg_snr",
+                "seg_n_pix")
 
 
 @dataclasses.dataclass
@@ -158,6 +162,55 @@ def as_short_params(params, bin=None):
     return dict(params)
 
 
+@dataclasses.dataclass
+class RadonWideParams:
+    """lfdmi_radon_wide_params with its defaults; ``validate`` applies the library's rules without a device (``min_len``: the
+    handle's, which bounds ``min_seg``)."""
+    max_width: int = 8
+    max_lines: int = 4
+    peel_halfwidth: int = 8
+    min_seg: int = 64
+    wide_threshold: float = 8.0
+
+    def as_dict(self):
+        return dataclasses.asdict(self)
+
+    def validate(self, min_len=None):
+        for name in ("max_width", "max_lines", "peel_halfwidth", "min_seg"):
+            if int(getattr(self, name)) != getattr(self, name):
+                raise ValueError(f"{name} must be an integer")
+        if not 1 <= self.max_width <= _native.RADON_MAX_WIDTH or self.max_width & (self.max_width - 1):
+            raise ValueError("max_width must be a power of two, 1 .. %d" % _native.RADON_MAX_WIDTH)
+        if not 1 <= self.max_lines <= _native.RADON_MAX_LINES:
+            raise ValueError("max_lines must be 1 .. %d" % _native.RADON_MAX_LINES)
+        if self.peel_halfwidth < 0:
+            raise ValueError("peel_halfwidth must be >= 0")
+        if self.min_seg < 1 or (min_len is not None and self.min_seg > min_len):
+            raise ValueError("min_seg must be 1 .. min_len")
+        if not (math.isfinite(self.wide_threshold) and self.wide_threshold > 0):
+            raise ValueError("wide_threshold must be finite and positive")
+        return self
+
+
+def default_wide_params():
+    """lfdmi_default_radon_wide_params as a RadonWideParams (read from the library: no GPU needed)."""
+    p = _native.make_radon_wide_params()
+    return RadonWideParams(**{k: getattr(p, k) for k, _ in _native.RadonWideParamsStruct._fields_ if k != "pad"})
+
+
+def as_wide_params(params, min_len=None):
+    """None / dict / RadonWideParams -> validated dict of lfdmi_radon_wide_params fields"""
+    if params is None:
+        return {}
+    if isinstance(params, RadonWideParams):
+        return params.validate(min_len).as_dict()
+    unknown = set(params) - {f.name for f in dataclasses.fields(RadonWideParams)}
+    if unknown:
+        raise TypeError(f"unknown radon wide parameter {sorted(unknown)[0]!r}")
+    RadonWideParams(**params).validate(min_len)
+    return dict(params)
+
+
 def working_dims(shape, bin):
     """(Hb, Wb, P of orientations 0 and 1, P of orientations 2 and 3)"""
     h, w = int(shape[0]), int(shape[1])
@@ -250,6 +303,20 @@ def search_short(ctx, frames, sigma=None, **params):
         return r.search_short(arr, sigma=sigma, **sp)
 
 
+def search_wide(ctx, frames, sigma=None, plain=False, **params):
+    """Search (n, h, w) or (h, w) frames on ``ctx`` for wide trails: (RADON_WIDE_DTYPE records [n, max_lines], n_lines [n]), and
+    with ``plain`` the RADON_DTYPE records of the plain search as a third item.  ``params``: fields of RadonParams and of
+    RadonWideParams.  The handle is created and destroyed per call."""
+    wnames = {f.name for f in dataclasses.fields(RadonWideParams)}
+    rp = as_params({k: v for k, v in params.items() if k not in wnames})
+    wp = as_wide_params({k: v for k, v in params.items() if k in wnames}, rp.get("min_len", RadonParams.min_len))
+    arr = frames if _native._is_dev(frames) or isinstance(frames, _native.DeviceFrames) else np.asarray(frames)
+    shp = tuple(arr.shape)
+    n, h, w = (1, *shp) if len(shp) == 2 else shp
+    with _native.Radon(ctx, (h, w), max_frames=max(1, min(n, ctx.max_inflight)), **rp) as r:
+        return r.search_wide(arr, sigma=sigma, plain=plain, **wp)
+
+
 def search_frames(ctx, frames, sigma=None, **params):
     """Search (n, h, w) or (h, w) frames on ``ctx``: RADON_DTYPE records, one per frame.  For repeated calls keep a
     ``_native.Radon`` handle instead: this one is created and destroyed per call."""
@@ -321,6 +388,29 @@ def read_short(path):
                 continue
             r = {}
             for k, v in zip(SHORT_COLUMNS, parts):
+                r[k] = v if k == "filter" else int(v) if k in ints else float(v)
+            rows.append(r)
+    return rows
+
+
+def format_wide_row(meta, line, rec):
+    """One radon_wide.txt row: meta = (run, camcol, filter, field), line = the record's place in peel order; floats with repr."""
+    return " ".join(str(v) for v in (*meta, int(line), int(rec["width"]), repr(float(rec["width_px"])), repr(float(rec["snr"])),
+                                      int(rec["n_pix"]), repr(float(rec["ex1"])), repr(float(rec["ey1"])), repr(float(rec["ex2"])),
+                                      repr(float(rec["ey2"])), repr(float(rec["seg_snr"])), int(rec["seg_n_pix"])))
+
+
+def read_wide(path):
+    """radon_wide.txt (rows only, no header line) -> list of dicts keyed by WIDE_COLUMNS."""
+    ints = ("run", "camcol", "field", "line", "width", "n_pix", "seg_n_pix")
+    rows = []
+    with open(path) as f:
+        for ln in f:
+            parts = ln.split()
+            if not parts:
+                continue
+            r = {}
+            for k, v in zip(WIDE_COLUMNS, parts):
                 r[k] = v if k == "filter" else int(v) if k in ints else float(v)
             rows.append(r)
     return rows

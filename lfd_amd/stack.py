@@ -107,6 +107,12 @@ def segments_from_radon_lines(lines, n_lines):
     return segments(rows), where
 
 
+def segments_from_radon_wide(lines, n_lines):
+    """The found bands of ``Radon.search_wide`` (records [n, K], n_lines [n]) -> (SEGMENT_DTYPE records, (frame, line) of each):
+    the records carry ``segments_from_radon_lines``' fields, and ex1 .. ey2 lie on the band's centre line."""
+    return segments_from_radon_lines(lines, n_lines)
+
+
 def segments_from_results(records):
     """Detection records (RESULT_DTYPE, one per frame) -> (SEGMENT_DTYPE records, frame of each): the x1 .. y2 of a results row for
     every frame with found != 0."""

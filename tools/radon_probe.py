@@ -3,7 +3,7 @@ between HIP events, beside the bytes each kernel has to move (the rows a level s
 16-bit counts) and the floor those bytes give at the copy rate the project quotes (4.8 TB/s, DESIGN.md: sky normalisation).
 Writes profiles/radon_probe.json.
 
-    python tools/radon_probe.py [--reps 5] [--frames 256] [--max-frames 16] [--out FILE] [--trace] [--lines K] [--short]
+    python tools/radon_probe.py [--reps 5] [--frames 256] [--max-frames 16] [--out FILE] [--trace] [--lines K] [--short] [--wide]
 
 --lines K  also times lfdmi_radon_search_lines(max_lines=K) on the same frames with one faint streak added to every second
            frame: ms per call and per round (a frame runs one round more than it has found lines, K at the most), beside the
@@ -13,7 +13,12 @@ Writes profiles/radon_probe.json.
            4 without it): ms per call and per frame-round, and the ratio of its frame-round to search_lines' frame-round,
            which is the yardstick: the scoring levels move the same bytes, so the ratio shows what the scores cost
 
---trace  one more run per bin under `rocprofv3 --kernel-trace --stats` -> profiles/radon_probe_kernel_stats_bin<b>.csv
+--wide     also times lfdmi_radon_search_wide(max_lines=K, max_width 8) in the same run on the same frames (K of --lines, 4
+           without it): ms per call and per frame-round, and the ratio of its frame-round to search_lines' frame-round: the wide
+           call stores the last level and reads it back, which search_lines never does, and scores four widths
+
+--trace  one more run per bin (32 frames, one timed call of each search asked for) under `rocprofv3 --kernel-trace --stats`
+         -> <--out without .json>_kernel_stats_bin<b>.csv beside --out (default: profiles/radon_probe_kernel_stats_bin<b>.csv)
 Every GPU step is a child process under its own `timeout`.
 """
 import argparse
@@ -101,6 +106,23 @@ def child(a):
                               "short_over_lines_per_frame_round": smed / srounds / lines["lines_ms_per_frame_round"],
                               "short_levels": sorted({int(v) for v in srecs["level"][srecs["status"] == 0]}),
                               "bytes_with_short": r.dims()[2]})
+            if a.wide:
+                wrecs, wnl = r.search_wide(frames, max_lines=a.lines)     # warm-up: the partial records
+                wms = []
+                for _ in range(a.reps):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    wrecs, wnl = r.search_wide(frames, max_lines=a.lines)
+                    e1.record()
+                    e1.synchronize()
+                    wms.append(e0.elapsed_time(e1))
+                wrounds = int(np.minimum(wnl + 1, a.lines).sum())
+                wmed = float(np.median(wms))
+                lines.update({"wide_ms_per_call": wmed, "wide_ms_all": wms, "wide_found": int(wnl.sum()),
+                              "wide_frame_rounds": wrounds, "wide_ms_per_frame_round": wmed / wrounds,
+                              "wide_over_lines_per_frame_round": wmed / wrounds / lines["lines_ms_per_frame_round"],
+                              "wide_widths": sorted({int(v) for v in wrecs["width"][wrecs["status"] == 0]}),
+                              "bytes_with_wide": r.dims()[2]})
             kb = kernel_bytes(SHAPE, b)
             total = float(sum(kb.values())) * a.frames
             med = float(np.median(ms))
@@ -129,34 +151,41 @@ def main():
     ap.add_argument("--bin", type=int, default=0)
     ap.add_argument("--lines", type=int, default=0)
     ap.add_argument("--short", action="store_true")
+    ap.add_argument("--wide", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "radon_probe.json"))
     ap.add_argument("--child", action="store_true")
     a = ap.parse_args()
-    if a.short and not a.lines:
+    if (a.short or a.wide) and not a.lines:
         a.lines = 4
     if a.child:
         child(a)
         return
-    common = ["--frames", str(a.frames), "--max-frames", str(a.max_frames), "--lines", str(a.lines)] + (["--short"] if a.short else [])
+    common = ["--frames", str(a.frames), "--max-frames", str(a.max_frames), "--lines", str(a.lines)] + (["--short"] if a.short else []) + \
+        (["--wide"] if a.wide else [])
     doc = {"tool": "tools/radon_probe.py", "copy_rate_TBps": COPY_RATE / 1e12,
            "runs": run_child(common + ["--reps", str(a.reps)], 500)}
     for r in doc["runs"]:
         print({k: r[k] for k in ("bin", "ms_per_call", "ms_floor_at_4.8_TBps", "x_the_floor", "lines_ms_per_call",
                                  "lines_ms_per_frame_round", "lines_found", "short_ms_per_call",
-                                 "short_ms_per_frame_round", "short_found", "short_over_lines_per_frame_round") if k in r}, flush=True)
+                                 "short_ms_per_frame_round", "short_found", "short_over_lines_per_frame_round", "wide_ms_per_call",
+                                 "wide_ms_per_frame_round", "wide_found", "wide_over_lines_per_frame_round") if k in r}, flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(doc, f, indent=1)
     if a.trace:
+        # the traced child runs the same searches as the timed one; the files are named after --out, so a --wide run written
+        # to radon_probe_wide.json leaves the plain search's radon_probe_kernel_stats_bin<b>.csv alone
+        stem = os.path.splitext(os.path.basename(a.out))[0]
+        modes = ["--lines", str(a.lines)] + (["--short"] if a.short else []) + (["--wide"] if a.wide else [])
         for b in (1, 2, 4):
             tmp = tempfile.mkdtemp(prefix="radon_probe_")
             try:
-                run_child(["--frames", "32", "--max-frames", str(a.max_frames), "--reps", "1", "--bin", str(b)], 300,
+                run_child(["--frames", "32", "--max-frames", str(a.max_frames), "--reps", "1", "--bin", str(b)] + modes, 300,
                           ["rocprofv3", "--kernel-trace", "--stats", "-d", tmp, "-o", "radon", "--output-format", "csv", "--"])
                 found = glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True)
                 if not found:
                     raise SystemExit("radon_probe: rocprofv3 wrote no kernel_stats.csv")
-                shutil.copy(found[0], os.path.join(os.path.dirname(os.path.abspath(a.out)), "radon_probe_kernel_stats_bin%d.csv" % b))
+                shutil.copy(found[0], os.path.join(os.path.dirname(os.path.abspath(a.out)), "%s_kernel_stats_bin%d.csv" % (stem, b)))
             finally:
                 shutil.rmtree(tmp, ignore_errors=True)
 
