@@ -1483,21 +1483,29 @@ class Radon(_Handle):
         ctx._chk(self._lib.lfdmi_radon_search(ctx._h, r, _ptr(frames), code, n, loc, _ptr(sg), _ptr(res)))
         return res
 
+    def _peel(self, what, make, params, dtype, plain, frames, sigma, pinned, native_device):
+        """the peeling search lfdmi_radon_<what>: ``make(**params)`` its params struct, ``dtype`` its records'; plain: None
+        where the call has no such argument"""
+        r, ctx = self._open(), self.ctx
+        p = make(**params)
+        frames, code, n, h, w, loc = self._frames(frames, pinned, "Radon." + what, native_device=native_device)
+        sg = _sigma(sigma, n)
+        k = max(1, min(int(p.max_lines), RADON_MAX_LINES))      # (out of range: the library refuses before it writes)
+        res = np.zeros((n, k), dtype)
+        nl = np.zeros(n, np.int32)
+        pl = np.zeros(n, RADON_DTYPE) if plain else None
+        ctx._chk(getattr(self._lib, "lfdmi_radon_" + what)(ctx._h, r, _ptr(frames), code, n, loc, _ptr(sg), C.byref(p), _ptr(res),
+                                                            _ptr(nl), *(() if plain is None else (_ptr(pl),))))
+        return (res, nl, pl) if plain else (res, nl)
+
     def search_lines(self, frames, sigma=None, max_lines=4, peel_halfwidth=8, min_seg=64, pinned=False, native_device=False):
         """Up to ``max_lines`` lines per frame by peeling, each with its extent (include/lfdmi.h: faint-trail search, steps
         7 - 9); frames and sigma as in ``search``.  Returns (RADON_LINE_DTYPE records [n, max_lines], n_lines [n]): a frame's
         found lines are its records 0 .. n_lines-1 in peel order, record n_lines (if there is room) is the round that stopped
         it.  The first call allocates the second V, M set; ``dims()`` counts it from then on."""
-        r, ctx = self._open(), self.ctx
-        lp = make_radon_lines_params(max_lines=max_lines, peel_halfwidth=peel_halfwidth, min_seg=min_seg)
-        frames, code, n, h, w, loc = self._frames(frames, pinned, "Radon.search_lines", native_device=native_device)
-        sg = _sigma(sigma, n)
-        k = max(1, min(int(lp.max_lines), RADON_MAX_LINES))      # (out of range: the library refuses before it writes)
-        res = np.zeros((n, k), RADON_LINE_DTYPE)
-        nl = np.zeros(n, np.int32)
-        ctx._chk(self._lib.lfdmi_radon_search_lines(ctx._h, r, _ptr(frames), code, n, loc, _ptr(sg), C.byref(lp), _ptr(res),
-                                                    _ptr(nl)))
-        return res, nl
+        return self._peel("search_lines", make_radon_lines_params, {"max_lines": max_lines, "peel_halfwidth": peel_halfwidth,
+                                                                    "min_seg": min_seg},
+                          RADON_LINE_DTYPE, None, frames, sigma, pinned, native_device)
 
     def search_short(self, frames, sigma=None, plain=False, pinned=False, native_device=False, **params):
         """Short trails: every stored level of the transform scored strip by strip, the best candidate's parent line, its
@@ -1505,17 +1513,8 @@ class Radon(_Handle):
         sigma as in ``search``, ``params`` the fields of lfdmi_radon_short_params.  Returns (RADON_SHORT_DTYPE records
         [n, max_lines], n_lines [n]) and, with ``plain``, a third item: the RADON_DTYPE records ``search`` returns for these
         frames.  The first call allocates the rounds' buffers and the partial records; ``dims()`` counts them from then on."""
-        r, ctx = self._open(), self.ctx
-        sp = make_radon_short_params(**params)
-        frames, code, n, h, w, loc = self._frames(frames, pinned, "Radon.search_short", native_device=native_device)
-        sg = _sigma(sigma, n)
-        k = max(1, min(int(sp.max_lines), RADON_MAX_LINES))      # (out of range: the library refuses before it writes)
-        res = np.zeros((n, k), RADON_SHORT_DTYPE)
-        nl = np.zeros(n, np.int32)
-        pl = np.zeros(n, RADON_DTYPE) if plain else None
-        ctx._chk(self._lib.lfdmi_radon_search_short(ctx._h, r, _ptr(frames), code, n, loc, _ptr(sg), C.byref(sp), _ptr(res),
-                                                    _ptr(nl), _ptr(pl)))
-        return (res, nl, pl) if plain else (res, nl)
+        return self._peel("search_short", make_radon_short_params, params, RADON_SHORT_DTYPE, bool(plain), frames, sigma, pinned,
+                          native_device)
 
     def search_wide(self, frames, sigma=None, plain=False, pinned=False, native_device=False, **params):
         """Wide trails: bands of 1, 2, 4, .. ``max_width`` neighbouring lines of the last level scored as one, the best band's
@@ -1524,14 +1523,5 @@ class Radon(_Handle):
         (RADON_WIDE_DTYPE records [n, max_lines], n_lines [n]) and, with ``plain``, a third item: the RADON_DTYPE records
         ``search`` returns for these frames.  The first call allocates the rounds' buffers and the partial records;
         ``dims()`` counts them from then on."""
-        r, ctx = self._open(), self.ctx
-        wp = make_radon_wide_params(**params)
-        frames, code, n, h, w, loc = self._frames(frames, pinned, "Radon.search_wide", native_device=native_device)
-        sg = _sigma(sigma, n)
-        k = max(1, min(int(wp.max_lines), RADON_MAX_LINES))      # (out of range: the library refuses before it writes)
-        res = np.zeros((n, k), RADON_WIDE_DTYPE)
-        nl = np.zeros(n, np.int32)
-        pl = np.zeros(n, RADON_DTYPE) if plain else None
-        ctx._chk(self._lib.lfdmi_radon_search_wide(ctx._h, r, _ptr(frames), code, n, loc, _ptr(sg), C.byref(wp), _ptr(res),
-                                                   _ptr(nl), _ptr(pl)))
-        return (res, nl, pl) if plain else (res, nl)
+        return self._peel("search_wide", make_radon_wide_params, params, RADON_WIDE_DTYPE, bool(plain), frames, sigma, pinned,
+                          native_device)

@@ -137,21 +137,24 @@ extern "C" int lfdmi_radon_dims(const lfdmi_radon *s, int32_t *p01, int32_t *p23
     return 0;
 }
 
-// the working point (c, r) of orientation q in pixels (step 6's mapping)
-static void radon_point(const RadonDev &p, int q, int c, int r, double &x, double &y) {
-    int i, j;
+// the working point (c, r) of orientation q in pixels (step 6's mapping); r: a row, or the middle between two rows (a band's
+// centre line, steps 15 and 16).  Every whole r is exact in a double, so a line's points do not depend on the route here
+static void radon_point(const RadonDev &p, int q, int c, double r, double &x, double &y) {
+    double i, j;
     if (q == 0) { i = c; j = r; }
-    else if (q == 1) { i = c; j = p.hb - 1 - r; }
+    else if (q == 1) { i = c; j = (double)(p.hb - 1) - r; }
     else if (q == 2) { i = r; j = c; }
-    else { i = p.wb - 1 - r; j = c; }
+    else { i = (double)(p.wb - 1) - r; j = c; }
     x = (double)p.b * i + (double)(p.b - 1) / 2.0;
     y = (double)p.b * j + (double)(p.b - 1) / 2.0;
 }
+// the row offset of the centre line of a band `width` lines wide above its lowest line (0: a mode without widths)
+static double radon_mid(int width) { return width > 1 ? (double)(width - 1) / 2.0 : 0.0; }
 
-// definition step 6 (o: an lfdmi_radon_result, or the lfdmi_radon_line that begins with its fields)
-template <class T> static void radon_line(const RadonDev &p, int q, int y0, int sl, T &o) {
-    radon_point(p, q, 0, y0, o.x1, o.y1);
-    radon_point(p, q, p.P[q >> 1] - 1, y0 + sl, o.x2, o.y2);
+// definition step 6, `mid` rows above the line (o: an lfdmi_radon_result, or a record that begins with its fields)
+template <class T> static void radon_line(const RadonDev &p, int q, int y0, int sl, double mid, T &o) {
+    radon_point(p, q, 0, (double)y0 + mid, o.x1, o.y1);
+    radon_point(p, q, p.P[q >> 1] - 1, (double)(y0 + sl) + mid, o.x2, o.y2);
     double theta = atan2(-(o.x2 - o.x1), o.y2 - o.y1);
     const double pi = 3.141592653589793;
     if (theta < 0.0) theta += pi;
@@ -160,14 +163,19 @@ template <class T> static void radon_line(const RadonDev &p, int q, int y0, int 
     o.rho = o.x1 * cos(theta) + o.y1 * sin(theta);
 }
 
-// the record of a frame's best line as the caller gets it (o zeroed before)
-template <class T> static void radon_fill(const lfdmi_radon *s, const RadonDev &p, const RadonRec &r, T &o) {
+// what every device record and every caller's record begin with (o zeroed before); false: no line, o stays as it is
+template <class R, class T> static bool radon_fill_head(const R &r, float threshold, T &o) {
     o.status = r.status;
-    if (o.status != LFDMI_RADON_OK) return;
+    if (o.status != LFDMI_RADON_OK) return false;
     o.q = r.q; o.y0 = r.y0; o.s = r.s; o.n_pix = r.n_pix;
     o.sum = r.sum; o.snr = r.snr;
-    o.found = o.snr >= s->par.threshold;
-    radon_line(p, o.q, o.y0, o.s, o);
+    o.found = o.snr >= threshold;
+    return true;
+}
+
+// the record of a frame's best line as the caller gets it (o zeroed before)
+template <class T> static void radon_fill(const lfdmi_radon *s, const RadonDev &p, const RadonRec &r, T &o) {
+    if (radon_fill_head(r, s->par.threshold, o)) radon_line(p, o.q, o.y0, o.s, 0.0, o);
 }
 
 // where the scoring levels of strip widths min_strip .. P/2 put their partial records (k_radon_short.h): the grids are
@@ -259,7 +267,18 @@ static int radon_transform(lfdmi_ctx *ctx, lfdmi_radon *s, const RadonDev &p, co
     return 0;
 }
 
-// what the two searches do alike: the checks of the handle and of the arguments, the frames' sigma on the host, the staging
+// every buffer a handle allocates after its creation goes through here: `count` values for *slot unless it has them.  Into a
+// local first: a failed hipMalloc leaves *slot null and uncounted, so the next call tries again and destroy frees nothing twice
+template <class T> static int radon_lazy(lfdmi_ctx *ctx, lfdmi_radon *s, T **slot, size_t count) {
+    if (*slot) return 0;
+    void *m = nullptr;
+    UHIP(hipMalloc(&m, count * sizeof(T)));
+    *slot = (T *)m;
+    s->bytes += (int64_t)(count * sizeof(T));
+    return 0;
+}
+
+// what the searches do alike: the checks of the handle and of the arguments, the frames' sigma on the host, the staging
 // buffer of host frames, and the front of every chunk
 struct LFD_HIDDEN RadonCall {
     lfdmi_ctx *ctx;
@@ -270,7 +289,7 @@ struct LFD_HIDDEN RadonCall {
     std::vector<float> hsig;
     size_t PX = 0, FB = 0;
     bool in_dev = false;
-    int CH = 0;
+    int n = 0, CH = 0;
     hipStream_t st = nullptr;
 
     int begin() {
@@ -281,11 +300,11 @@ struct LFD_HIDDEN RadonCall {
         return 0;
     }
     // (outs: every output array of the call is there)
-    int args(const void *fr, bool outs, int dtype, int n, int loc, const float *sigma) {
+    int args(const void *fr, bool outs, int dtype, int nfr, int loc, const float *sigma) {
         int rc;
-        if (n < 0 || (n > 0 && (!fr || !outs))) return ctx_fail(ctx, LFDMI_ERR_ARG, "NULL argument");
-        if ((rc = unit_dtype(ctx, fn, dtype)) || (rc = unit_loc(ctx, loc)) || (rc = unit_sigma(ctx, fn, sigma, n, &hsig))) return rc;
-        frames = fr;
+        if (nfr < 0 || (nfr > 0 && (!fr || !outs))) return ctx_fail(ctx, LFDMI_ERR_ARG, "NULL argument");
+        if ((rc = unit_dtype(ctx, fn, dtype)) || (rc = unit_loc(ctx, loc)) || (rc = unit_sigma(ctx, fn, sigma, nfr, &hsig))) return rc;
+        frames = fr; n = nfr;
         p = s->p;
         p.be = dtype == LFDMI_F32_BE;
         PX = (size_t)p.h * p.w; FB = PX * sizeof(float);
@@ -295,10 +314,8 @@ struct LFD_HIDDEN RadonCall {
     }
     // the staging buffer, allocated by the first call with host frames
     int stage() {
-        if (!in_dev && !s->stage) {
-            UHIP(hipMalloc(&s->stage, (size_t)CH * FB));
-            s->bytes += (int64_t)((size_t)CH * FB);
-        }
+        int rc;
+        if (!in_dev && (rc = radon_lazy(ctx, s, &s->stage, (size_t)CH * PX))) return rc;
         st = ctx_stream(ctx);
         return 0;
     }
@@ -353,332 +370,93 @@ static int radon_path(int c, int sl, int P) {
     return d;
 }
 
-// what the rounds of both peeling searches need, allocated by the first call of either
-static int radon_rounds_alloc(lfdmi_ctx *ctx, lfdmi_radon *s, int pstride) {
-    if (s->V2) return 0;
-    const size_t F = (size_t)s->max_frames, px = (size_t)s->p.hb * s->p.wb;
-    UHIP(hipMalloc(&s->V2, F * px * sizeof(float)));
-    UHIP(hipMalloc(&s->M2, F * px * sizeof(uint16_t)));
-    UHIP(hipMalloc(&s->pre, F * pstride * sizeof(float)));
-    UHIP(hipMalloc(&s->cnt, F * pstride * sizeof(int)));
-    UHIP(hipMalloc(&s->lnd, F * sizeof(RadonLineDev)));
-    UHIP(hipMalloc(&s->ext, F * sizeof(RadonExtDev)));
-    s->bytes += (int64_t)(F * px * 6 + F * pstride * 8 + F * (sizeof(RadonLineDev) + sizeof(RadonExtDev)));
+// what the rounds of every peeling search need, allocated by the first call of any (pstride: a line's prefix values)
+static int radon_pstride(const RadonDev &p) { return std::max(p.hb, p.wb) + 1; }
+static int radon_rounds_alloc(lfdmi_ctx *ctx, lfdmi_radon *s) {
+    const size_t F = (size_t)s->max_frames, px = (size_t)s->p.hb * s->p.wb, ps = (size_t)radon_pstride(s->p);
+    int rc;
+    if ((rc = radon_lazy(ctx, s, &s->V2, F * px)) || (rc = radon_lazy(ctx, s, &s->M2, F * px)) || (rc = radon_lazy(ctx, s, &s->pre, F * ps)) ||
+        (rc = radon_lazy(ctx, s, &s->cnt, F * ps)) || (rc = radon_lazy(ctx, s, &s->lnd, F)) || (rc = radon_lazy(ctx, s, &s->ext, F)))
+        return rc;
     return 0;
 }
 
-extern "C" int lfdmi_radon_search_lines(lfdmi_ctx *ctx, lfdmi_radon *s, const void *frames, int dtype, int n, int loc, const float *sigma,
-                                        const lfdmi_radon_lines_params *lp, lfdmi_radon_line *lines, int32_t *n_lines) {
-    RadonCall c{ctx, s, "lfdmi_radon_search_lines"};
-    int rc = c.begin();
-    if (rc) return rc;
-    lfdmi_radon_lines_params lq;
-    if (lp) lq = *lp; else lfdmi_default_radon_lines_params(&lq);
-    if (lq.max_lines < 1 || lq.max_lines > LFDMI_RADON_MAX_LINES || lq.peel_halfwidth < 0 || lq.min_seg < 1 || lq.min_seg > s->par.min_len)
-        return ctx_fail(ctx, LFDMI_ERR_ARG, "radon lines params out of range (include/lfdmi.h: lfdmi_radon_lines_params)");
-    if ((rc = c.args(frames, lines && n_lines, dtype, n, loc, sigma))) return rc;
-    if (n == 0) return 0;
+// ---- the peeling searches ------------------------------------------------------------------------------------------------------------
+// A Mode is what one of them adds to radon_rounds: Out, the caller's record; Rec, the device's, and where a round leaves them
+// (rec()); q, its parameters (max_lines, peel_halfwidth and min_seg among them); transform(), radon_transform with the mode's
+// arguments for round k; fill(), Rec -> Out (o zeroed before); width(), the found band's lines, 0 where lines have no width.
+struct LFD_HIDDEN RadonLinesMode {
+    typedef lfdmi_radon_line Out;
+    typedef RadonRec Rec;
+    lfdmi_radon *s;
+    lfdmi_radon_lines_params q;
+    const Rec *rec() const { return s->rec; }
+    int transform(const RadonCall &c, const float *V, const uint16_t *M, int nf, int) const { return radon_transform(c.ctx, s, c.p, V, M, nf, c.st); }
+    void fill(const RadonDev &p, const Rec &r, Out &o) const { radon_fill(s, p, r, o); }
+    static int width(const Out &) { return 0; }
+};
+
+struct LFD_HIDDEN RadonShortMode {
+    typedef lfdmi_radon_short Out;
+    typedef RadonShortRec Rec;
+    lfdmi_radon *s;
+    lfdmi_radon_short_params q;
+    RadonShortDev sd;
+    const Rec *rec() const { return s->srec; }
+    // round 0 runs the last level too: the plain search's record comes with it
+    int transform(const RadonCall &c, const float *V, const uint16_t *M, int nf, int k) const {
+        return radon_transform(c.ctx, s, c.p, V, M, nf, c.st, &sd, k == 0);
+    }
+    // the parent line's geometry by step 6
+    void fill(const RadonDev &p, const Rec &r, Out &o) const {
+        if (!radon_fill_head(r, q.short_threshold, o)) return;
+        o.level = r.level; o.strip = r.strip; o.ys = r.ys; o.ss = r.ss;
+        radon_line(p, o.q, o.y0, o.s, 0.0, o);
+    }
+    static int width(const Out &) { return 0; }
+};
+
+struct LFD_HIDDEN RadonWideMode {
+    typedef lfdmi_radon_wide Out;
+    typedef RadonWideRec Rec;
+    lfdmi_radon *s;
+    lfdmi_radon_wide_params q;
+    const Rec *rec() const { return s->wrec; }
+    // every round's width-1 pass is step 5: round 0's is the plain search's record
+    int transform(const RadonCall &c, const float *V, const uint16_t *M, int nf, int) const {
+        return radon_transform(c.ctx, s, c.p, V, M, nf, c.st, nullptr, true, q.max_width);
+    }
+    // steps 14 and 15
+    void fill(const RadonDev &p, const Rec &r, Out &o) const {
+        if (!radon_fill_head(r, q.wide_threshold, o)) return;
+        o.width = r.k;
+        radon_line(p, o.q, o.y0, o.s, radon_mid(o.width), o);
+        const long long run = p.P[o.q >> 1] - 1, rise = o.s;
+        o.width_px = (double)(o.width * p.b) * ((double)run / sqrt((double)(run * run + rise * rise)));
+    }
+    static int width(const Out &o) { return o.width; }
+};
+
+// The chunks and the rounds of a peeling search, after the entry point's checks, c.stage() and the lazy allocations: lines
+// [n * max_lines] and n_lines [n], and with `plain` the plain search's records, which round 0 leaves in s->rec.  A round queues
+// the transform and the records' copy, waits for the stream (the call's one wait per round of a chunk, but for the last one of a
+// pending segment copy), and then queues the found lines' extents, the copy of their segments, which the next round's wait
+// covers, the peel into the other V, M set and the found frames' sigma.
+template <class Mode>
+static int radon_rounds(RadonCall &c, const Mode &m, typename Mode::Out *lines, int32_t *n_lines, lfdmi_radon_result *plain) {
+    typedef typename Mode::Out Out;
+    lfdmi_ctx *ctx = c.ctx;
+    lfdmi_radon *s = c.s;
     const RadonDev &p = c.p;
-    const std::vector<float> &hsig = c.hsig;
-    const int CH = c.CH, K = lq.max_lines;
-    const int hw = (int)(((int64_t)lq.peel_halfwidth + p.b - 1) / p.b);
-    const int pstride = std::max(p.hb, p.wb) + 1;
-    if ((rc = c.stage()) || (rc = radon_rounds_alloc(ctx, s, pstride))) return rc;
     hipStream_t st = c.st;
+    const int n = c.n, CH = c.CH, K = m.q.max_lines, pstride = radon_pstride(p);
+    const int hw = (int)(((int64_t)m.q.peel_halfwidth + p.b - 1) / p.b);
+    int rc;
     memset(lines, 0, (size_t)n * K * sizeof(*lines));
     memset(n_lines, 0, (size_t)n * sizeof(*n_lines));
     float *Vs[2] = {s->V, s->V2};
     uint16_t *Ms[2] = {s->M, s->M2};
-    std::vector<RadonRec> hrec(CH);
-    // (round k's host buffers are read or written by copies that finish with round k + 1's wait: two of each alternate)
-    std::vector<RadonLineDev> hl[2];
-    std::vector<RadonExtDev> hx[2];
-    std::vector<float> hs[2];
-    std::vector<int> alive, found_frames[2];
-    for (int c0 = 0; c0 < n; c0 += CH) {
-        const int nf = std::min(CH, n - c0);
-        if ((rc = c.chunk(c0, nf))) return rc;
-        alive.resize(nf);
-        for (int a = 0; a < nf; a++) alive[a] = c0 + a;     // slot -> frame
-        int cur = 0, pending = -1;                          // pending: the round whose segments are on their way to hx[round & 1]
-        // the segments of round k's found lines, once their copy has been waited for
-        auto segments = [&](int k) {
-            const int b = k & 1;
-            for (size_t e = 0; e < found_frames[b].size(); e++) {
-                lfdmi_radon_line &o = lines[(size_t)found_frames[b][e] * K + k];
-                const RadonExtDev &x = hx[b][e];
-                const int P = p.P[o.q >> 1];
-                o.c1 = x.c1; o.c2 = x.c2; o.seg_n_pix = x.n; o.seg_sum = x.sum; o.seg_snr = x.snr;
-                radon_point(p, o.q, o.c1, o.y0 + radon_path(o.c1, o.s, P), o.ex1, o.ey1);
-                radon_point(p, o.q, o.c2, o.y0 + radon_path(o.c2, o.s, P), o.ex2, o.ey2);
-            }
-        };
-        for (int k = 0; k < K && !alive.empty(); k++) {
-            const int na = (int)alive.size(), b = k & 1;
-            rc = radon_transform(ctx, s, p, Vs[cur], Ms[cur], na, st);
-            if (rc) return rc;
-            UHIP(hipMemcpyAsync(hrec.data(), s->rec, (size_t)na * sizeof(RadonRec), hipMemcpyDeviceToHost, st));
-            UHIP(hipStreamSynchronize(st));
-            if (pending >= 0) { segments(pending); pending = -1; }
-            hl[b].clear(); found_frames[b].clear(); hs[b].clear();
-            for (int a = 0; a < na; a++) {
-                lfdmi_radon_line &o = lines[(size_t)alive[a] * K + k];
-                radon_fill(s, p, hrec[a], o);
-                if (!o.found) continue;
-                n_lines[alive[a]] = k + 1;
-                hl[b].push_back(RadonLineDev{a, o.q, o.y0, o.s});
-                found_frames[b].push_back(alive[a]);
-                hs[b].push_back(hsig[alive[a]]);
-            }
-            const int nl = (int)hl[b].size();
-            if (!nl) break;
-            hx[b].resize(nl);
-            UHIP(hipMemcpyAsync(s->lnd, hl[b].data(), (size_t)nl * sizeof(RadonLineDev), hipMemcpyHostToDevice, st));
-            k_radon_extent<<<nl, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, s->sigma, lq.min_seg, s->pre, s->cnt, pstride, s->ext, nullptr);
-            ULAUNCH("k_radon_extent");
-            UHIP(hipMemcpyAsync(hx[b].data(), s->ext, (size_t)nl * sizeof(RadonExtDev), hipMemcpyDeviceToHost, st));
-            pending = k;
-            if (k + 1 == K) break;
-            // the found frames go on: slot e of the other set is the frame of line e
-            if (p.wb % 8 == 0) {
-                const dim3 grid(ceil_div(p.wb, RAD_THREADS * 8), ceil_div(p.hb, RADL_ROWS), nl);
-                k_radon_peel<8><<<grid, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, hw, Vs[cur ^ 1], Ms[cur ^ 1], nullptr);
-            } else {
-                const dim3 grid(ceil_div(p.wb, RAD_THREADS), ceil_div(p.hb, RADL_ROWS), nl);
-                k_radon_peel<1><<<grid, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, hw, Vs[cur ^ 1], Ms[cur ^ 1], nullptr);
-            }
-            ULAUNCH("k_radon_peel");
-            UHIP(hipMemcpyAsync(s->sigma, hs[b].data(), (size_t)nl * sizeof(float), hipMemcpyHostToDevice, st));
-            alive = found_frames[b];
-            cur ^= 1;
-        }
-        if (pending >= 0) {
-            UHIP(hipStreamSynchronize(st));
-            segments(pending);
-        }
-    }
-    return 0;
-}
-
-extern "C" void lfdmi_default_radon_short_params(lfdmi_radon_short_params *o) {
-    if (!o) return;
-    memset(o, 0, sizeof(*o));
-    o->min_strip = 64; o->max_lines = 4; o->peel_halfwidth = 8; o->min_seg = 32; o->short_threshold = 8.5f;
-}
-
-// the record of a frame's short candidate as the caller gets it (o zeroed before): the parent line's geometry by step 6
-static void radon_short_fill(const RadonDev &p, const RadonShortRec &r, float threshold, lfdmi_radon_short &o) {
-    o.status = r.status;
-    if (o.status != LFDMI_RADON_OK) return;
-    o.q = r.q; o.y0 = r.y0; o.s = r.s; o.n_pix = r.n_pix;
-    o.sum = r.sum; o.snr = r.snr;
-    o.level = r.level; o.strip = r.strip; o.ys = r.ys; o.ss = r.ss;
-    o.found = o.snr >= threshold;
-    radon_line(p, o.q, o.y0, o.s, o);
-}
-
-extern "C" int lfdmi_radon_search_short(lfdmi_ctx *ctx, lfdmi_radon *s, const void *frames, int dtype, int n, int loc, const float *sigma,
-                                        const lfdmi_radon_short_params *sp, lfdmi_radon_short *lines, int32_t *n_lines,
-                                        lfdmi_radon_result *plain) {
-    RadonCall c{ctx, s, "lfdmi_radon_search_short"};
-    int rc = c.begin();
-    if (rc) return rc;
-    lfdmi_radon_short_params sq;
-    if (sp) sq = *sp; else lfdmi_default_radon_short_params(&sq);
-    const int bb = s->p.b * s->p.b;
-    if (sq.min_strip < 64 || (sq.min_strip & (sq.min_strip - 1)) || sq.max_lines < 1 || sq.max_lines > LFDMI_RADON_MAX_LINES ||
-        sq.peel_halfwidth < 0 || sq.min_seg < 1 || (int64_t)sq.min_seg > (int64_t)sq.min_strip * bb / 2 ||
-        !std::isfinite(sq.short_threshold) || !(sq.short_threshold > 0))
-        return ctx_fail(ctx, LFDMI_ERR_ARG, "radon short params out of range (include/lfdmi.h: lfdmi_radon_short_params)");
-    if ((rc = c.args(frames, lines && n_lines, dtype, n, loc, sigma))) return rc;
-    if (n == 0) return 0;
-    const RadonDev &p = c.p;
-    const std::vector<float> &hsig = c.hsig;
-    const int CH = c.CH, K = sq.max_lines;
-    const int hw = (int)(((int64_t)sq.peel_halfwidth + p.b - 1) / p.b);
-    const int pstride = std::max(p.hb, p.wb) + 1;
-    if ((rc = c.stage()) || (rc = radon_rounds_alloc(ctx, s, pstride))) return rc;
-    {   // (each buffer on its own: a call that failed between the two allocates only what is missing)
-        const size_t F = (size_t)CH, total = (size_t)std::max(1LL, radon_short_layout(p, 64).total);
-        if (!s->spart) {
-            UHIP(hipMalloc(&s->spart, F * total * sizeof(RadonShortPart)));
-            s->bytes += (int64_t)(F * total * sizeof(RadonShortPart));
-        }
-        if (!s->srec) {
-            UHIP(hipMalloc(&s->srec, F * sizeof(RadonShortRec)));
-            s->bytes += (int64_t)(F * sizeof(RadonShortRec));
-        }
-    }
-    const RadonShortDev sd = radon_short_layout(p, sq.min_strip);
-    hipStream_t st = c.st;
-    memset(lines, 0, (size_t)n * K * sizeof(*lines));
-    memset(n_lines, 0, (size_t)n * sizeof(*n_lines));
-    float *Vs[2] = {s->V, s->V2};
-    uint16_t *Ms[2] = {s->M, s->M2};
-    std::vector<RadonShortRec> hrec(CH);
-    std::vector<RadonRec> hplain(plain ? n : 0);
-    // (round k's host buffers are read or written by copies that finish with round k + 1's wait: two of each alternate)
-    std::vector<RadonLineDev> hl[2];
-    std::vector<RadonExtDev> hx[2];
-    std::vector<float> hs[2];
-    std::vector<int> alive, found_frames[2];
-    for (int c0 = 0; c0 < n; c0 += CH) {
-        const int nf = std::min(CH, n - c0);
-        if ((rc = c.chunk(c0, nf))) return rc;
-        alive.resize(nf);
-        for (int a = 0; a < nf; a++) alive[a] = c0 + a;     // slot -> frame
-        int cur = 0, pending = -1;
-        auto segments = [&](int k) {
-            const int b = k & 1;
-            for (size_t e = 0; e < found_frames[b].size(); e++) {
-                lfdmi_radon_short &o = lines[(size_t)found_frames[b][e] * K + k];
-                const RadonExtDev &x = hx[b][e];
-                const int P = p.P[o.q >> 1];
-                o.c1 = x.c1; o.c2 = x.c2; o.seg_n_pix = x.n; o.seg_sum = x.sum; o.seg_snr = x.snr;
-                radon_point(p, o.q, o.c1, o.y0 + radon_path(o.c1, o.s, P), o.ex1, o.ey1);
-                radon_point(p, o.q, o.c2, o.y0 + radon_path(o.c2, o.s, P), o.ex2, o.ey2);
-            }
-        };
-        for (int k = 0; k < K && !alive.empty(); k++) {
-            const int na = (int)alive.size(), b = k & 1;
-            // round 0 runs the last level too: the plain search's record comes with it
-            rc = radon_transform(ctx, s, p, Vs[cur], Ms[cur], na, st, &sd, k == 0);
-            if (rc) return rc;
-            UHIP(hipMemcpyAsync(hrec.data(), s->srec, (size_t)na * sizeof(RadonShortRec), hipMemcpyDeviceToHost, st));
-            if (k == 0 && plain) UHIP(hipMemcpyAsync(hplain.data() + c0, s->rec, (size_t)na * sizeof(RadonRec), hipMemcpyDeviceToHost, st));
-            UHIP(hipStreamSynchronize(st));
-            if (pending >= 0) { segments(pending); pending = -1; }
-            hl[b].clear(); found_frames[b].clear(); hs[b].clear();
-            for (int a = 0; a < na; a++) {
-                lfdmi_radon_short &o = lines[(size_t)alive[a] * K + k];
-                radon_short_fill(p, hrec[a], sq.short_threshold, o);
-                if (!o.found) continue;
-                n_lines[alive[a]] = k + 1;
-                hl[b].push_back(RadonLineDev{a, o.q, o.y0, o.s});
-                found_frames[b].push_back(alive[a]);
-                hs[b].push_back(hsig[alive[a]]);
-            }
-            const int nl = (int)hl[b].size();
-            if (!nl) break;
-            hx[b].resize(nl);
-            UHIP(hipMemcpyAsync(s->lnd, hl[b].data(), (size_t)nl * sizeof(RadonLineDev), hipMemcpyHostToDevice, st));
-            k_radon_extent<<<nl, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, s->sigma, sq.min_seg, s->pre, s->cnt, pstride, s->ext, nullptr);
-            ULAUNCH("k_radon_extent");
-            UHIP(hipMemcpyAsync(hx[b].data(), s->ext, (size_t)nl * sizeof(RadonExtDev), hipMemcpyDeviceToHost, st));
-            pending = k;
-            if (k + 1 == K) break;
-            if (p.wb % 8 == 0) {
-                const dim3 grid(ceil_div(p.wb, RAD_THREADS * 8), ceil_div(p.hb, RADL_ROWS), nl);
-                k_radon_peel<8><<<grid, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, hw, Vs[cur ^ 1], Ms[cur ^ 1], nullptr);
-            } else {
-                const dim3 grid(ceil_div(p.wb, RAD_THREADS), ceil_div(p.hb, RADL_ROWS), nl);
-                k_radon_peel<1><<<grid, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, hw, Vs[cur ^ 1], Ms[cur ^ 1], nullptr);
-            }
-            ULAUNCH("k_radon_peel");
-            UHIP(hipMemcpyAsync(s->sigma, hs[b].data(), (size_t)nl * sizeof(float), hipMemcpyHostToDevice, st));
-            alive = found_frames[b];
-            cur ^= 1;
-        }
-        if (pending >= 0) {
-            UHIP(hipStreamSynchronize(st));
-            segments(pending);
-        }
-    }
-    if (plain)
-        for (int i = 0; i < n; i++) {
-            memset(&plain[i], 0, sizeof(plain[i]));
-            radon_fill(s, p, hplain[i], plain[i]);
-        }
-    return 0;
-}
-
-extern "C" void lfdmi_default_radon_wide_params(lfdmi_radon_wide_params *o) {
-    if (!o) return;
-    memset(o, 0, sizeof(*o));
-    o->max_width = 8; o->max_lines = 4; o->peel_halfwidth = 8; o->min_seg = 64; o->wide_threshold = 8.0f;
-}
-
-// radon_point for a working row between two cells (a band's centre line, steps 15 and 16)
-static void radon_point_mid(const RadonDev &p, int q, int c, double r, double &x, double &y) {
-    double i, j;
-    if (q == 0) { i = c; j = r; }
-    else if (q == 1) { i = c; j = (double)(p.hb - 1) - r; }
-    else if (q == 2) { i = r; j = c; }
-    else { i = (double)(p.wb - 1) - r; j = c; }
-    x = (double)p.b * i + (double)(p.b - 1) / 2.0;
-    y = (double)p.b * j + (double)(p.b - 1) / 2.0;
-}
-
-// the record of a frame's best band as the caller gets it (o zeroed before): steps 14 and 15
-static void radon_wide_fill(const RadonDev &p, const RadonWideRec &r, float threshold, lfdmi_radon_wide &o) {
-    o.status = r.status;
-    if (o.status != LFDMI_RADON_OK) return;
-    o.q = r.q; o.y0 = r.y0; o.s = r.s; o.n_pix = r.n_pix;
-    o.sum = r.sum; o.snr = r.snr;
-    o.width = r.k;
-    o.found = o.snr >= threshold;
-    const int P = p.P[o.q >> 1];
-    const double mid = (double)(o.width - 1) / 2.0;
-    radon_point_mid(p, o.q, 0, (double)o.y0 + mid, o.x1, o.y1);
-    radon_point_mid(p, o.q, P - 1, (double)(o.y0 + o.s) + mid, o.x2, o.y2);
-    double theta = atan2(-(o.x2 - o.x1), o.y2 - o.y1);
-    const double pi = 3.141592653589793;
-    if (theta < 0.0) theta += pi;
-    if (theta >= pi) theta -= pi;
-    o.theta = theta;
-    o.rho = o.x1 * cos(theta) + o.y1 * sin(theta);
-    const long long run = P - 1, rise = o.s;
-    o.width_px = (double)(o.width * p.b) * ((double)run / sqrt((double)(run * run + rise * rise)));
-}
-
-extern "C" int lfdmi_radon_search_wide(lfdmi_ctx *ctx, lfdmi_radon *s, const void *frames, int dtype, int n, int loc, const float *sigma,
-                                       const lfdmi_radon_wide_params *wp, lfdmi_radon_wide *lines, int32_t *n_lines,
-                                       lfdmi_radon_result *plain) {
-    RadonCall c{ctx, s, "lfdmi_radon_search_wide"};
-    int rc = c.begin();
-    if (rc) return rc;
-    lfdmi_radon_wide_params wq;
-    if (wp) wq = *wp; else lfdmi_default_radon_wide_params(&wq);
-    if (wq.max_width < 1 || wq.max_width > LFDMI_RADON_MAX_WIDTH || (wq.max_width & (wq.max_width - 1)) || wq.max_lines < 1 ||
-        wq.max_lines > LFDMI_RADON_MAX_LINES || wq.peel_halfwidth < 0 || wq.min_seg < 1 || wq.min_seg > s->par.min_len ||
-        !std::isfinite(wq.wide_threshold) || !(wq.wide_threshold > 0))
-        return ctx_fail(ctx, LFDMI_ERR_ARG, "radon wide params out of range (include/lfdmi.h: lfdmi_radon_wide_params)");
-    if ((rc = c.args(frames, lines && n_lines, dtype, n, loc, sigma))) return rc;
-    if (n == 0) return 0;
-    const RadonDev &p = c.p;
-    const std::vector<float> &hsig = c.hsig;
-    const int CH = c.CH, K = wq.max_lines;
-    const int hw = (int)(((int64_t)wq.peel_halfwidth + p.b - 1) / p.b);
-    const int pstride = std::max(p.hb, p.wb) + 1;
-    if ((rc = c.stage()) || (rc = radon_rounds_alloc(ctx, s, pstride))) return rc;
-    {   // (each buffer on its own: a call that failed between two allocates only what is missing)
-        const size_t F = (size_t)CH, np = (size_t)4 * s->wstride * 2;
-        // (into a local first: a failed hipMalloc must leave the handle's pointer null for the next call and for destroy)
-        if (!s->wpart) {
-            void *m = nullptr;
-            UHIP(hipMalloc(&m, F * np * sizeof(RadonWidePart)));
-            s->wpart = (RadonWidePart *)m;
-            s->bytes += (int64_t)(F * np * sizeof(RadonWidePart));
-        }
-        if (!s->wrec) {
-            void *m = nullptr;
-            UHIP(hipMalloc(&m, F * sizeof(RadonWideRec)));
-            s->wrec = (RadonWideRec *)m;
-            s->bytes += (int64_t)(F * sizeof(RadonWideRec));
-        }
-        if (!s->wid) {
-            void *m = nullptr;
-            UHIP(hipMalloc(&m, F * sizeof(int)));
-            s->wid = (int *)m;
-            s->bytes += (int64_t)(F * sizeof(int));
-        }
-    }
-    hipStream_t st = c.st;
-    memset(lines, 0, (size_t)n * K * sizeof(*lines));
-    memset(n_lines, 0, (size_t)n * sizeof(*n_lines));
-    float *Vs[2] = {s->V, s->V2};
-    uint16_t *Ms[2] = {s->M, s->M2};
-    std::vector<RadonWideRec> hrec(CH);
+    std::vector<typename Mode::Rec> hrec(CH);
     std::vector<RadonRec> hplain(plain ? n : 0);
     // (round k's host buffers are read or written by copies that finish with round k + 1's wait: two of each alternate)
     std::vector<RadonLineDev> hl[2];
@@ -690,55 +468,57 @@ extern "C" int lfdmi_radon_search_wide(lfdmi_ctx *ctx, lfdmi_radon *s, const voi
         if ((rc = c.chunk(c0, nf))) return rc;
         alive.resize(nf);
         for (int a = 0; a < nf; a++) alive[a] = c0 + a;     // slot -> frame
-        int cur = 0, pending = -1;
+        int cur = 0, pending = -1;                          // pending: the round whose segments are on their way to hx[round & 1]
+        // the segments of round k's found lines, once their copy has been waited for
         auto segments = [&](int k) {
             const int b = k & 1;
             for (size_t e = 0; e < found_frames[b].size(); e++) {
-                lfdmi_radon_wide &o = lines[(size_t)found_frames[b][e] * K + k];
+                Out &o = lines[(size_t)found_frames[b][e] * K + k];
                 const RadonExtDev &x = hx[b][e];
                 const int P = p.P[o.q >> 1];
-                const double mid = (double)(o.width - 1) / 2.0;
+                const double mid = radon_mid(m.width(o));
                 o.c1 = x.c1; o.c2 = x.c2; o.seg_n_pix = x.n; o.seg_sum = x.sum; o.seg_snr = x.snr;
-                radon_point_mid(p, o.q, o.c1, (double)(o.y0 + radon_path(o.c1, o.s, P)) + mid, o.ex1, o.ey1);
-                radon_point_mid(p, o.q, o.c2, (double)(o.y0 + radon_path(o.c2, o.s, P)) + mid, o.ex2, o.ey2);
+                radon_point(p, o.q, o.c1, (double)(o.y0 + radon_path(o.c1, o.s, P)) + mid, o.ex1, o.ey1);
+                radon_point(p, o.q, o.c2, (double)(o.y0 + radon_path(o.c2, o.s, P)) + mid, o.ex2, o.ey2);
             }
         };
         for (int k = 0; k < K && !alive.empty(); k++) {
             const int na = (int)alive.size(), b = k & 1;
-            rc = radon_transform(ctx, s, p, Vs[cur], Ms[cur], na, st, nullptr, true, wq.max_width);
-            if (rc) return rc;
-            UHIP(hipMemcpyAsync(hrec.data(), s->wrec, (size_t)na * sizeof(RadonWideRec), hipMemcpyDeviceToHost, st));
-            // round 0's width-1 pass is step 5: the plain search's record comes with it
+            if ((rc = m.transform(c, Vs[cur], Ms[cur], na, k))) return rc;
+            UHIP(hipMemcpyAsync(hrec.data(), m.rec(), (size_t)na * sizeof(hrec[0]), hipMemcpyDeviceToHost, st));
             if (k == 0 && plain) UHIP(hipMemcpyAsync(hplain.data() + c0, s->rec, (size_t)na * sizeof(RadonRec), hipMemcpyDeviceToHost, st));
             UHIP(hipStreamSynchronize(st));
             if (pending >= 0) { segments(pending); pending = -1; }
             hl[b].clear(); found_frames[b].clear(); hs[b].clear(); hwid[b].clear();
             for (int a = 0; a < na; a++) {
-                lfdmi_radon_wide &o = lines[(size_t)alive[a] * K + k];
-                radon_wide_fill(p, hrec[a], wq.wide_threshold, o);
+                Out &o = lines[(size_t)alive[a] * K + k];
+                m.fill(p, hrec[a], o);
                 if (!o.found) continue;
                 n_lines[alive[a]] = k + 1;
                 hl[b].push_back(RadonLineDev{a, o.q, o.y0, o.s});
-                hwid[b].push_back(o.width);
+                if (m.width(o)) hwid[b].push_back(m.width(o));
                 found_frames[b].push_back(alive[a]);
-                hs[b].push_back(hsig[alive[a]]);
+                hs[b].push_back(c.hsig[alive[a]]);
             }
             const int nl = (int)hl[b].size();
             if (!nl) break;
             hx[b].resize(nl);
+            // (a mode with widths has one for every found line; the others pass none and upload nothing)
+            const int *wid = (int)hwid[b].size() == nl ? s->wid : nullptr;
             UHIP(hipMemcpyAsync(s->lnd, hl[b].data(), (size_t)nl * sizeof(RadonLineDev), hipMemcpyHostToDevice, st));
-            UHIP(hipMemcpyAsync(s->wid, hwid[b].data(), (size_t)nl * sizeof(int), hipMemcpyHostToDevice, st));
-            k_radon_extent<<<nl, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, s->sigma, wq.min_seg, s->pre, s->cnt, pstride, s->ext, s->wid);
+            if (wid) UHIP(hipMemcpyAsync(s->wid, hwid[b].data(), (size_t)nl * sizeof(int), hipMemcpyHostToDevice, st));
+            k_radon_extent<<<nl, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, s->sigma, m.q.min_seg, s->pre, s->cnt, pstride, s->ext, wid);
             ULAUNCH("k_radon_extent");
             UHIP(hipMemcpyAsync(hx[b].data(), s->ext, (size_t)nl * sizeof(RadonExtDev), hipMemcpyDeviceToHost, st));
             pending = k;
             if (k + 1 == K) break;
+            // the found frames go on: slot e of the other set is the frame of line e
             if (p.wb % 8 == 0) {
                 const dim3 grid(ceil_div(p.wb, RAD_THREADS * 8), ceil_div(p.hb, RADL_ROWS), nl);
-                k_radon_peel<8><<<grid, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, hw, Vs[cur ^ 1], Ms[cur ^ 1], s->wid);
+                k_radon_peel<8><<<grid, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, hw, Vs[cur ^ 1], Ms[cur ^ 1], wid);
             } else {
                 const dim3 grid(ceil_div(p.wb, RAD_THREADS), ceil_div(p.hb, RADL_ROWS), nl);
-                k_radon_peel<1><<<grid, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, hw, Vs[cur ^ 1], Ms[cur ^ 1], s->wid);
+                k_radon_peel<1><<<grid, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, hw, Vs[cur ^ 1], Ms[cur ^ 1], wid);
             }
             ULAUNCH("k_radon_peel");
             UHIP(hipMemcpyAsync(s->sigma, hs[b].data(), (size_t)nl * sizeof(float), hipMemcpyHostToDevice, st));
@@ -756,4 +536,78 @@ extern "C" int lfdmi_radon_search_wide(lfdmi_ctx *ctx, lfdmi_radon *s, const voi
             radon_fill(s, p, hplain[i], plain[i]);
         }
     return 0;
+}
+
+extern "C" int lfdmi_radon_search_lines(lfdmi_ctx *ctx, lfdmi_radon *s, const void *frames, int dtype, int n, int loc, const float *sigma,
+                                        const lfdmi_radon_lines_params *lp, lfdmi_radon_line *lines, int32_t *n_lines) {
+    RadonCall c{ctx, s, "lfdmi_radon_search_lines"};
+    int rc = c.begin();
+    if (rc) return rc;
+    RadonLinesMode m{s};
+    if (lp) m.q = *lp; else lfdmi_default_radon_lines_params(&m.q);
+    if (m.q.max_lines < 1 || m.q.max_lines > LFDMI_RADON_MAX_LINES || m.q.peel_halfwidth < 0 || m.q.min_seg < 1 || m.q.min_seg > s->par.min_len)
+        return ctx_fail(ctx, LFDMI_ERR_ARG, "radon lines params out of range (include/lfdmi.h: lfdmi_radon_lines_params)");
+    if ((rc = c.args(frames, lines && n_lines, dtype, n, loc, sigma))) return rc;
+    if (n == 0) return 0;
+    if ((rc = c.stage()) || (rc = radon_rounds_alloc(ctx, s))) return rc;
+    return radon_rounds(c, m, lines, n_lines, nullptr);
+}
+
+extern "C" void lfdmi_default_radon_short_params(lfdmi_radon_short_params *o) {
+    if (!o) return;
+    memset(o, 0, sizeof(*o));
+    o->min_strip = 64; o->max_lines = 4; o->peel_halfwidth = 8; o->min_seg = 32; o->short_threshold = 8.5f;
+}
+
+extern "C" int lfdmi_radon_search_short(lfdmi_ctx *ctx, lfdmi_radon *s, const void *frames, int dtype, int n, int loc, const float *sigma,
+                                        const lfdmi_radon_short_params *sp, lfdmi_radon_short *lines, int32_t *n_lines,
+                                        lfdmi_radon_result *plain) {
+    RadonCall c{ctx, s, "lfdmi_radon_search_short"};
+    int rc = c.begin();
+    if (rc) return rc;
+    RadonShortMode m{s};
+    lfdmi_radon_short_params &sq = m.q;
+    if (sp) sq = *sp; else lfdmi_default_radon_short_params(&sq);
+    const int bb = s->p.b * s->p.b;
+    if (sq.min_strip < 64 || (sq.min_strip & (sq.min_strip - 1)) || sq.max_lines < 1 || sq.max_lines > LFDMI_RADON_MAX_LINES ||
+        sq.peel_halfwidth < 0 || sq.min_seg < 1 || (int64_t)sq.min_seg > (int64_t)sq.min_strip * bb / 2 ||
+        !std::isfinite(sq.short_threshold) || !(sq.short_threshold > 0))
+        return ctx_fail(ctx, LFDMI_ERR_ARG, "radon short params out of range (include/lfdmi.h: lfdmi_radon_short_params)");
+    if ((rc = c.args(frames, lines && n_lines, dtype, n, loc, sigma))) return rc;
+    if (n == 0) return 0;
+    // (the partial records in the layout for min_strip = 64, which holds every other)
+    const size_t F = (size_t)c.CH, total = (size_t)std::max(1LL, radon_short_layout(c.p, 64).total);
+    if ((rc = c.stage()) || (rc = radon_rounds_alloc(ctx, s)) || (rc = radon_lazy(ctx, s, &s->spart, F * total)) ||
+        (rc = radon_lazy(ctx, s, &s->srec, F)))
+        return rc;
+    m.sd = radon_short_layout(c.p, sq.min_strip);
+    return radon_rounds(c, m, lines, n_lines, plain);
+}
+
+extern "C" void lfdmi_default_radon_wide_params(lfdmi_radon_wide_params *o) {
+    if (!o) return;
+    memset(o, 0, sizeof(*o));
+    o->max_width = 8; o->max_lines = 4; o->peel_halfwidth = 8; o->min_seg = 64; o->wide_threshold = 8.0f;
+}
+
+extern "C" int lfdmi_radon_search_wide(lfdmi_ctx *ctx, lfdmi_radon *s, const void *frames, int dtype, int n, int loc, const float *sigma,
+                                       const lfdmi_radon_wide_params *wp, lfdmi_radon_wide *lines, int32_t *n_lines,
+                                       lfdmi_radon_result *plain) {
+    RadonCall c{ctx, s, "lfdmi_radon_search_wide"};
+    int rc = c.begin();
+    if (rc) return rc;
+    RadonWideMode m{s};
+    lfdmi_radon_wide_params &wq = m.q;
+    if (wp) wq = *wp; else lfdmi_default_radon_wide_params(&wq);
+    if (wq.max_width < 1 || wq.max_width > LFDMI_RADON_MAX_WIDTH || (wq.max_width & (wq.max_width - 1)) || wq.max_lines < 1 ||
+        wq.max_lines > LFDMI_RADON_MAX_LINES || wq.peel_halfwidth < 0 || wq.min_seg < 1 || wq.min_seg > s->par.min_len ||
+        !std::isfinite(wq.wide_threshold) || !(wq.wide_threshold > 0))
+        return ctx_fail(ctx, LFDMI_ERR_ARG, "radon wide params out of range (include/lfdmi.h: lfdmi_radon_wide_params)");
+    if ((rc = c.args(frames, lines && n_lines, dtype, n, loc, sigma))) return rc;
+    if (n == 0) return 0;
+    const size_t F = (size_t)c.CH;
+    if ((rc = c.stage()) || (rc = radon_rounds_alloc(ctx, s)) || (rc = radon_lazy(ctx, s, &s->wpart, F * 4 * s->wstride * 2)) ||
+        (rc = radon_lazy(ctx, s, &s->wrec, F)) || (rc = radon_lazy(ctx, s, &s->wid, F)))
+        return rc;
+    return radon_rounds(c, m, lines, n_lines, plain);
 }

@@ -53,6 +53,33 @@ def kernel_bytes(shape, b):
     return out
 
 
+def timed(call, reps):
+    """(what the last call returned, the ms of each of ``reps`` calls between HIP events), after one warm-up call: module load,
+    first touch, the buffers a search allocates on its first call"""
+    import torch
+    out, ms = call(), []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = call()
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return out, ms
+
+
+def peel_mode(name, r, call, a, lines_round=None):
+    """a peeling search's records and its keys of the result; lines_round: search_lines' ms per frame-round, the yardstick"""
+    import numpy as np
+    (recs, nl), ms = timed(call, a.reps)
+    rounds = int(np.minimum(nl + 1, a.lines).sum())               # frame-rounds the call ran
+    med = float(np.median(ms))
+    out = {"ms_per_call": med, "ms_all": ms, "found": int(nl.sum()), "frame_rounds": rounds, "ms_per_frame_round": med / rounds}
+    if lines_round is not None:
+        out["over_lines_per_frame_round"] = med / rounds / lines_round
+    return recs, {**{"%s_%s" % (name, k): v for k, v in out.items()}, "bytes_with_" + name: r.dims()[2]}
+
+
 def child(a):
     import numpy as np
     import torch
@@ -64,68 +91,20 @@ def child(a):
         frames[::2, h // 3, :] += 0.02                       # a faint row: every second frame peels at least once
     for b in ((a.bin,) if a.bin else (1, 2, 4)):
         with _native.Context(0, h, w, 2) as ctx, _native.Radon(ctx, SHAPE, max_frames=a.max_frames, bin=b) as r:
-            rec = r.search(frames)                                  # warm-up: module load, first touch
-            ms = []
-            for _ in range(a.reps):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                rec = r.search(frames)
-                e1.record()
-                e1.synchronize()
-                ms.append(e0.elapsed_time(e1))
+            rec, ms = timed(lambda: r.search(frames), a.reps)
+            med = float(np.median(ms))
             lines = {}
             if a.lines:
-                recs, nl = r.search_lines(frames, max_lines=a.lines)      # warm-up: the second V, M set
-                lms = []
-                for _ in range(a.reps):
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    recs, nl = r.search_lines(frames, max_lines=a.lines)
-                    e1.record()
-                    e1.synchronize()
-                    lms.append(e0.elapsed_time(e1))
-                rounds = int(np.minimum(nl + 1, a.lines).sum())           # frame-rounds the call ran
-                lmed = float(np.median(lms))
-                lines = {"lines_max": a.lines, "lines_ms_per_call": lmed, "lines_ms_all": lms, "lines_found": int(nl.sum()),
-                         "lines_frame_rounds": rounds, "lines_ms_per_frame_round": lmed / rounds,
-                         "plain_ms_per_call": float(np.median(ms)), "bytes_with_lines": r.dims()[2]}
+                _, lines = peel_mode("lines", r, lambda: r.search_lines(frames, max_lines=a.lines), a)
+                lines.update({"lines_max": a.lines, "plain_ms_per_call": med})
             if a.short:
-                srecs, snl = r.search_short(frames, max_lines=a.lines)    # warm-up: the partial records
-                sms = []
-                for _ in range(a.reps):
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    srecs, snl = r.search_short(frames, max_lines=a.lines)
-                    e1.record()
-                    e1.synchronize()
-                    sms.append(e0.elapsed_time(e1))
-                srounds = int(np.minimum(snl + 1, a.lines).sum())
-                smed = float(np.median(sms))
-                lines.update({"short_ms_per_call": smed, "short_ms_all": sms, "short_found": int(snl.sum()),
-                              "short_frame_rounds": srounds, "short_ms_per_frame_round": smed / srounds,
-                              "short_over_lines_per_frame_round": smed / srounds / lines["lines_ms_per_frame_round"],
-                              "short_levels": sorted({int(v) for v in srecs["level"][srecs["status"] == 0]}),
-                              "bytes_with_short": r.dims()[2]})
+                srecs, more = peel_mode("short", r, lambda: r.search_short(frames, max_lines=a.lines), a, lines["lines_ms_per_frame_round"])
+                lines.update(more, short_levels=sorted({int(v) for v in srecs["level"][srecs["status"] == 0]}))
             if a.wide:
-                wrecs, wnl = r.search_wide(frames, max_lines=a.lines)     # warm-up: the partial records
-                wms = []
-                for _ in range(a.reps):
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    wrecs, wnl = r.search_wide(frames, max_lines=a.lines)
-                    e1.record()
-                    e1.synchronize()
-                    wms.append(e0.elapsed_time(e1))
-                wrounds = int(np.minimum(wnl + 1, a.lines).sum())
-                wmed = float(np.median(wms))
-                lines.update({"wide_ms_per_call": wmed, "wide_ms_all": wms, "wide_found": int(wnl.sum()),
-                              "wide_frame_rounds": wrounds, "wide_ms_per_frame_round": wmed / wrounds,
-                              "wide_over_lines_per_frame_round": wmed / wrounds / lines["lines_ms_per_frame_round"],
-                              "wide_widths": sorted({int(v) for v in wrecs["width"][wrecs["status"] == 0]}),
-                              "bytes_with_wide": r.dims()[2]})
+                wrecs, more = peel_mode("wide", r, lambda: r.search_wide(frames, max_lines=a.lines), a, lines["lines_ms_per_frame_round"])
+                lines.update(more, wide_widths=sorted({int(v) for v in wrecs["width"][wrecs["status"] == 0]}))
             kb = kernel_bytes(SHAPE, b)
             total = float(sum(kb.values())) * a.frames
-            med = float(np.median(ms))
             print("RESULT " + json.dumps({
                 "bin": b, "frames": a.frames, "max_frames": a.max_frames, "shape": list(SHAPE), "P": [r.p01, r.p23],
                 "device_bytes_per_inflight_frame": r.bytes // a.max_frames, "ms_per_call": med, "ms_all": ms,
