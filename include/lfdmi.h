@@ -879,6 +879,110 @@ int lfdmi_light_curves(lfdmi_ctx *ctx, const void *frames, int dtype, int n, int
                        const lfdmi_lc_segment *segs, int n_seg, const float *sigma, const lfdmi_lc_params *p, lfdmi_lc *out,
                        lfdmi_lc_section *sections, int max_sections_per_seg);
 
+/* ---- trail strips -----------------------------------------------------------------------------------------------------------
+ * lfdmi_trail_strips gives the band around a segment itself, straightened: a map of n_sec sections along the trail by n_off
+ * offsets across it.  The stacked cross-sections keep the offsets and sum along the trail, the light curves keep the sections
+ * and sum across it; a strip keeps both, which is what a person or a classifier looks at to accept a detection, what shows a
+ * width or a centre that changes along the trail, and what checks the other two units: a strip summed over its offsets is a
+ * light curve's integers.  The reference has no such step.  The procedure below is the definition; tests/strip_ref.py restates
+ * it in numpy and the device reproduces it in every integer and every bit of every double: a pixel enters a cell as a
+ * fixed-point integer, so the sums are integer sums and nothing depends on the order in which the device works, and every
+ * double is made on the host by a fixed sequence of rounded operations.
+ *
+ * 1. Pixels: exactly step 1 of the light curves.  The frame is the flipped one; a pixel is valid when it is finite, not +-0,
+ *    |v| <= clip and (mask & skip_bits) == 0; a valid pixel enters as q = llrint((double)v * 1073741824.0).
+ * 2. Geometry of a segment: dx, dy, L, e, nrm exactly as step 2 of the trail masks.  On the host, in double:
+ *        inv_s = 1.0 / sec_len;  inv_u = 1.0 / step;  n_sec = max(1, (int)ceil(L * inv_s));
+ *        K = max(0, (int)ceil(half * inv_u - 0.5));  n_off = 2 K + 1;  kc = (double)K + 0.5.
+ *    The segment is LFDMI_STRIP_BAD_SEGMENT when an end point is not finite, a coordinate exceeds 1e6 in magnitude, L == 0,
+ *    half is not finite or <= 0, or n_off > LFDMI_STRIP_MAX_OFF.  It is LFDMI_STRIP_TOO_LONG when n_sec >
+ *    max_sections_per_seg (at most LFDMI_STRIP_MAX_SECTIONS) or n_sec * n_off > max_cells_per_seg.
+ * 3. Membership of the pixel centre (x, y): u and t exactly as step 3 of the trail masks (double, left to right, no
+ *    contraction).  The pixel takes part iff t >= 0 && t <= L && fabs(u) <= half.  Its section is j = min((int)floor(t *
+ *    inv_s), n_sec - 1), its offset bin b = min(max((int)floor(u * inv_u + kc), 0), 2 K).  The centre of bin b is u_b =
+ *    (double)(b - K) * step.
+ * 4. Cells, three exact integers per (segment, j, b): n_geom = the pixels of the frame in the cell, valid or not; n = the valid
+ *    ones; q = the sum of their q.  Cell (j, b) is record j * n_off + b of the segment's row of `cells`; the records past n_sec *
+ *    n_off, and every record of a segment that is not measured, are zero bytes.  Integer addition has no order, so crossing
+ *    segments, shared tiles and atomics need no rule.
+ * 5. Section record j, on the host in double, each operation rounded, left to right, b ascending.  t0 = j * sec_len, t1 = min((j
+ *    + 1) * sec_len, L).  hw = half - wing; bin b is a wing bin iff fabs(u_b) >= hw, else a core bin.  n_geom = the sum of the
+ *    cells' n_geom; n_core and n_wing = the sums of n over the core and the wing bins; Q_wing = the int64 sum of q over the wing
+ *    bins.  status LFDMI_STRIP_SEC_EMPTY when n_geom == 0; else LFDMI_STRIP_SEC_LOW when n_core < min_core or n_wing < min_wing;
+ *    in both the doubles below are NaN and the integers are kept.  Else LFDMI_STRIP_SEC_OK and, with sigma the frame's sky sigma:
+ *        bkg = (double)Q_wing * 2^-30 / (double)n_wing;
+ *        S0 = S1 = S2 = R = 0.0;  nc = 0;  for every core bin with n_b > 0, b ascending:
+ *            m = (double)q_b * 2^-30 / (double)n_b;  v = m - bkg;
+ *            S0 = S0 + v;  S1 = S1 + v * u_b;  S2 = S2 + v * u_b * u_b;  R = R + 1.0 / (double)n_b;  nc = nc + 1;
+ *        rate = S0 * step                        (the flux per px of trail length, as the light curves' rate and the stack's flux);
+ *        rate_err = sigma * step * sqrt(R + (double)nc * (double)nc / (double)n_wing);
+ *        if rate >= k_mom * rate_err:  centre = S1 / S0;  d = S2 / S0 - centre * centre;  width = sqrt(d > 0.0 ? d : 0.0);
+ *        else centre = width = NaN.
+ *    The rows j >= n_sec of a segment, and every row of a segment that is not measured, are zero bytes.
+ * 6. Segment record.  status LFDMI_STRIP_OK, LFDMI_STRIP_BAD_SEGMENT, LFDMI_STRIP_TOO_LONG, or LFDMI_STRIP_EMPTY for a good
+ *    segment without an OK section; n_sec, n_off, K; n_ok = the OK sections.  Over the OK sections whose centre is finite, j
+ *    ascending (n_mom of them):
+ *        mean_centre = (sum of n_core_j * centre_j) / (sum of n_core_j);   mean_width = (sum of n_core_j * width_j) / (the same);
+ *        max_dev = the largest fabs(centre_j - mean_centre), dev_section its j (ties: the lowest).
+ *    Without such a section the three doubles are NaN and dev_section = -1.  A BAD_SEGMENT or TOO_LONG record has NaN doubles
+ *    and zero integers.
+ * No transcendental function but sqrt appears anywhere.  The per-cell mean (float)((double)q * 2^-30 / (double)n) is made by
+ * the caller (lfd_amd/strips.py).
+ *
+ * The device follows the light curves: it culls 64 x 16 pixel tiles against every segment's band (|u| <= half, t in [0, L],
+ * widened by the tile's half extents; k_strip_cull) and runs persistent blocks over the surviving (frame, tile) pairs
+ * (k_strip_render).  A thread loads its pixels once, tests them and converts them to q; the cells of a tile go through a table
+ * in LDS (integer atomics) and from there to memory with one integer atomicAdd per non-zero entry.  There is no float sum and
+ * no float atomic on the device. */
+#define LFDMI_STRIP_MAX_SECTIONS 1024  /* largest max_sections_per_seg */
+#define LFDMI_STRIP_MAX_OFF 129        /* largest n_off */
+enum { LFDMI_STRIP_OK = 0, LFDMI_STRIP_BAD_SEGMENT = 1, LFDMI_STRIP_TOO_LONG = 2, LFDMI_STRIP_EMPTY = 3 };
+enum { LFDMI_STRIP_SEC_OK = 0, LFDMI_STRIP_SEC_LOW = 1, LFDMI_STRIP_SEC_EMPTY = 2 };
+typedef struct {
+    int32_t frame;            /* 0 .. n-1 */
+    int32_t pad;
+    double x1, y1, x2, y2;    /* flipped frame, as lfdmi_mask_segment */
+    double half;              /* the band: |u| <= half (> 0, finite), its outermost `wing` px on either side are sky */
+} lfdmi_strip_segment;
+typedef struct {
+    double sec_len;           /* section length in px (4 .. 4096); default 8 */
+    double step;              /* offset bin in px (0.5 .. 8); default 1 */
+    double wing;              /* the bins with |u_b| >= half - wing are sky (> 0, finite); default 6 */
+    double k_mom;             /* centre and width need rate >= k_mom * rate_err (>= 0, finite); default 5 */
+    float clip;               /* a pixel above clip in magnitude is invalid (finite, 0 < clip <= 1024); default 0.125 */
+    int32_t min_core;         /* valid core pixels an OK section needs (>= 1); default 8 */
+    int32_t min_wing;         /* and valid wing pixels (>= 1); default 8 */
+    int32_t pad;
+} lfdmi_strip_params;
+typedef struct {
+    int32_t n_geom, n;
+    int64_t q;
+} lfdmi_strip_cell;
+typedef struct {
+    int32_t status;           /* LFDMI_STRIP_SEC_* */
+    int32_t n_geom, n_core, n_wing;
+    double t0, t1;            /* the section along the segment, px from (x1, y1) */
+    double bkg, rate, rate_err, centre, width;
+} lfdmi_strip_section;
+typedef struct {
+    int32_t status;           /* LFDMI_STRIP_* */
+    int32_t n_sec, n_off, K, n_ok, n_mom, dev_section;
+    int32_t pad;
+    double mean_centre, mean_width, max_dev;
+} lfdmi_strip;
+void lfdmi_default_strip_params(lfdmi_strip_params *out);
+/* frames, mask, skip_bits, segs, sigma: as lfdmi_light_curves takes them.  p NULL: the defaults.  out: n_seg records;
+ * sections: n_seg x max_sections_per_seg records, max_sections_per_seg 1 .. LFDMI_STRIP_MAX_SECTIONS; cells: n_seg x
+ * max_cells_per_seg records, max_cells_per_seg 1 .. LFDMI_STRIP_MAX_SECTIONS * LFDMI_STRIP_MAX_OFF (all host).  LFDMI_ERR_ARG,
+ * and no output is touched: a bad dtype or loc, n or n_seg < 0, h or w outside 1 .. 65536 or h * w > 1e9, a NULL argument that
+ * is needed, a bad max_sections_per_seg, max_cells_per_seg or skip_bits, parameters out of range, a frame outside [0, n), a bad
+ * sigma.  The call keeps no state (its device memory comes from the stream's pool and goes back before it returns; the
+ * segments go through the device in batches of at most 512 MiB of cells), refuses while calls are in flight, runs on the
+ * context's stream and waits for it once. */
+int lfdmi_trail_strips(lfdmi_ctx *ctx, const void *frames, int dtype, int n, int h, int w, int loc, const uint8_t *mask, int skip_bits,
+                       const lfdmi_strip_segment *segs, int n_seg, const float *sigma, const lfdmi_strip_params *p, lfdmi_strip *out,
+                       lfdmi_strip_section *sections, int max_sections_per_seg, lfdmi_strip_cell *cells, int max_cells_per_seg);
+
 /* ---- faint-trail search -----------------------------------------------------------------------------------------------------
  * The detector finds a trail whose pixels survive the 8-bit conversion; lfdmi_radon_search finds one that is faint in every
  * pixel but long: it sums the frame along every line of a dyadic family (the fast Radon transform of Goetz and Druckmueller /

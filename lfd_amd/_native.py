@@ -42,6 +42,7 @@ SYMBOLS = (
     "lfdmi_inject_trails",
     "lfdmi_default_mask_params", "lfdmi_mask_trails",
     "lfdmi_default_lc_params", "lfdmi_light_curves",
+    "lfdmi_default_strip_params", "lfdmi_trail_strips",
     "lfdmi_default_radon_params", "lfdmi_radon_create", "lfdmi_radon_destroy", "lfdmi_radon_dims", "lfdmi_radon_search",
     "lfdmi_default_radon_lines_params", "lfdmi_radon_search_lines",
     "lfdmi_default_radon_short_params", "lfdmi_radon_search_short",
@@ -254,6 +255,51 @@ def make_lc_params(**params):
     return _make_params(LcParamsStruct, "lfdmi_default_lc_params", "light curve", params)
 
 
+class StripParamsStruct(C.Structure):
+    """lfdmi_strip_params (include/lfdmi.h: trail strips)."""
+    _fields_ = [("sec_len", C.c_double), ("step", C.c_double), ("wing", C.c_double), ("k_mom", C.c_double), ("clip", C.c_float),
+                ("min_core", C.c_int32), ("min_wing", C.c_int32), ("pad", C.c_int32)]
+
+
+STRIP_PARAMS = StripParamsStruct
+# lfdmi_strip_segment: one record per segment of lfdmi_trail_strips; lfdmi_strip: its result; lfdmi_strip_section: one per
+# section; lfdmi_strip_cell: one per (section, offset bin)
+STRIP_SEGMENT_DTYPE = np.dtype([("frame", "<i4"), ("pad", "<i4"), ("x1", "<f8"), ("y1", "<f8"), ("x2", "<f8"), ("y2", "<f8"),
+                                ("half", "<f8")])
+STRIP_DTYPE = np.dtype([("status", "<i4"), ("n_sec", "<i4"), ("n_off", "<i4"), ("K", "<i4"), ("n_ok", "<i4"), ("n_mom", "<i4"),
+                        ("dev_section", "<i4"), ("pad", "<i4"), ("mean_centre", "<f8"), ("mean_width", "<f8"), ("max_dev", "<f8")])
+STRIP_SECTION_DTYPE = np.dtype([("status", "<i4"), ("n_geom", "<i4"), ("n_core", "<i4"), ("n_wing", "<i4"), ("t0", "<f8"), ("t1", "<f8"),
+                                ("bkg", "<f8"), ("rate", "<f8"), ("rate_err", "<f8"), ("centre", "<f8"), ("width", "<f8")])
+STRIP_CELL_DTYPE = np.dtype([("n_geom", "<i4"), ("n", "<i4"), ("q", "<i8")])
+STRIP_OK, STRIP_BAD_SEGMENT, STRIP_TOO_LONG, STRIP_EMPTY = 0, 1, 2, 3
+STRIP_SEC_OK, STRIP_SEC_LOW, STRIP_SEC_EMPTY = 0, 1, 2
+STRIP_MAX_SECTIONS = 1024
+STRIP_MAX_OFF = 129
+
+
+def make_strip_params(**params):
+    """lfdmi_default_strip_params with the given fields replaced (unknown names raise)."""
+    if "pad" in params:
+        raise TypeError("unknown strip parameter 'pad'")
+    return _make_params(StripParamsStruct, "lfdmi_default_strip_params", "strip", params)
+
+
+def strip_cells_needed(segs, p, max_sections):
+    """the largest n_sec * n_off of the segments that fit max_sections rows (step 2 of the trail strips, in the header's
+    operations), at least 1: the ``max_cells`` with which no such segment is TOO_LONG"""
+    most = 1
+    inv_s, inv_u = np.float64(1.0) / np.float64(p.sec_len), np.float64(1.0) / np.float64(p.step)
+    for s in segs:
+        with np.errstate(all="ignore"):
+            dx, dy = np.float64(s["x2"]) - np.float64(s["x1"]), np.float64(s["y2"]) - np.float64(s["y1"])
+            ns = np.ceil(np.sqrt(dx * dx + dy * dy) * inv_s)
+            kk = np.ceil(np.float64(s["half"]) * inv_u - np.float64(0.5))
+        if not (np.isfinite(ns) and np.isfinite(kk)) or ns > max_sections or 2 * kk + 1 > STRIP_MAX_OFF:
+            continue
+        most = max(most, max(1, int(ns)) * (2 * max(0, int(kk)) + 1))
+    return most
+
+
 class RadonParamsStruct(C.Structure):
     """lfdmi_radon_params (include/lfdmi.h: faint-trail search)."""
     _fields_ = [("bin", C.c_int32), ("min_len", C.c_int32), ("clip", C.c_float), ("threshold", C.c_float)]
@@ -454,6 +500,10 @@ def lib():
         _lib.lfdmi_default_lc_params.argtypes = [C.c_void_p]
         _lib.lfdmi_light_curves.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                             C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        _lib.lfdmi_default_strip_params.restype = None
+        _lib.lfdmi_default_strip_params.argtypes = [C.c_void_p]
+        _lib.lfdmi_trail_strips.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                            C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
         _lib.lfdmi_default_radon_params.restype = None
         _lib.lfdmi_default_radon_params.argtypes = [C.c_void_p]
         _lib.lfdmi_radon_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
@@ -1276,6 +1326,46 @@ class Context:
         self._chk(self._lib.lfdmi_light_curves(self._h, _ptr(frames), code, n, h, w, loc, _ptr(mask), int(skip_bits), _ptr(sg), len(sg),
                                                _ptr(sig), C.byref(p), _ptr(out), _ptr(sec), m))
         return out, sec
+
+    # -- trail strips (lfdmi_trail_strips) ----------------------------------------------------------------------------------------
+    def trail_strips(self, frames, segs, mask=None, skip_bits=0, sigma=None, max_sections=256, max_cells=None, pinned=False,
+                     native_device=False, **params):
+        """The straightened band of every segment (include/lfdmi.h: trail strips).  frames, segs' coordinates, mask, skip_bits and
+        sigma: what ``light_curves`` takes; segs: STRIP_SEGMENT_DTYPE records; params: fields of lfdmi_strip_params.  max_cells:
+        the cells a segment may have (default: what the longest segment of the call needs, at most max_sections x 129).  Returns
+        (STRIP_DTYPE records [n_seg], STRIP_SECTION_DTYPE records [n_seg, max_sections], STRIP_CELL_DTYPE records [n_seg,
+        max_cells]); cell (j, b) of segment i is [i, j * n_off + b]."""
+        frames, code, n, h, w, loc = self._frames(frames, pinned, "trail_strips", native_device=native_device)
+        sg = np.ascontiguousarray(segs, STRIP_SEGMENT_DTYPE).reshape(-1)
+        p = make_strip_params(**params)
+        sig = _sigma(sigma, n)
+        m = int(max_sections)
+        if not 1 <= m <= STRIP_MAX_SECTIONS:
+            raise ValueError(f"max_sections: 1 .. {STRIP_MAX_SECTIONS}")
+        if max_cells is None:
+            max_cells = strip_cells_needed(sg, p, m)
+        mc = int(max_cells)
+        if not 1 <= mc <= STRIP_MAX_SECTIONS * STRIP_MAX_OFF:
+            raise ValueError(f"max_cells: 1 .. {STRIP_MAX_SECTIONS * STRIP_MAX_OFF}")
+        if mask is not None:
+            shp = tuple(mask.shape)
+            if shp != (n, h, w) and not (n == 1 and shp == (h, w)):      # (one frame may come with a 2-d plane)
+                raise ValueError(f"mask of shape {shp} for frames of shape {(n, h, w)}")
+            if str(mask.dtype).replace("torch.", "") != "uint8":
+                raise TypeError("trail_strips needs a uint8 mask")
+            if _is_dev(mask) != (loc == DEVICE):
+                raise ValueError("trail_strips needs the mask where the frames are")
+            if _is_dev(mask):
+                if not mask.is_contiguous():
+                    raise ValueError("device tensors must be contiguous")
+            else:
+                mask = np.ascontiguousarray(mask)
+        out = np.zeros(len(sg), STRIP_DTYPE)
+        sec = np.zeros((len(sg), m), STRIP_SECTION_DTYPE)
+        cells = np.zeros((len(sg), mc), STRIP_CELL_DTYPE)
+        self._chk(self._lib.lfdmi_trail_strips(self._h, _ptr(frames), code, n, h, w, loc, _ptr(mask), int(skip_bits), _ptr(sg), len(sg),
+                                               _ptr(sig), C.byref(p), _ptr(out), _ptr(sec), m, _ptr(cells), mc))
+        return out, sec, cells
 
     # -- stacked cross-sections (lfdmi_stack_profiles) ----------------------------------------------------------------------------
     def stack_profiles(self, frames, segments, sigma=None, pinned=False, native_device=False, raw=False, **params):

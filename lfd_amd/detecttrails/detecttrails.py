@@ -289,11 +289,12 @@ class _RadonStage:
     the lines' rows with ``lines``."""
 
     def __init__(self, out, params, sigma, lines=None, lines_params=None, seg_out=None, prof_out=None, stack_params=None,
-                 defocus_out=None, defocus_params=None, short=None, short_out=None, lc=None, wide=None, wide_out=None):
+                 defocus_out=None, defocus_params=None, short=None, short_out=None, lc=None, wide=None, wide_out=None, strip=None):
         from ..radon import as_params
         self.out, self.params, self.sigma, self._handles = out, as_params(params), float(sigma), {}
         self.wide, self.wide_out = (dict(wide) if wide is not None else None), wide_out
         self.lc, self.last_lc = lc, {}                # an ``_LcStage``; {position: [(record, sections)]} of the last ``batch`` / ``one``
+        self.strip, self.last_strip = strip, {}       # a ``_StripStage``; {position: its items} likewise
         self.short, self.short_out = (dict(short) if short is not None else None), short_out
         self.lines, self.seg_out = lines, seg_out
         self.lines_params = dict(lines_params or {}, max_lines=lines) if lines is not None else None
@@ -310,6 +311,12 @@ class _RadonStage:
                 self._lc_part = self.lc.radon(handle.ctx, frames, recs, **where)
             except Exception as e:  # noqa: BLE001 - the frames' errors entries; their radon rows stay
                 self._lc_part = [e] * len(recs)
+        self._strip_part = None
+        if self.strip is not None and self.lines is not None:
+            try:
+                self._strip_part = self.strip.radon(handle.ctx, frames, recs, **where)
+            except Exception as e:  # noqa: BLE001 - likewise
+                self._strip_part = [e] * len(recs)
         return recs
 
     def _search_all(self, handle, frames, **where):
@@ -370,7 +377,7 @@ class _RadonStage:
     def batch(self, ctx, frames, shape, todo, **where):
         """the frames ``todo`` (ascending positions in ``frames``), searched in runs of neighbours -> {position: record}"""
         out, k = {}, 0
-        self.last_lc = {}
+        self.last_lc, self.last_strip = {}, {}
         while k < len(todo):
             m = k
             while m + 1 < len(todo) and todo[m + 1] == todo[m] + 1:
@@ -381,6 +388,8 @@ class _RadonStage:
             out.update(zip(range(a, b), recs))
             if self._lc_part is not None:
                 self.last_lc.update(zip(range(a, b), self._lc_part))
+            if self._strip_part is not None:
+                self.last_strip.update(zip(range(a, b), self._strip_part))
             k = m + 1
         return out
 
@@ -390,6 +399,7 @@ class _RadonStage:
         with use_context(*img.shape) as ctx:
             rec = self._search(self._handle(ctx, img.shape, 1), img)[0]
         self.last_lc = {0: self._lc_part[0]} if self._lc_part is not None else {}
+        self.last_strip = {0: self._strip_part[0]} if self._strip_part is not None else {}
         return rec
 
     def row(self, key, rec):
@@ -563,6 +573,58 @@ class _LcStage:
         self.summary_out.flush()
 
 
+class _StripStage:
+    """The trail strips behind the measurements for ``DetectTrails(trail_strips=True)`` (include/lfdmi.h: trail strips): the
+    segments ``_LcStage`` measures, at the same places, each half-width widened by ``wing`` so that the wings are sky
+    (``strips.segments_from_mask_segments``' rule), kept in the chunk's slot until ``_emit`` writes one strips.txt row per section
+    that is not EMPTY and, with ``strips_dir``, the segment's maps (.npz) and preview (.png).  ``sigma``: the frames' sky sigma."""
+
+    def __init__(self, out, params, sigma, half_params=None, strips_dir=None, max_sections=1024):
+        from ..strips import DEFAULT_WING, as_params
+        self.out, self.params, self.sigma, self.strips_dir = out, as_params(params), float(sigma), strips_dir
+        self.wing = float(self.params.get("wing", DEFAULT_WING))
+        self.max_sections = int(max_sections)             # (a results row reaches about 1000 px past the frame: 512 sections of 8 px)
+        self.segs = _MaskStage(None, half_params)
+        if strips_dir is not None:
+            os.makedirs(strips_dir, exist_ok=True)
+
+    def measure(self, ctx, frames, rows, **where):
+        """(frame, x1, y1, x2, y2, half) rows on ``frames`` -> [(record, its sections, its maps, its segment)] in the rows' order"""
+        from .. import strips
+        if not rows:
+            return []
+        segs = strips.segments([(*r[:5], float(r[5]) + self.wing) for r in rows])
+        rec, sec, cells = ctx.trail_strips(frames, segs, sigma=self.sigma, max_sections=self.max_sections, **where, **self.params)
+        return [(rec[k], sec[k], strips.maps(rec[k], cells[k]), segs[k]) for k in range(len(rows))]
+
+    def radon(self, ctx, frames, lines, **where):
+        """a run of frames and their ``_RadonStage`` records -> per frame the items of its found lines"""
+        rows, owner = [], []
+        for j, line in enumerate(lines):
+            for s in self.segs.radon_segments(line):
+                rows.append((j, *s))
+                owner.append(j)
+        out = [[] for _ in lines]
+        for j, item in zip(owner, self.measure(ctx, frames, rows, **where)):
+            out[j].append(item)
+        return out
+
+    def rows(self, key, source, items):
+        from .. import strips
+        for k, (rec, sec, maps, seg) in enumerate(items):
+            text = strips.format_rows(key, source, k, rec, sec)
+            if text:
+                self.out.write("\n".join(text) + "\n")
+            if self.strips_dir is not None:
+                stem = os.path.join(self.strips_dir, "strip-%s-%s-%s-%s-%s%d" % (*key, source, k))
+                _np.savez(stem + ".npz", mean=maps["mean"], n=maps["n"], n_geom=maps["n_geom"],
+                          segment=_np.array([float(seg[f]) for f in ("x1", "y1", "x2", "y2", "half")]))
+                strips.write_png(stem + ".png", maps["mean"])
+
+    def flush(self):
+        self.out.flush()
+
+
 def _load_frame(run, camcol, filter, field, catalog=True):
     """Frame image (float32, C-contiguous), results-row head, photoObj columns; raises like the
     reference when neither the .fits nor the .fits.bz2 exists (detecttrails.py:81-87)."""
@@ -632,11 +694,13 @@ class _Chunk:
     per-frame product gets a slot here, a step in ``_run_group`` and ``_run_frame``, and its row in ``_emit``."""
 
     def __init__(self, n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon=None,
-                 stars=None, masks=None, lc=None):
+                 stars=None, masks=None, lc=None, strip=None):
         self.results, self.errors, self.profiles, self.sky, self.radon, self.stars = results, errors, profiles, sky, radon, stars
         self.masks = masks                            # a ``_MaskStage``: its rows are made in ``_emit``, from the slots below
         self.lc = lc                                  # a ``_LcStage``; ``lcs[i]``: (source, [(record, sections)]) or the exception
         self.lcs = [None] * n
+        self.strip = strip                            # a ``_StripStage``; ``strips[i]``: (source, its items) or the exception
+        self.strips = [None] * n
         self.shapes = [None] * n                      # the shape of a frame that ran on its own
         self.strecs = [None] * n                      # (frame record, n_extended) of the source finder (``stars``: a ``_StarsStage``)
         self.params_bright, self.params_dim, self.params_removestars = params_bright, params_dim, params_removestars
@@ -649,7 +713,7 @@ class _Chunk:
 def _run_frame(c, i, filter, frame):
     """Frame i on its own, under its own try: ``frame()`` -> (float32 img, cat); sky normalisation if on, detection, and the
     trail measurement of a detected frame."""
-    c.lcs[i] = None
+    c.lcs[i] = c.strips[i] = None
     try:
         img, cat = frame()
         c.shapes[i] = tuple(img.shape)
@@ -670,12 +734,22 @@ def _run_frame(c, i, filter, frame):
                     c.lcs[i] = ("detect", c.lc.measure(ctx, fr, [(0, *c.lc.segs.detect_segment(c.rows[i][1], c.meas[i]))]))
             except Exception as e:  # noqa: BLE001
                 c.lcs[i] = e
+        if c.strip is not None and c.rows[i][0]:
+            try:
+                fr = _np.ascontiguousarray(img, _np.float32)
+                with use_context(*fr.shape) as ctx:
+                    c.strips[i] = ("detect", c.strip.measure(ctx, fr, [(0, *c.strip.segs.detect_segment(c.rows[i][1], c.meas[i]))]))
+            except Exception as e:  # noqa: BLE001
+                c.strips[i] = e
         if c.radon is not None and not c.rows[i][0]:
             try:
                 c.rlines[i] = c.radon.one(img)
                 if 0 in c.radon.last_lc:
                     lc = c.radon.last_lc[0]
                     c.lcs[i] = lc if isinstance(lc, Exception) else ("radon", lc)
+                if 0 in c.radon.last_strip:
+                    st = c.radon.last_strip[0]
+                    c.strips[i] = st if isinstance(st, Exception) else ("radon", st)
             except Exception as e:  # noqa: BLE001
                 c.rlines[i] = e
     except Exception as e:  # noqa: BLE001 - the reference swallows everything per frame
@@ -724,6 +798,15 @@ def _run_group(c, idx, filter, shape, inflight, source, second, detect_kw=None, 
                 except Exception as e:  # noqa: BLE001
                     for j in found:
                         c.lcs[idx[j]] = e
+            if c.strip is not None:                   # the same frames, the same segments
+                found = [j for j, r in enumerate(recs) if not int(r["status"]) and int(r["found"])]
+                try:
+                    rows = [(j, *c.strip.segs.detect_segment(_detection(recs[j], shape)[1], c.meas[idx[j]])) for j in found]
+                    for j, item in zip(found, c.strip.measure(ctx, frames, rows, **measure_kw)):
+                        c.strips[idx[j]] = ("detect", [item])
+                except Exception as e:  # noqa: BLE001
+                    for j in found:
+                        c.strips[idx[j]] = e
             if c.radon is not None:                   # the frames without a detection, where the detect call left them
                 todo = [j for j, r in enumerate(recs) if not int(r["status"]) and not int(r["found"])]
                 try:
@@ -731,6 +814,8 @@ def _run_group(c, idx, filter, shape, inflight, source, second, detect_kw=None, 
                         c.rlines[idx[j]] = line
                     for j, lc in c.radon.last_lc.items():
                         c.lcs[idx[j]] = lc if isinstance(lc, Exception) else ("radon", lc)
+                    for j, st in c.radon.last_strip.items():
+                        c.strips[idx[j]] = st if isinstance(st, Exception) else ("radon", st)
                 except Exception as e:  # noqa: BLE001
                     for j in todo:
                         c.rlines[idx[j]] = e
@@ -785,6 +870,14 @@ def _emit(c, i, key, head, shape):
             _log_error(c.errors, key, c.lcs[i], c.debug)
         elif c.lcs[i][1]:
             c.lc.rows(key, *c.lcs[i])
+    if c.strip is not None and c.strips[i] is not None:   # (after the frame's light-curve rows)
+        if isinstance(c.strips[i], Exception):
+            _log_error(c.errors, key, c.strips[i], c.debug)
+        elif c.strips[i][1]:
+            try:
+                c.strip.rows(key, *c.strips[i])
+            except Exception as e:  # noqa: BLE001 - a map that cannot be written costs no other row
+                _log_error(c.errors, key, e, c.debug)
     if not detection or c.profiles is None:
         return
     try:                                              # (results.txt is written before, untouched)
@@ -797,7 +890,8 @@ def _emit(c, i, key, head, shape):
 
 
 def process_field(results, errors, run, camcol, filter, field, params_bright, params_dim,
-                  params_removestars, profiles=None, trail_params=None, sky=None, radon=None, stars=None, masks=None, lc=None):
+                  params_removestars, profiles=None, trail_params=None, sky=None, radon=None, stars=None, masks=None, lc=None,
+                  strip=None):
     """One frame end to end (reference: detecttrails.py:30-143): locate the frame (or its .bz2),
     read image + header + photoObj, detect, append ``run camcol filter field tai crpix1 crpix2
     crval1 crval2 cd11 cd12 cd21 cd22 x1 y1 x2 y2`` to ``results``; every exception is logged
@@ -808,7 +902,7 @@ def process_field(results, errors, run, camcol, filter, field, params_bright, pa
     ``_StarsStage``; the photoObj file is not opened, the catalogue is what the source finder finds in the frame (after the
     normalisation, if on), and the frame's stars.txt row is written.  ``masks``: a ``_MaskStage``; a results row, and every found
     faint line of ``radon`` with lines, gets its masks.txt row."""
-    c = _Chunk(1, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon, stars, masks, lc)
+    c = _Chunk(1, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon, stars, masks, lc, strip)
     head = None
     try:
         img, head, cat = _load_frame(run, camcol, filter, field, catalog=stars is None)
@@ -852,7 +946,7 @@ def process_fields_batched(results, errors, ids, params_bright, params_dim, para
 
 
 def process_loaded(results, errors, loaded, params_bright, params_dim, params_removestars, profiles=None, trail_params=None, sky=None,
-                   radon=None, stars=None, masks=None, lc=None):
+                   radon=None, stars=None, masks=None, lc=None, strip=None):
     """process_fields_batched for a chunk the loader has read (``loader.Loaded``): the frames that sit in pinned memory go to
     the GPU as contiguous same-filter slices of that memory with the matching rows of the padded catalogue arrays (no copy
     of a frame on the host, no per-frame Python), the others take the per-frame path; rows and errors entries come out in
@@ -867,7 +961,7 @@ def process_loaded(results, errors, loaded, params_bright, params_dim, params_re
     import time
     t_in = time.perf_counter()
     n = len(loaded.keys)
-    c = _Chunk(n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon, stars, masks, lc)
+    c = _Chunk(n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon, stars, masks, lc, strip)
     by_slot = {}
     for i in range(n):
         if loaded.error[i] is not None:
@@ -987,6 +1081,13 @@ class DetectTrails:
     source line status n_sec n_ok mean_rate mean_rate_err chi2 dof peak_section peak_rate length flux flux_err``.  The default
     ``clip`` (0.125) is the faint-trail units' star cut; a bright trail needs ``lc_params={"clip": ...}`` above its peak.  Rank files,
     resume and ``Jobs`` treat both like masks.txt; every other output stays byte for byte what it is.
+    ``trail_strips=True`` (default off): the same segments, at the same places, are straightened into maps of sections along the
+    trail by offsets across it (include/lfdmi.h: trail strips; ``strips_params``: dict of lfdmi_strip_params fields), each
+    half-width widened by ``wing`` so that the wings are sky.  ``strips_file`` (default ``<savepath>/strips.txt``) gets one row
+    per section that is not EMPTY: ``run camcol filter field source line section t0 t1 n_core n_wing bkg rate rate_err centre
+    width status``.  ``strips_dir``: each segment's maps are written there as ``strip-<run>-<camcol>-<filter>-<field>-<source>
+    <line>.npz`` (``mean``, ``n``, ``n_geom``, ``segment`` = x1 y1 x2 y2 half) with a ``.png`` preview beside it.  Rank files,
+    resume and ``Jobs`` treat strips.txt like lightcurves.txt; every other output stays byte for byte what it is.
     """
 
     _FILTERS = ('u', 'g', 'r', 'i', 'z')
@@ -1066,6 +1167,15 @@ class DetectTrails:
             from ..lightcurve import as_params as lc_as_params
             from ..masks import half_width
             lc_as_params(self.lc_params)                         # (unknown names and bad values raise here, not per frame)
+            half_width(1.0, **self.mask_params)
+        self.trail_strips = bool(kwargs.get("trail_strips", False))
+        self.strips_file = kwargs.get("strips_file", os.path.join(save, "strips.txt"))
+        self.strips_dir = kwargs.get("strips_dir")
+        self.strips_params = dict(kwargs.get("strips_params") or {})
+        if self.trail_strips:
+            from ..masks import half_width
+            from ..strips import as_params as strips_as_params
+            strips_as_params(self.strips_params)                 # (unknown names and bad values raise here, not per frame)
             half_width(1.0, **self.mask_params)
         if self.trail_profiles:
             _native.make_trail_params(**self.trail_params)      # (unknown names raise here, not per frame)
@@ -1233,7 +1343,8 @@ class DetectTrails:
                  else contextlib.nullcontext()) as rdef_out, \
                 (open(self.masks_file + suffix, "a") if self.trail_masks else contextlib.nullcontext()) as masks_out, \
                 (open(self.lightcurves_file + suffix, "a") if self.light_curves else contextlib.nullcontext()) as lc_out, \
-                (open(self.lightcurve_summary_file + suffix, "a") if self.light_curves else contextlib.nullcontext()) as lcsum_out:
+                (open(self.lightcurve_summary_file + suffix, "a") if self.light_curves else contextlib.nullcontext()) as lcsum_out, \
+                (open(self.strips_file + suffix, "a") if self.trail_strips else contextlib.nullcontext()) as strips_out:
             if self.trail_profiles:
                 profiles = _DefocusTee(profiles, defocus_out, self.defocus_params, self.trail_params)
             prof_kw = {"profiles": profiles, "trail_params": self.trail_params} if self.trail_profiles else {}
@@ -1248,12 +1359,16 @@ class DetectTrails:
             if self.light_curves:
                 sigma = _native.make_sky_params(**self.sky_params).target_sigma if self.normalize else 0.025
                 lc = prof_kw["lc"] = _LcStage(lc_out, lcsum_out, self.lc_params, sigma, self.mask_params)
+            strip = None
+            if self.trail_strips:
+                sigma = _native.make_sky_params(**self.sky_params).target_sigma if self.normalize else 0.025
+                strip = prof_kw["strip"] = _StripStage(strips_out, self.strips_params, sigma, self.mask_params, self.strips_dir)
             radon = None
             if self.radon:
                 sigma = _native.make_sky_params(**self.sky_params).target_sigma if self.normalize else 0.025
                 radon = prof_kw["radon"] = _RadonStage(radon_out, self.radon_params, sigma, self.radon_lines, self.radon_lines_params,
                                                        segments_out, rprof_out, self.stack_params, rdef_out, self.defocus_params,
-                                                       self.radon_short, short_out, lc, self.radon_wide, wide_out)
+                                                       self.radon_short, short_out, lc, self.radon_wide, wide_out, strip)
             masks = None
             if self.trail_masks:
                 masks = prof_kw["masks"] = _MaskStage(masks_out, self.mask_params, self.mask_dir)
@@ -1276,6 +1391,8 @@ class DetectTrails:
                     masks.flush()
                 if lc is not None:
                     lc.flush()
+                if strip is not None:
+                    strip.flush()
                 progress.write("".join("%s %s %s %s\n" % tuple(k) for k in done_keys))
                 progress.flush()
 
