@@ -983,6 +983,86 @@ int lfdmi_trail_strips(lfdmi_ctx *ctx, const void *frames, int dtype, int n, int
                        const lfdmi_strip_segment *segs, int n_seg, const float *sigma, const lfdmi_strip_params *p, lfdmi_strip *out,
                        lfdmi_strip_section *sections, int max_sections_per_seg, lfdmi_strip_cell *cells, int max_cells_per_seg);
 
+/* ---- trail subtraction ------------------------------------------------------------------------------------------------------
+ * lfdmi_subtract_trails gives back the sky under a trail: it makes a smooth, star-robust model of the trail's brightness from
+ * the segment's own strip (sections along the trail by offsets across it) and subtracts the model, interpolated at every pixel
+ * centre, from the frame.  lfdmi_mask_trails with a fill destroys every source the trail crosses; this leaves them standing.
+ * The reference has no such step.  The procedure below is the definition; tests/sub_ref.py restates it in numpy and the device
+ * equals it bit for bit: everything up to the model is exact integers, so nothing depends on the order in which the device
+ * works, and the only float arithmetic is the interpolation, a fixed sequence of float32 operations as in lfdmi_inject_trails
+ * step 3.  The device divides integers only.
+ *
+ * 1. Pixels and cells: steps 1 to 4 of the trail strips, unchanged (validity with clip and the mask plane, q = llrint(v * 2^30),
+ *    the geometry, the cell integers n_geom, n, q per (segment, j, b)); LFDMI_SUB_BAD_SEGMENT and LFDMI_SUB_TOO_LONG are decided
+ *    exactly as the strips decide theirs, with max_sections_per_seg and max_cells_per_seg.  The cells are taken from the frames as
+ *    the caller passed them, for every segment of the call, before any pixel is written.
+ * 2. Section background, int64.  Bin b is a wing bin iff fabs(u_b) >= half - wing (the strips' step 5; on the host).  N_j and Q_j
+ *    = the sums of n and of q over section j's wing bins.  The section is usable iff N_j >= min_wing; then B_j = Q_j / N_j (C
+ *    integer division, truncating toward zero).
+ * 3. Cell excess, for a usable section j and a core bin b with n_jb >= min_n: X_jb = q_jb / n_jb - B_j (truncating division).
+ *    Otherwise it is absent.
+ * 4. Model.  For every (j, core b): the present X_ib with i in [max(0, j - R), min(n_sec - 1, j + R)], R = smooth; c their
+ *    number.  c < min_sec: M_jb = 0.  Else sorted ascending x[0 .. c-1]: c odd, M_jb = x[(c-1)/2]; c even, M_jb = x[c/2-1] +
+ *    (x[c/2] - x[c/2-1]) / 2.  m_jb = (float)((double)M_jb * 2^-30): the conversion and the product are exact, the narrowing is
+ *    correctly rounded.  A wing bin has m = 0, so the model tapers to zero at the first wing bin.  A section that is itself not
+ *    usable (a star above clip in its wings, say) still gets a model from its neighbours: that is the point of the median.
+ * 5. Value at the pixel centre (x, y): u and t as step 3 of the trail masks.  The pixel takes part iff t >= 0 && t <= L &&
+ *    fabs(u) <= half and its value as passed is finite and not +-0 (a blotted pixel stays blotted; clip and the mask plane play
+ *    no part here: the trail's light under a star is removed too).  In double:
+ *        a = t * inv_s - 0.5;   g = u * inv_u + (double)K;
+ *        j0 = clamp((int)floor(a), 0, n_sec-1);  j1 = min(j0+1, n_sec-1);  ft = (float)min(max(a - j0, 0.0), 1.0);
+ *        b0 = clamp((int)floor(g), 0, 2K);       b1 = min(b0+1, 2K);       fb = (float)min(max(g - b0, 0.0), 1.0);
+ *    in float32, each operation rounded, no FMA:
+ *        v0 = m[j0][b0] + fb * (m[j0][b1] - m[j0][b0]);   v1 = m[j1][b0] + fb * (m[j1][b1] - m[j1][b0]);   v = v0 + ft * (v1 - v0).
+ *    v != 0: pixel = pixel - v (one float32 subtraction), n_pix += 1, q_removed += llrint((double)v * 2^30).  v == 0: the pixel
+ *    is not written.
+ * 6. Several segments of a frame: all models come from the frames as passed (step 1); a pixel's subtractions are applied in
+ *    ascending segment index, so crossings are defined bit for bit.  A thread owns its pixels; the image sees no atomic.
+ * 7. Record.  status LFDMI_SUB_OK, LFDMI_SUB_BAD_SEGMENT, LFDMI_SUB_TOO_LONG, or LFDMI_SUB_EMPTY when no cell has a model
+ *    (n_model == 0).  n_sec, n_off, K; n_usable = the usable sections; n_model = the core cells with c >= min_sec; n_pix = the
+ *    pixels written (apply == 0: that would be); peak_section = the section of the largest m over those cells (ties: the lowest
+ *    j, then the lowest b), -1 when n_model == 0; q_removed (int64); removed = (double)q_removed * 2^-30; peak = that largest m as
+ *    a double, NaN when n_model == 0.  A BAD_SEGMENT or TOO_LONG segment changes no pixel; its integers are zero, its doubles NaN.
+ * 8. model (may be NULL): n_seg x max_cells_per_seg float32 (host), m_jb at j * n_off + b; everything past n_sec * n_off, and
+ *    every row of a segment that is not measured, is zero.
+ *
+ * The device makes the cells with the strips' kernels and keeps them: only the segments and the records cross the bus.
+ * k_sub_model makes each segment's table (a block per run of 16 sections, its halo of R rows in LDS, the at most 17 values of a
+ * median in registers); k_sub_render walks the tiles the strips' cull listed, segments through LDS in ascending index, four
+ * pixels of a row per thread, the four table reads of a pixel through L2, n_pix and q_removed as one integer atomic per wave and
+ * segment.  Host frames go through the device in chunks of frames: a chunk is measured, modelled and rendered while staged once. */
+#define LFDMI_SUB_MAX_SMOOTH 8         /* largest smooth */
+enum { LFDMI_SUB_OK = 0, LFDMI_SUB_BAD_SEGMENT = 1, LFDMI_SUB_TOO_LONG = 2, LFDMI_SUB_EMPTY = 3 };
+typedef struct {
+    double sec_len;           /* section length in px (4 .. 4096); default 32 */
+    double step;              /* offset bin in px (0.5 .. 8); default 1 */
+    double wing;              /* the bins with |u_b| >= half - wing are sky (> 0, finite); default 6 */
+    float clip;               /* a pixel above clip in magnitude is invalid (finite, 0 < clip <= 1024); default 0.125 */
+    int32_t smooth;           /* R, the running median's half-window in sections (0 .. LFDMI_SUB_MAX_SMOOTH); default 2 */
+    int32_t min_sec;          /* present values a model cell needs (1 .. 2 R + 1); default 3 */
+    int32_t min_n;            /* valid pixels a cell needs (>= 1); default 8 */
+    int32_t min_wing;         /* valid wing pixels a section needs (>= 1); default 8 */
+    int32_t apply;            /* 0: the model and the counts, no pixel is written; 1: subtract; default 1 */
+} lfdmi_sub_params;
+typedef struct {
+    int32_t status;           /* LFDMI_SUB_* */
+    int32_t n_sec, n_off, K, n_usable, n_model, n_pix, peak_section;
+    int64_t q_removed;
+    double removed, peak;
+} lfdmi_sub;
+void lfdmi_default_sub_params(lfdmi_sub_params *out);
+/* frames: n frames of h x w at loc.  apply == 1: LFDMI_F32 only; LFDMI_DEVICE frames are changed in place; of LFDMI_HOST /
+ * LFDMI_HOST_PINNED frames those that carry a good segment are uploaded, changed and copied back, the others are neither copied
+ * nor written.  apply == 0: LFDMI_F32 or LFDMI_F32_BE, nothing is written.  mask, skip_bits, segs (lfdmi_strip_segment records),
+ * sigma: as lfdmi_trail_strips takes them; sigma is validated and not used.  p NULL: the defaults.  out: n_seg records; model:
+ * NULL or n_seg x max_cells_per_seg float32 (host).  LFDMI_ERR_ARG, and no pixel and no output is touched: what
+ * lfdmi_trail_strips refuses, LFDMI_F32_BE with apply == 1, parameters out of range (min_sec > 2 smooth + 1 among them).  The
+ * call keeps no state (its device memory comes from the stream's pool and goes back before it returns), refuses while calls are
+ * in flight, runs on the context's stream and waits for it once. */
+int lfdmi_subtract_trails(lfdmi_ctx *ctx, void *frames, int dtype, int n, int h, int w, int loc, const uint8_t *mask, int skip_bits,
+                          const lfdmi_strip_segment *segs, int n_seg, const float *sigma, const lfdmi_sub_params *p, lfdmi_sub *out,
+                          float *model, int max_sections_per_seg, int max_cells_per_seg);
+
 /* ---- faint-trail search -----------------------------------------------------------------------------------------------------
  * The detector finds a trail whose pixels survive the 8-bit conversion; lfdmi_radon_search finds one that is faint in every
  * pixel but long: it sums the frame along every line of a dyadic family (the fast Radon transform of Goetz and Druckmueller /

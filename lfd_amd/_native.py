@@ -43,6 +43,7 @@ SYMBOLS = (
     "lfdmi_default_mask_params", "lfdmi_mask_trails",
     "lfdmi_default_lc_params", "lfdmi_light_curves",
     "lfdmi_default_strip_params", "lfdmi_trail_strips",
+    "lfdmi_default_sub_params", "lfdmi_subtract_trails",
     "lfdmi_default_radon_params", "lfdmi_radon_create", "lfdmi_radon_destroy", "lfdmi_radon_dims", "lfdmi_radon_search",
     "lfdmi_default_radon_lines_params", "lfdmi_radon_search_lines",
     "lfdmi_default_radon_short_params", "lfdmi_radon_search_short",
@@ -300,6 +301,25 @@ def strip_cells_needed(segs, p, max_sections):
     return most
 
 
+class SubParamsStruct(C.Structure):
+    """lfdmi_sub_params (include/lfdmi.h: trail subtraction)."""
+    _fields_ = [("sec_len", C.c_double), ("step", C.c_double), ("wing", C.c_double), ("clip", C.c_float), ("smooth", C.c_int32),
+                ("min_sec", C.c_int32), ("min_n", C.c_int32), ("min_wing", C.c_int32), ("apply", C.c_int32)]
+
+
+SUB_PARAMS = SubParamsStruct
+# lfdmi_sub: one record per segment of lfdmi_subtract_trails (its segments are lfdmi_strip_segment records)
+SUB_DTYPE = np.dtype([("status", "<i4"), ("n_sec", "<i4"), ("n_off", "<i4"), ("K", "<i4"), ("n_usable", "<i4"), ("n_model", "<i4"),
+                      ("n_pix", "<i4"), ("peak_section", "<i4"), ("q_removed", "<i8"), ("removed", "<f8"), ("peak", "<f8")])
+SUB_OK, SUB_BAD_SEGMENT, SUB_TOO_LONG, SUB_EMPTY = 0, 1, 2, 3
+SUB_MAX_SMOOTH = 8
+
+
+def make_sub_params(**params):
+    """lfdmi_default_sub_params with the given fields replaced (unknown names raise)."""
+    return _make_params(SubParamsStruct, "lfdmi_default_sub_params", "subtraction", params)
+
+
 class RadonParamsStruct(C.Structure):
     """lfdmi_radon_params (include/lfdmi.h: faint-trail search)."""
     _fields_ = [("bin", C.c_int32), ("min_len", C.c_int32), ("clip", C.c_float), ("threshold", C.c_float)]
@@ -504,6 +524,10 @@ def lib():
         _lib.lfdmi_default_strip_params.argtypes = [C.c_void_p]
         _lib.lfdmi_trail_strips.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                             C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        _lib.lfdmi_default_sub_params.restype = None
+        _lib.lfdmi_default_sub_params.argtypes = [C.c_void_p]
+        _lib.lfdmi_subtract_trails.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                               C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         _lib.lfdmi_default_radon_params.restype = None
         _lib.lfdmi_default_radon_params.argtypes = [C.c_void_p]
         _lib.lfdmi_radon_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
@@ -1366,6 +1390,48 @@ class Context:
         self._chk(self._lib.lfdmi_trail_strips(self._h, _ptr(frames), code, n, h, w, loc, _ptr(mask), int(skip_bits), _ptr(sg), len(sg),
                                                _ptr(sig), C.byref(p), _ptr(out), _ptr(sec), m, _ptr(cells), mc))
         return out, sec, cells
+
+    # -- trail subtraction (lfdmi_subtract_trails) --------------------------------------------------------------------------------
+    def subtract_trails(self, frames, segs, mask=None, skip_bits=0, max_sections=256, max_cells=None, want_model=False, pinned=False,
+                        native_device=False, **params):
+        """Model every segment's trail from its own strip and subtract it from ``frames`` in place (include/lfdmi.h: trail
+        subtraction).  frames: as ``inject_trails`` takes them (a torch CUDA tensor is changed where it is; of a numpy array the
+        frames that carry a good segment are uploaded, changed and copied back); with ``apply=0`` nothing is written and what
+        ``trail_strips`` takes is accepted, big-endian frames too.  segs: STRIP_SEGMENT_DTYPE records; mask, skip_bits,
+        max_sections, max_cells: as ``trail_strips``; params: fields of lfdmi_sub_params.  Returns (SUB_DTYPE records [n_seg],
+        and with ``want_model`` the float32 tables [n_seg, max_cells], cell (j, b) of segment i at [i, j * n_off + b], else None)."""
+        p = make_sub_params(**params)
+        if p.apply and not isinstance(frames, DeviceFrames) and not _is_dev(frames) and not (
+                isinstance(frames, np.ndarray) and frames.flags.c_contiguous and frames.flags.writeable):
+            raise ValueError("subtract_trails needs a writable C-contiguous array (it is modified in place)")
+        frames, code, n, h, w, loc = self._frames(frames, pinned, "subtract_trails", native_device=native_device)
+        sg = np.ascontiguousarray(segs, STRIP_SEGMENT_DTYPE).reshape(-1)
+        m = int(max_sections)
+        if not 1 <= m <= STRIP_MAX_SECTIONS:
+            raise ValueError(f"max_sections: 1 .. {STRIP_MAX_SECTIONS}")
+        if max_cells is None:
+            max_cells = strip_cells_needed(sg, p, m)
+        mc = int(max_cells)
+        if not 1 <= mc <= STRIP_MAX_SECTIONS * STRIP_MAX_OFF:
+            raise ValueError(f"max_cells: 1 .. {STRIP_MAX_SECTIONS * STRIP_MAX_OFF}")
+        if mask is not None:
+            shp = tuple(mask.shape)
+            if shp != (n, h, w) and not (n == 1 and shp == (h, w)):      # (one frame may come with a 2-d plane)
+                raise ValueError(f"mask of shape {shp} for frames of shape {(n, h, w)}")
+            if str(mask.dtype).replace("torch.", "") != "uint8":
+                raise TypeError("subtract_trails needs a uint8 mask")
+            if _is_dev(mask) != (loc == DEVICE):
+                raise ValueError("subtract_trails needs the mask where the frames are")
+            if _is_dev(mask):
+                if not mask.is_contiguous():
+                    raise ValueError("device tensors must be contiguous")
+            else:
+                mask = np.ascontiguousarray(mask)
+        out = np.zeros(len(sg), SUB_DTYPE)
+        model = np.zeros((len(sg), mc), np.float32) if want_model else None
+        self._chk(self._lib.lfdmi_subtract_trails(self._h, _ptr(frames), code, n, h, w, loc, _ptr(mask), int(skip_bits), _ptr(sg), len(sg),
+                                                  None, C.byref(p), _ptr(out), _ptr(model), m, mc))
+        return out, model
 
     # -- stacked cross-sections (lfdmi_stack_profiles) ----------------------------------------------------------------------------
     def stack_profiles(self, frames, segments, sigma=None, pinned=False, native_device=False, raw=False, **params):

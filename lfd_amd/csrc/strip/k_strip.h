@@ -94,9 +94,10 @@ __device__ __forceinline__ void strip_tile_box(const StripDev &p, int tile, int 
     r0 = ty * STRIP_TILE_H; r1 = min(r0 + STRIP_TILE_H, p.h) - 1;
 }
 
+// (both kernels have internal linkage: the trail subtraction, sub/, includes this header and launches its own copies)
 // one thread per (job, tile): the pair is listed when any of the job's segments reaches the tile; the list's order is the order
 // of arrival and no result depends on it
-__global__ void __launch_bounds__(STRIP_THREADS) k_strip_cull(const StripJob *jobs, int njobs, const StripSeg *segs, StripDev p, int2 *list,
+static __global__ void __launch_bounds__(STRIP_THREADS) k_strip_cull(const StripJob *jobs, int njobs, const StripSeg *segs, StripDev p, int2 *list,
                                                                int *count) {
     const int64_t g = (int64_t)blockIdx.x * STRIP_THREADS + threadIdx.x;
     const int ntiles = p.ntx * p.nty;
@@ -142,7 +143,7 @@ __device__ __forceinline__ void strip_add(uint32_t *T_c, unsigned long long *T_q
 // sec_len px long), so the ballot loop would run nearly once per lane and cost more than the atomics it saves; only the merge
 // that costs nothing is kept, the thread's own.  After a barrier the window's non-zero entries go to memory with one atomicAdd
 // per count and per q.  The loops that hold a barrier are uniform over the block.
-__global__ void __launch_bounds__(STRIP_THREADS) k_strip_render(const uint32_t *frames, const uint8_t *mask, const StripJob *jobs,
+static __global__ void __launch_bounds__(STRIP_THREADS) k_strip_render(const uint32_t *frames, const uint8_t *mask, const StripJob *jobs,
                                                                  const StripSeg *segs, StripDev p, const int2 *list, const int *count,
                                                                  StripCell *cells) {
     __shared__ StripSeg S[STRIP_CHUNK];

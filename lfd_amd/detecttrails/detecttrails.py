@@ -13,6 +13,7 @@ Deliberate fixes of reference bugs: C8 ``params_dim=`` /
 carries the 13 header values instead of literal ``{h['CRPIX2']}`` text.
 """
 import bz2
+import contextlib
 import os
 import traceback
 
@@ -625,6 +626,83 @@ class _StripStage:
         self.out.flush()
 
 
+@contextlib.contextmanager
+def _both(a, b):
+    """two context managers as one (``process`` is at Python's limit of nested blocks)"""
+    with a as x, b as y:
+        yield x, y
+
+
+class _DevView:
+    """device frames as something ``torch.as_tensor`` can look at without a copy"""
+
+    def __init__(self, ptr, shape):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<f4", "data": (int(ptr), False), "version": 2}
+
+
+class _SubStage:
+    """The trail subtraction for ``DetectTrails(subtract_trails=True)`` (include/lfdmi.h: trail subtraction): the segments
+    ``_LcStage`` and ``_StripStage`` measure, each half-width widened by ``wing``, modelled and taken out of the chunk's frames
+    after every other measurement, because it changes them.  Frames on the device change where they are; the loader's pinned
+    big-endian slots are left alone and the frames that carry a segment are cleaned as native copies.  The chunk's slot keeps
+    (source, [(record, segment)], the cleaned frame if ``clean_dir``) until ``_emit`` writes one subtracted.txt row per segment
+    and, with ``clean_dir``, the frame as clean-<run>-<camcol>-<filter>-<field>.npz."""
+
+    def __init__(self, out, params, half_params=None, clean_dir=None, max_sections=1024):
+        from ..subtract import DEFAULT_WING, as_params
+        self.out, self.params, self.clean_dir = out, as_params(params), clean_dir
+        if not int(self.params.get("apply", 1)):
+            raise ValueError("sub_params: apply=0 subtracts nothing; leave subtract_trails off instead")
+        self.wing = float(self.params.get("wing", DEFAULT_WING))
+        self.max_sections = int(max_sections)             # (a results row reaches about 1000 px past the frame)
+        self.segs = _MaskStage(None, half_params)
+        if clean_dir is not None:
+            os.makedirs(clean_dir, exist_ok=True)
+
+    def run(self, ctx, frames, per_frame, **where):
+        """per_frame: {frame index j: (source, [(x1, y1, x2, y2, half)])} on ``frames`` -> {j: (source, [(record, segment)],
+        cleaned frame or None)}"""
+        from .. import _native, subtract
+        js = sorted(j for j in per_frame if per_frame[j][1])
+        if not js:
+            return {}
+        host_be = isinstance(frames, _np.ndarray) and frames.dtype != _np.float32
+        if host_be:                                       # native copies of the frames that carry a segment
+            work, at, where = _np.ascontiguousarray(frames[js], _np.float32), {j: k for k, j in enumerate(js)}, {}
+        else:
+            work, at = frames, {j: j for j in js}
+        rows = [(at[j], *seg[:4], float(seg[4]) + self.wing) for j in js for seg in per_frame[j][1]]
+        segs = subtract.segments(rows)
+        rec, _ = ctx.subtract_trails(work, segs, max_sections=self.max_sections, **where, **self.params)
+        out, k = {}, 0
+        for j in js:
+            n = len(per_frame[j][1])
+            clean = None
+            if self.clean_dir is not None:
+                if isinstance(work, _np.ndarray):
+                    clean = _np.array(work[at[j]], _np.float32)
+                elif isinstance(work, _native.DeviceFrames):
+                    import torch
+                    view = torch.as_tensor(_DevView(work.address_of(j), work.shape[1:]), device="cuda")
+                    clean = view.cpu().numpy()
+                else:
+                    clean = work[j].cpu().numpy()
+            out[j] = (per_frame[j][0], [(rec[k + m], segs[k + m]) for m in range(n)], clean)
+            k += n
+        return out
+
+    def rows(self, key, source, items, clean):
+        from .. import subtract
+        for k, (rec, seg) in enumerate(items):
+            self.out.write("\n".join(subtract.format_rows(key, source, k, rec)) + "\n")
+        if self.clean_dir is not None and clean is not None:
+            _np.savez(os.path.join(self.clean_dir, "clean-%s-%s-%s-%s.npz" % tuple(key)), frame=clean,
+                      segments=_np.array([[float(seg[f]) for f in ("x1", "y1", "x2", "y2", "half")] for _, seg in items]))
+
+    def flush(self):
+        self.out.flush()
+
+
 def _load_frame(run, camcol, filter, field, catalog=True):
     """Frame image (float32, C-contiguous), results-row head, photoObj columns; raises like the
     reference when neither the .fits nor the .fits.bz2 exists (detecttrails.py:81-87)."""
@@ -694,8 +772,10 @@ class _Chunk:
     per-frame product gets a slot here, a step in ``_run_group`` and ``_run_frame``, and its row in ``_emit``."""
 
     def __init__(self, n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon=None,
-                 stars=None, masks=None, lc=None, strip=None):
+                 stars=None, masks=None, lc=None, strip=None, sub=None):
         self.results, self.errors, self.profiles, self.sky, self.radon, self.stars = results, errors, profiles, sky, radon, stars
+        self.sub = sub                                # a ``_SubStage``; ``subs[i]``: (source, [(record, segment)], frame) or the exception
+        self.subs = [None] * n
         self.masks = masks                            # a ``_MaskStage``: its rows are made in ``_emit``, from the slots below
         self.lc = lc                                  # a ``_LcStage``; ``lcs[i]``: (source, [(record, sections)]) or the exception
         self.lcs = [None] * n
@@ -710,10 +790,20 @@ class _Chunk:
         self.gpu_s = 0.0                              # inside the sky + detect calls of the groups that went through
 
 
+def _sub_segments(c, i, detection, res, line):
+    """frame i's segments for the subtraction: (source, [(x1, y1, x2, y2, half)]), the trail masks' of its results row or of its
+    found faint lines"""
+    if detection:
+        return "detect", [c.sub.segs.detect_segment(res, c.meas[i])]
+    if line is not None and not isinstance(line, Exception):
+        return "radon", list(c.sub.segs.radon_segments(line))
+    return "detect", []
+
+
 def _run_frame(c, i, filter, frame):
     """Frame i on its own, under its own try: ``frame()`` -> (float32 img, cat); sky normalisation if on, detection, and the
     trail measurement of a detected frame."""
-    c.lcs[i] = c.strips[i] = None
+    c.lcs[i] = c.strips[i] = c.subs[i] = None
     try:
         img, cat = frame()
         c.shapes[i] = tuple(img.shape)
@@ -752,6 +842,15 @@ def _run_frame(c, i, filter, frame):
                     c.strips[i] = st if isinstance(st, Exception) else ("radon", st)
             except Exception as e:  # noqa: BLE001
                 c.rlines[i] = e
+        if c.sub is not None:                         # last: it changes the frame (a copy of it here)
+            try:
+                todo = _sub_segments(c, i, c.rows[i][0], c.rows[i][1], c.rlines[i])
+                if todo[1]:
+                    fr = _np.array(img, _np.float32, order="C")
+                    with use_context(*fr.shape) as ctx:
+                        c.subs[i] = c.sub.run(ctx, fr[None], {0: todo}).get(0)
+            except Exception as e:  # noqa: BLE001
+                c.subs[i] = e
     except Exception as e:  # noqa: BLE001 - the reference swallows everything per frame
         c.rows[i] = e
 
@@ -819,6 +918,20 @@ def _run_group(c, idx, filter, shape, inflight, source, second, detect_kw=None, 
                 except Exception as e:  # noqa: BLE001
                     for j in todo:
                         c.rlines[idx[j]] = e
+            if c.sub is not None:                     # after every other measurement of the chunk: it changes the frames
+                per_frame = {}
+                try:
+                    for j, r in enumerate(recs):
+                        if int(r["status"]):
+                            continue
+                        found = int(r["found"])
+                        per_frame[j] = _sub_segments(c, idx[j], found, _detection(r, shape)[1] if found else None, c.rlines[idx[j]])
+                    for j, item in c.sub.run(ctx, frames, per_frame, **measure_kw).items():
+                        c.subs[idx[j]] = item
+                except Exception as e:  # noqa: BLE001
+                    for j, (_, segs) in per_frame.items():
+                        if segs:
+                            c.subs[idx[j]] = e
         for i, rec in zip(idx, recs):
             c.rows[i] = rec
     except Exception as e:  # noqa: BLE001
@@ -878,6 +991,14 @@ def _emit(c, i, key, head, shape):
                 c.strip.rows(key, *c.strips[i])
             except Exception as e:  # noqa: BLE001 - a map that cannot be written costs no other row
                 _log_error(c.errors, key, e, c.debug)
+    if c.sub is not None and c.subs[i] is not None:   # (after the frame's strips rows)
+        if isinstance(c.subs[i], Exception):
+            _log_error(c.errors, key, c.subs[i], c.debug)
+        else:
+            try:
+                c.sub.rows(key, *c.subs[i])
+            except Exception as e:  # noqa: BLE001 - a frame that cannot be written costs no other row
+                _log_error(c.errors, key, e, c.debug)
     if not detection or c.profiles is None:
         return
     try:                                              # (results.txt is written before, untouched)
@@ -891,7 +1012,7 @@ def _emit(c, i, key, head, shape):
 
 def process_field(results, errors, run, camcol, filter, field, params_bright, params_dim,
                   params_removestars, profiles=None, trail_params=None, sky=None, radon=None, stars=None, masks=None, lc=None,
-                  strip=None):
+                  strip=None, sub=None):
     """One frame end to end (reference: detecttrails.py:30-143): locate the frame (or its .bz2),
     read image + header + photoObj, detect, append ``run camcol filter field tai crpix1 crpix2
     crval1 crval2 cd11 cd12 cd21 cd22 x1 y1 x2 y2`` to ``results``; every exception is logged
@@ -902,7 +1023,7 @@ def process_field(results, errors, run, camcol, filter, field, params_bright, pa
     ``_StarsStage``; the photoObj file is not opened, the catalogue is what the source finder finds in the frame (after the
     normalisation, if on), and the frame's stars.txt row is written.  ``masks``: a ``_MaskStage``; a results row, and every found
     faint line of ``radon`` with lines, gets its masks.txt row."""
-    c = _Chunk(1, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon, stars, masks, lc, strip)
+    c = _Chunk(1, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon, stars, masks, lc, strip, sub)
     head = None
     try:
         img, head, cat = _load_frame(run, camcol, filter, field, catalog=stars is None)
@@ -946,7 +1067,7 @@ def process_fields_batched(results, errors, ids, params_bright, params_dim, para
 
 
 def process_loaded(results, errors, loaded, params_bright, params_dim, params_removestars, profiles=None, trail_params=None, sky=None,
-                   radon=None, stars=None, masks=None, lc=None, strip=None):
+                   radon=None, stars=None, masks=None, lc=None, strip=None, sub=None):
     """process_fields_batched for a chunk the loader has read (``loader.Loaded``): the frames that sit in pinned memory go to
     the GPU as contiguous same-filter slices of that memory with the matching rows of the padded catalogue arrays (no copy
     of a frame on the host, no per-frame Python), the others take the per-frame path; rows and errors entries come out in
@@ -961,7 +1082,7 @@ def process_loaded(results, errors, loaded, params_bright, params_dim, params_re
     import time
     t_in = time.perf_counter()
     n = len(loaded.keys)
-    c = _Chunk(n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon, stars, masks, lc, strip)
+    c = _Chunk(n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon, stars, masks, lc, strip, sub)
     by_slot = {}
     for i in range(n):
         if loaded.error[i] is not None:
@@ -1088,6 +1209,13 @@ class DetectTrails:
     width status``.  ``strips_dir``: each segment's maps are written there as ``strip-<run>-<camcol>-<filter>-<field>-<source>
     <line>.npz`` (``mean``, ``n``, ``n_geom``, ``segment`` = x1 y1 x2 y2 half) with a ``.png`` preview beside it.  Rank files,
     resume and ``Jobs`` treat strips.txt like lightcurves.txt; every other output stays byte for byte what it is.
+    ``subtract_trails=True`` (default off): the same segments, each half-width widened by ``wing``, are modelled from their own
+    strips and taken out of the frames (include/lfdmi.h: trail subtraction; ``sub_params``: dict of lfdmi_sub_params fields),
+    after every other measurement of the chunk, because it changes the frames, and while they are still on the device.
+    ``subtracted_file`` (default ``<savepath>/subtracted.txt``) gets one row per segment: ``run camcol filter field source line
+    status n_sec n_usable n_model n_pix removed peak peak_section``.  ``clean_dir``: each changed frame is written there as
+    ``clean-<run>-<camcol>-<filter>-<field>.npz`` (float32 ``frame`` in buffer order, and its ``segments``).  Rank files, resume
+    and ``Jobs`` treat subtracted.txt like strips.txt; every other output stays byte for byte what it is.
     """
 
     _FILTERS = ('u', 'g', 'r', 'i', 'z')
@@ -1176,6 +1304,14 @@ class DetectTrails:
             from ..masks import half_width
             from ..strips import as_params as strips_as_params
             strips_as_params(self.strips_params)                 # (unknown names and bad values raise here, not per frame)
+            half_width(1.0, **self.mask_params)
+        self.subtract_trails = bool(kwargs.get("subtract_trails", False))
+        self.subtracted_file = kwargs.get("subtracted_file", os.path.join(save, "subtracted.txt"))
+        self.clean_dir = kwargs.get("clean_dir")
+        self.sub_params = dict(kwargs.get("sub_params") or {})
+        if self.subtract_trails:
+            from ..masks import half_width
+            _SubStage(None, self.sub_params)                     # (unknown names and bad values raise here, not per frame)
             half_width(1.0, **self.mask_params)
         if self.trail_profiles:
             _native.make_trail_params(**self.trail_params)      # (unknown names raise here, not per frame)
@@ -1344,7 +1480,8 @@ class DetectTrails:
                 (open(self.masks_file + suffix, "a") if self.trail_masks else contextlib.nullcontext()) as masks_out, \
                 (open(self.lightcurves_file + suffix, "a") if self.light_curves else contextlib.nullcontext()) as lc_out, \
                 (open(self.lightcurve_summary_file + suffix, "a") if self.light_curves else contextlib.nullcontext()) as lcsum_out, \
-                (open(self.strips_file + suffix, "a") if self.trail_strips else contextlib.nullcontext()) as strips_out:
+                _both(open(self.strips_file + suffix, "a") if self.trail_strips else contextlib.nullcontext(),
+                      open(self.subtracted_file + suffix, "a") if self.subtract_trails else contextlib.nullcontext()) as (strips_out, sub_out):
             if self.trail_profiles:
                 profiles = _DefocusTee(profiles, defocus_out, self.defocus_params, self.trail_params)
             prof_kw = {"profiles": profiles, "trail_params": self.trail_params} if self.trail_profiles else {}
@@ -1372,6 +1509,9 @@ class DetectTrails:
             masks = None
             if self.trail_masks:
                 masks = prof_kw["masks"] = _MaskStage(masks_out, self.mask_params, self.mask_dir)
+            sub = None
+            if self.subtract_trails:
+                sub = prof_kw["sub"] = _SubStage(sub_out, self.sub_params, self.mask_params, self.clean_dir)
             if fresh:
                 progress.write(header + "\n")
                 progress.flush()
@@ -1393,6 +1533,8 @@ class DetectTrails:
                     lc.flush()
                 if strip is not None:
                     strip.flush()
+                if sub is not None:
+                    sub.flush()
                 progress.write("".join("%s %s %s %s\n" % tuple(k) for k in done_keys))
                 progress.flush()
 

@@ -83,7 +83,7 @@ class Jobs:
         joined = [results, errors] + ([probe.profiles] if probe.trail_profiles else []) + ([probe.defocus_file] if probe.defocus else []) + \
             ([probe.sky_file] if probe.normalize else []) + ([probe.stars_file] if probe.find_stars else []) + ([probe.masks_file] if probe.trail_masks else []) + \
             ([probe.lightcurves_file, probe.lightcurve_summary_file] if probe.light_curves else []) + \
-            ([probe.strips_file] if probe.trail_strips else [])
+            ([probe.strips_file] if probe.trail_strips else []) + ([probe.subtracted_file] if probe.subtract_trails else [])
         if not resume:
             for path in joined:                           # the joined files are rewritten by this launch
                 if self.n > 1 and os.path.exists(path):
