@@ -1300,6 +1300,47 @@ int lfdmi_radon_search_wide(lfdmi_ctx *ctx, lfdmi_radon *radon, const void *fram
                             const lfdmi_radon_wide_params *wp, lfdmi_radon_wide *lines, int32_t *n_lines,
                             lfdmi_radon_result *plain);
 
+/* null peaks: the frame's own noise ceiling.  The thresholds above rest on crops of pure Gaussian noise (steps 5, 12, 14); a
+ * real frame has many more lines, what remove_stars left behind, and a sigma that is an estimate.  lfdmi_radon_null measures
+ * what the very same search reaches on the frame once every line in it is destroyed: the frame is scrambled -- every pixel
+ * takes the exact bits of a pixel drawn from the frame itself, so the value distribution, the share of invalid pixels and
+ * sigma stay and no geometry does -- and searched, K times.  Nothing below is new arithmetic: tests/radon_null_ref.py builds
+ * the scrambled frame with numpy integers and calls the restatements of the searches, and the device matches bit for bit.
+ * 17. Key.  For frame f with the caller's seed[f] (uint64; without seeds, seed[f] = f) and realisation r = 0 .. K-1:
+ *        k = splitmix64(seed[f] + 0x9E3779B97F4A7C15 * (r + 1)),
+ *        splitmix64(x): x += 0x9E3779B97F4A7C15;  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9;
+ *                       x = (x ^ (x >> 27)) * 0x94D049BB133111EB;  return x ^ (x >> 31)
+ *    all modulo 2^64, on the host.
+ * 18. Source pixel.  N = H W (below 2^32 for every shape a handle takes).  For buffer index i = row * W + column (row: the
+ *    buffer's, before step 1's flip), in uint32 arithmetic modulo 2^32 but for the last product:
+ *        a = fmix32(i * 0x9E3779B1 + lo32(k));  u = fmix32(a ^ hi32(k));  j = (uint32)(((uint64)u * N) >> 32)
+ *        fmix32(h): h ^= h >> 16;  h *= 0x85EBCA6B;  h ^= h >> 13;  h *= 0xC2B2AE35;  h ^= h >> 16     (murmur3's finaliser)
+ *    j < N always.
+ * 19. Scrambled frame.  X'[i] = X[j] as a 32-bit pattern (of a big-endian frame: the stored pattern, which step 1 then swaps
+ *    as it does for X).  This is sampling with replacement, not a permutation: every value, valid or not, arrives with its
+ *    exact bits.  X' is never stored: step 2's cells read their b x b pixels through j.
+ * 20. Null record (f, r) of a kind is record 0 of that kind's search of X' with the frame's sigma[f]: LFDMI_RADON_NULL_LINES,
+ *    steps 1 - 6, an lfdmi_radon_result; LFDMI_RADON_NULL_SHORT, steps 10 - 12 with max_lines = 1, an lfdmi_radon_short;
+ *    LFDMI_RADON_NULL_WIDE, steps 13 - 16 with max_lines = 1, an lfdmi_radon_wide.  No peel round runs; a short or wide
+ *    record with found = 1 has its segment (steps 12, 16), which at the default thresholds a null record should never be.
+ *    With the null peaks snr_0 .. snr_K-1 of a frame, a line of that frame with score x has the false-alarm estimate
+ *    (1 + #{snr_r >= x}) / (K + 1), which is never 0, and margin * max snr_r is the rule the default thresholds follow.
+ *    Not covered: a null that keeps the noise's spatial correlation, sign-flip or row-shift nulls, nulls of peel rounds after
+ *    the first; no default threshold changes on these numbers. */
+enum { LFDMI_RADON_NULL_LINES = 0, LFDMI_RADON_NULL_SHORT = 1, LFDMI_RADON_NULL_WIDE = 2 };
+#define LFDMI_RADON_NULL_MAX 64
+/* The null records of n frames: frames, dtype, n, loc and sigma as in lfdmi_radon_search.  seeds: n uint64 (host); NULL: frame
+ * f has seed f.  K: realisations per frame, 1 .. LFDMI_RADON_NULL_MAX.  kind: LFDMI_RADON_NULL_*.  kind_params: an
+ * lfdmi_radon_short_params (SHORT) or lfdmi_radon_wide_params (WIDE), checked as their searches check them (max_lines and
+ * peel_halfwidth are checked and not used); NULL: the defaults; LINES takes none (it must be NULL).  records: n * K records of
+ * the kind's type (host), frame f's at records[f * K ..].  Realisation r of frame f takes one of the handle's max_frames slots,
+ * so n * K > max_frames runs in chunks of max_frames realisations (a frame's realisations may lie in two chunks).  The first
+ * call of a kind allocates what that kind's search does; lfdmi_radon_dims counts it.  The frames are only read; the call
+ * refuses (LFDMI_ERR_ARG) while calls are in flight, on a sigma that is not positive, on K or kind out of range and on
+ * parameters out of range, runs on the context's stream and waits for it once, at its end. */
+int lfdmi_radon_null(lfdmi_ctx *ctx, lfdmi_radon *radon, const void *frames, int dtype, int n, int loc, const float *sigma,
+                     const uint64_t *seeds, int K, int kind, const void *kind_params, void *records);
+
 /* ---- stacked cross-sections -------------------------------------------------------------------------------------------------
  * lfdmi_measure_trails needs every 64-position piece of a trail to stand 5 sigma on its own; a trail of the faint-trail search
  * never does.  lfdmi_stack_profiles measures such a trail's cross-section by the Radon idea turned by 90 degrees: the frame is

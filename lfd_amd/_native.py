@@ -48,6 +48,7 @@ SYMBOLS = (
     "lfdmi_default_radon_lines_params", "lfdmi_radon_search_lines",
     "lfdmi_default_radon_short_params", "lfdmi_radon_search_short",
     "lfdmi_default_radon_wide_params", "lfdmi_radon_search_wide",
+    "lfdmi_radon_null",
     "lfdmi_default_stack_params", "lfdmi_stack_profiles",
     "lfdmi_default_stars_params", "lfdmi_find_stars", "lfdmi_stars_catalog",
 )
@@ -393,6 +394,9 @@ class RadonWide(C.Structure):
 
 RADON_WIDE_DTYPE = np.dtype(RADON_LINE_DTYPE.descr + [("width", "<i4"), ("pad2", "<i4"), ("width_px", "<f8")])
 RADON_MAX_WIDTH = 16
+RADON_NULL_LINES, RADON_NULL_SHORT, RADON_NULL_WIDE = 0, 1, 2
+RADON_NULL_MAX = 64
+RADON_NULL_KINDS = {"lines": RADON_NULL_LINES, "short": RADON_NULL_SHORT, "wide": RADON_NULL_WIDE}
 
 
 def make_radon_wide_params(**params):
@@ -545,6 +549,8 @@ def lib():
         _lib.lfdmi_default_radon_wide_params.argtypes = [C.c_void_p]
         _lib.lfdmi_radon_search_wide.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.lfdmi_radon_null.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         _lib.lfdmi_radon_search_short.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.lfdmi_default_stack_params.restype = None
@@ -1681,3 +1687,28 @@ class Radon(_Handle):
         ``dims()`` counts them from then on."""
         return self._peel("search_wide", make_radon_wide_params, params, RADON_WIDE_DTYPE, bool(plain), frames, sigma, pinned,
                           native_device)
+
+    def null(self, frames, K=16, kind="lines", sigma=None, seeds=None, pinned=False, native_device=False, **kind_params):
+        """The null peaks of every frame: record 0 of the ``kind`` search ("lines", "short" or "wide") of K scrambled
+        realisations of each frame (include/lfdmi.h: faint-trail search, null peaks, steps 17 - 20); frames and sigma as in
+        ``search``.  seeds: None (frame f has seed f) or n uint64.  ``kind_params``: the fields of lfdmi_radon_short_params /
+        lfdmi_radon_wide_params; "lines" takes none.  Returns records [n, K]: RADON_DTYPE, RADON_SHORT_DTYPE or
+        RADON_WIDE_DTYPE.  The first call of a kind allocates what that kind's search does; ``dims()`` counts it."""
+        r, ctx = self._open(), self.ctx
+        if kind not in RADON_NULL_KINDS:
+            raise ValueError("kind: 'lines', 'short' or 'wide'")
+        if kind == "lines" and kind_params:
+            raise TypeError(f"unknown radon null parameter {sorted(kind_params)[0]!r}: kind 'lines' takes none")
+        p = {"lines": lambda: None, "short": make_radon_short_params, "wide": make_radon_wide_params}[kind](**kind_params)
+        dtype = {"lines": RADON_DTYPE, "short": RADON_SHORT_DTYPE, "wide": RADON_WIDE_DTYPE}[kind]
+        frames, code, n, h, w, loc = self._frames(frames, pinned, "Radon.null", native_device=native_device)
+        sg = _sigma(sigma, n)
+        if seeds is not None:
+            seeds = np.ascontiguousarray(seeds, np.uint64).reshape(-1)
+            if seeds.size != n:
+                raise ValueError("seeds: one uint64 per frame")
+        K = int(K)
+        res = np.zeros((n, max(1, min(K, RADON_NULL_MAX))), dtype)       # (out of range: the library refuses before it writes)
+        ctx._chk(self._lib.lfdmi_radon_null(ctx._h, r, _ptr(frames), code, n, loc, _ptr(sg), _ptr(seeds), K, RADON_NULL_KINDS[kind],
+                                            None if p is None else C.byref(p), _ptr(res)))
+        return res

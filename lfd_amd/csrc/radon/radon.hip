@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <math.h>
+#include <stddef.h>
 #include <string.h>
 
 #include <algorithm>
@@ -16,6 +17,7 @@
 #include "k_radon_lines.h"
 #include "k_radon_short.h"
 #include "k_radon_wide.h"
+#include "k_radon_null.h"
 
 struct lfdmi_radon {
     lfdmi_ctx *ctx = nullptr;   // lfdmi_radon_search only: destroy does not touch the context (it may be gone by then)
@@ -44,6 +46,8 @@ struct lfdmi_radon {
     RadonWidePart *wpart = nullptr;
     RadonWideRec *wrec = nullptr;
     int *wid = nullptr;
+    // lfdmi_radon_null only, allocated on its first call: the key and the frame of every slot
+    RadonNullSlot *nslot = nullptr;
     int64_t bytes = 0;
 };
 
@@ -124,7 +128,8 @@ extern "C" void lfdmi_radon_destroy(lfdmi_radon *s) {
     DeviceGuard on(s->device);   // the caller's current device stays what it was
     for (void *x : {(void *)s->V, (void *)s->M, (void *)s->S[0], (void *)s->S[1], (void *)s->N[0], (void *)s->N[1], (void *)s->sigma,
                     (void *)s->stage, (void *)s->part, (void *)s->rec, (void *)s->V2, (void *)s->M2, (void *)s->pre, (void *)s->cnt,
-                    (void *)s->lnd, (void *)s->ext, (void *)s->spart, (void *)s->srec, (void *)s->wpart, (void *)s->wrec, (void *)s->wid})
+                    (void *)s->lnd, (void *)s->ext, (void *)s->spart, (void *)s->srec, (void *)s->wpart, (void *)s->wrec, (void *)s->wid,
+                    (void *)s->nslot})
         if (x) hipFree(x);
     delete s;
 }
@@ -397,6 +402,8 @@ struct LFD_HIDDEN RadonLinesMode {
 };
 
 struct LFD_HIDDEN RadonShortMode {
+    static constexpr int null_wfield = -1;      // (lfdmi_radon_null: a found record has a segment, and no width)
+    float threshold() const { return q.short_threshold; }
     typedef lfdmi_radon_short Out;
     typedef RadonShortRec Rec;
     lfdmi_radon *s;
@@ -417,6 +424,8 @@ struct LFD_HIDDEN RadonShortMode {
 };
 
 struct LFD_HIDDEN RadonWideMode {
+    static constexpr int null_wfield = 7;       // (lfdmi_radon_null: a found record has a segment; RadonWideRec.k in ints, asserted below)
+    float threshold() const { return q.wide_threshold; }
     typedef lfdmi_radon_wide Out;
     typedef RadonWideRec Rec;
     lfdmi_radon *s;
@@ -436,6 +445,15 @@ struct LFD_HIDDEN RadonWideMode {
     }
     static int width(const Out &o) { return o.width; }
 };
+
+// definition step 9's fields of a found record from its line's (width 0) or band's extent
+template <class T> static void radon_fill_segment(const RadonDev &p, const RadonExtDev &x, int width, T &o) {
+    const int P = p.P[o.q >> 1];
+    const double mid = radon_mid(width);
+    o.c1 = x.c1; o.c2 = x.c2; o.seg_n_pix = x.n; o.seg_sum = x.sum; o.seg_snr = x.snr;
+    radon_point(p, o.q, o.c1, (double)(o.y0 + radon_path(o.c1, o.s, P)) + mid, o.ex1, o.ey1);
+    radon_point(p, o.q, o.c2, (double)(o.y0 + radon_path(o.c2, o.s, P)) + mid, o.ex2, o.ey2);
+}
 
 // The chunks and the rounds of a peeling search, after the entry point's checks, c.stage() and the lazy allocations: lines
 // [n * max_lines] and n_lines [n], and with `plain` the plain search's records, which round 0 leaves in s->rec.  A round queues
@@ -474,12 +492,7 @@ static int radon_rounds(RadonCall &c, const Mode &m, typename Mode::Out *lines, 
             const int b = k & 1;
             for (size_t e = 0; e < found_frames[b].size(); e++) {
                 Out &o = lines[(size_t)found_frames[b][e] * K + k];
-                const RadonExtDev &x = hx[b][e];
-                const int P = p.P[o.q >> 1];
-                const double mid = radon_mid(m.width(o));
-                o.c1 = x.c1; o.c2 = x.c2; o.seg_n_pix = x.n; o.seg_sum = x.sum; o.seg_snr = x.snr;
-                radon_point(p, o.q, o.c1, (double)(o.y0 + radon_path(o.c1, o.s, P)) + mid, o.ex1, o.ey1);
-                radon_point(p, o.q, o.c2, (double)(o.y0 + radon_path(o.c2, o.s, P)) + mid, o.ex2, o.ey2);
+                radon_fill_segment(p, hx[b][e], m.width(o), o);
             }
         };
         for (int k = 0; k < K && !alive.empty(); k++) {
@@ -538,6 +551,40 @@ static int radon_rounds(RadonCall &c, const Mode &m, typename Mode::Out *lines, 
     return 0;
 }
 
+// the rules of lfdmi_radon_short_params and lfdmi_radon_wide_params for handle s
+static int radon_short_check(lfdmi_ctx *ctx, const lfdmi_radon *s, const lfdmi_radon_short_params &sq) {
+    const int bb = s->p.b * s->p.b;
+    if (sq.min_strip < 64 || (sq.min_strip & (sq.min_strip - 1)) || sq.max_lines < 1 || sq.max_lines > LFDMI_RADON_MAX_LINES ||
+        sq.peel_halfwidth < 0 || sq.min_seg < 1 || (int64_t)sq.min_seg > (int64_t)sq.min_strip * bb / 2 ||
+        !std::isfinite(sq.short_threshold) || !(sq.short_threshold > 0))
+        return ctx_fail(ctx, LFDMI_ERR_ARG, "radon short params out of range (include/lfdmi.h: lfdmi_radon_short_params)");
+    return 0;
+}
+static int radon_wide_check(lfdmi_ctx *ctx, const lfdmi_radon *s, const lfdmi_radon_wide_params &wq) {
+    if (wq.max_width < 1 || wq.max_width > LFDMI_RADON_MAX_WIDTH || (wq.max_width & (wq.max_width - 1)) || wq.max_lines < 1 ||
+        wq.max_lines > LFDMI_RADON_MAX_LINES || wq.peel_halfwidth < 0 || wq.min_seg < 1 || wq.min_seg > s->par.min_len ||
+        !std::isfinite(wq.wide_threshold) || !(wq.wide_threshold > 0))
+        return ctx_fail(ctx, LFDMI_ERR_ARG, "radon wide params out of range (include/lfdmi.h: lfdmi_radon_wide_params)");
+    return 0;
+}
+
+// what the short and the wide search allocate on their first call
+static int radon_short_alloc(lfdmi_ctx *ctx, lfdmi_radon *s) {
+    // (the partial records in the layout for min_strip = 64, which holds every other)
+    const size_t F = (size_t)s->max_frames, total = (size_t)std::max(1LL, radon_short_layout(s->p, 64).total);
+    int rc;
+    if ((rc = radon_rounds_alloc(ctx, s)) || (rc = radon_lazy(ctx, s, &s->spart, F * total)) || (rc = radon_lazy(ctx, s, &s->srec, F))) return rc;
+    return 0;
+}
+static int radon_wide_alloc(lfdmi_ctx *ctx, lfdmi_radon *s) {
+    const size_t F = (size_t)s->max_frames;
+    int rc;
+    if ((rc = radon_rounds_alloc(ctx, s)) || (rc = radon_lazy(ctx, s, &s->wpart, F * 4 * s->wstride * 2)) ||
+        (rc = radon_lazy(ctx, s, &s->wrec, F)) || (rc = radon_lazy(ctx, s, &s->wid, F)))
+        return rc;
+    return 0;
+}
+
 extern "C" int lfdmi_radon_search_lines(lfdmi_ctx *ctx, lfdmi_radon *s, const void *frames, int dtype, int n, int loc, const float *sigma,
                                         const lfdmi_radon_lines_params *lp, lfdmi_radon_line *lines, int32_t *n_lines) {
     RadonCall c{ctx, s, "lfdmi_radon_search_lines"};
@@ -568,18 +615,10 @@ extern "C" int lfdmi_radon_search_short(lfdmi_ctx *ctx, lfdmi_radon *s, const vo
     RadonShortMode m{s};
     lfdmi_radon_short_params &sq = m.q;
     if (sp) sq = *sp; else lfdmi_default_radon_short_params(&sq);
-    const int bb = s->p.b * s->p.b;
-    if (sq.min_strip < 64 || (sq.min_strip & (sq.min_strip - 1)) || sq.max_lines < 1 || sq.max_lines > LFDMI_RADON_MAX_LINES ||
-        sq.peel_halfwidth < 0 || sq.min_seg < 1 || (int64_t)sq.min_seg > (int64_t)sq.min_strip * bb / 2 ||
-        !std::isfinite(sq.short_threshold) || !(sq.short_threshold > 0))
-        return ctx_fail(ctx, LFDMI_ERR_ARG, "radon short params out of range (include/lfdmi.h: lfdmi_radon_short_params)");
+    if ((rc = radon_short_check(ctx, s, sq))) return rc;
     if ((rc = c.args(frames, lines && n_lines, dtype, n, loc, sigma))) return rc;
     if (n == 0) return 0;
-    // (the partial records in the layout for min_strip = 64, which holds every other)
-    const size_t F = (size_t)c.CH, total = (size_t)std::max(1LL, radon_short_layout(c.p, 64).total);
-    if ((rc = c.stage()) || (rc = radon_rounds_alloc(ctx, s)) || (rc = radon_lazy(ctx, s, &s->spart, F * total)) ||
-        (rc = radon_lazy(ctx, s, &s->srec, F)))
-        return rc;
+    if ((rc = c.stage()) || (rc = radon_short_alloc(ctx, s))) return rc;
     m.sd = radon_short_layout(c.p, sq.min_strip);
     return radon_rounds(c, m, lines, n_lines, plain);
 }
@@ -599,15 +638,133 @@ extern "C" int lfdmi_radon_search_wide(lfdmi_ctx *ctx, lfdmi_radon *s, const voi
     RadonWideMode m{s};
     lfdmi_radon_wide_params &wq = m.q;
     if (wp) wq = *wp; else lfdmi_default_radon_wide_params(&wq);
-    if (wq.max_width < 1 || wq.max_width > LFDMI_RADON_MAX_WIDTH || (wq.max_width & (wq.max_width - 1)) || wq.max_lines < 1 ||
-        wq.max_lines > LFDMI_RADON_MAX_LINES || wq.peel_halfwidth < 0 || wq.min_seg < 1 || wq.min_seg > s->par.min_len ||
-        !std::isfinite(wq.wide_threshold) || !(wq.wide_threshold > 0))
-        return ctx_fail(ctx, LFDMI_ERR_ARG, "radon wide params out of range (include/lfdmi.h: lfdmi_radon_wide_params)");
+    if ((rc = radon_wide_check(ctx, s, wq))) return rc;
     if ((rc = c.args(frames, lines && n_lines, dtype, n, loc, sigma))) return rc;
     if (n == 0) return 0;
-    const size_t F = (size_t)c.CH;
-    if ((rc = c.stage()) || (rc = radon_rounds_alloc(ctx, s)) || (rc = radon_lazy(ctx, s, &s->wpart, F * 4 * s->wstride * 2)) ||
-        (rc = radon_lazy(ctx, s, &s->wrec, F)) || (rc = radon_lazy(ctx, s, &s->wid, F)))
-        return rc;
+    if ((rc = c.stage()) || (rc = radon_wide_alloc(ctx, s))) return rc;
     return radon_rounds(c, m, lines, n_lines, plain);
+}
+
+// ---- null peaks (definition steps 17 - 20) ----------------------------------------------------------------------------------------------
+// The plain search as a Mode: what lfdmi_radon_null needs of one
+struct LFD_HIDDEN RadonPlainMode {
+    static constexpr int null_wfield = -2;      // (no segment: lfdmi_radon_result has none)
+    typedef lfdmi_radon_result Out;
+    typedef RadonRec Rec;
+    lfdmi_radon *s;
+    const Rec *rec() const { return s->rec; }
+    int transform(const RadonCall &c, const float *V, const uint16_t *M, int nf, int) const { return radon_transform(c.ctx, s, c.p, V, M, nf, c.st); }
+    void fill(const RadonDev &p, const Rec &r, Out &o) const { radon_fill(s, p, r, o); }
+};
+
+// k_radon_null_lines reads every kind's record as ints: the fields it names, where it expects them
+#define RADON_NULL_PREFIX(T)                                                                                                      \
+    static_assert(offsetof(T, status) == 0 && offsetof(T, q) == 4 && offsetof(T, y0) == 8 && offsetof(T, s) == 12 &&               \
+                      offsetof(T, n_pix) == 16 && offsetof(T, sum) == 20 && offsetof(T, snr) == 4 * RADN_SNR,                       \
+                  #T ": k_radon_null_lines expects status, q, y0, s, n_pix, sum, snr first")
+RADON_NULL_PREFIX(RadonRec);
+RADON_NULL_PREFIX(RadonShortRec);
+RADON_NULL_PREFIX(RadonWideRec);
+static_assert(offsetof(RadonWideRec, k) == 4 * RadonWideMode::null_wfield, "RadonWideMode::null_wfield is RadonWideRec.k");
+
+static uint64_t radon_splitmix64(uint64_t x) {
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+
+// The chunks of lfdmi_radon_null after the entry point's checks, c.stage() and the lazy allocations.  Slot g = f K + r is
+// realisation r of frame f; a chunk is max_frames consecutive slots, so it reads at most that many frames (which fit the staging
+// buffer) and a frame's realisations may continue in the next chunk, which then uploads the frame again.  Everything is queued;
+// the host buffers live until the one wait at the end.
+template <class Mode>
+static int radon_null(RadonCall &c, const Mode &m, const uint64_t *seeds, int K, typename Mode::Out *records) {
+    typedef typename Mode::Rec Rec;
+    static_assert(sizeof(Rec) % sizeof(int) == 0, "k_radon_null_lines reads records as ints");
+    constexpr bool SEG = Mode::null_wfield >= -1;
+    lfdmi_ctx *ctx = c.ctx;
+    lfdmi_radon *s = c.s;
+    const RadonDev &p = c.p;
+    hipStream_t st = c.st;
+    const int64_t total = (int64_t)c.n * K;
+    const int CH = c.CH;
+    int rc;
+    if ((rc = radon_lazy(ctx, s, &s->nslot, (size_t)CH))) return rc;
+    std::vector<RadonNullSlot> hslot((size_t)total);
+    std::vector<float> hsg((size_t)total);
+    std::vector<Rec> hrec((size_t)total);
+    std::vector<RadonExtDev> hext(SEG ? (size_t)total : 0);
+    for (int64_t g0 = 0; g0 < total; g0 += CH) {
+        const int ns = (int)std::min<int64_t>(CH, total - g0), f0 = (int)(g0 / K), nfr = (int)((g0 + ns - 1) / K) - f0 + 1;
+        for (int a = 0; a < ns; a++) {
+            const int f = (int)((g0 + a) / K), r = (int)((g0 + a) % K);
+            const uint64_t k = radon_splitmix64((seeds ? seeds[f] : (uint64_t)f) + 0x9E3779B97F4A7C15ull * (uint64_t)(r + 1));
+            hslot[g0 + a] = RadonNullSlot{(uint32_t)k, (uint32_t)(k >> 32), f - f0, 0};
+            hsg[g0 + a] = c.hsig[f];
+        }
+        const uint32_t *src = (const uint32_t *)c.frames + (size_t)f0 * c.PX;
+        if (!c.in_dev) {
+            UHIP(hipMemcpyAsync(s->stage, (const char *)c.frames + (size_t)f0 * c.FB, (size_t)nfr * c.FB, hipMemcpyHostToDevice, st));
+            src = (const uint32_t *)s->stage;
+        }
+        UHIP(hipMemcpyAsync(s->sigma, hsg.data() + g0, (size_t)ns * sizeof(float), hipMemcpyHostToDevice, st));
+        UHIP(hipMemcpyAsync(s->nslot, hslot.data() + g0, (size_t)ns * sizeof(RadonNullSlot), hipMemcpyHostToDevice, st));
+        k_radon_prep_null<<<dim3(ceil_div(p.wb, RAD_THREADS), p.hb, ns), RAD_THREADS, 0, st>>>(src, p, s->nslot, s->V, s->M);
+        ULAUNCH("k_radon_prep_null");
+        if ((rc = m.transform(c, s->V, s->M, ns, 0))) return rc;
+        UHIP(hipMemcpyAsync(hrec.data() + g0, m.rec(), (size_t)ns * sizeof(Rec), hipMemcpyDeviceToHost, st));
+        if constexpr (SEG) {
+            int *wid = Mode::null_wfield >= 0 ? s->wid : nullptr;
+            k_radon_null_lines<<<ceil_div(ns, RAD_THREADS), RAD_THREADS, 0, st>>>((const int *)m.rec(), (int)(sizeof(Rec) / sizeof(int)),
+                                                                                  Mode::null_wfield, m.threshold(), ns, s->lnd, wid);
+            ULAUNCH("k_radon_null_lines");
+            k_radon_extent<<<ns, RAD_THREADS, 0, st>>>(s->V, s->M, p, s->lnd, s->sigma, m.q.min_seg, s->pre, s->cnt, radon_pstride(p), s->ext, wid);
+            ULAUNCH("k_radon_extent");
+            UHIP(hipMemcpyAsync(hext.data() + g0, s->ext, (size_t)ns * sizeof(RadonExtDev), hipMemcpyDeviceToHost, st));
+        }
+    }
+    UHIP(hipStreamSynchronize(st));
+    for (int64_t g = 0; g < total; g++) {
+        typename Mode::Out &o = records[g];
+        memset(&o, 0, sizeof(o));
+        m.fill(p, hrec[g], o);
+        if constexpr (SEG)
+            if (o.found) radon_fill_segment(p, hext[g], Mode::width(o), o);
+    }
+    return 0;
+}
+
+extern "C" int lfdmi_radon_null(lfdmi_ctx *ctx, lfdmi_radon *s, const void *frames, int dtype, int n, int loc, const float *sigma,
+                                const uint64_t *seeds, int K, int kind, const void *kind_params, void *records) {
+    RadonCall c{ctx, s, "lfdmi_radon_null"};
+    int rc = c.begin();
+    if (rc) return rc;
+    if (K < 1 || K > LFDMI_RADON_NULL_MAX || kind < LFDMI_RADON_NULL_LINES || kind > LFDMI_RADON_NULL_WIDE ||
+        (kind == LFDMI_RADON_NULL_LINES && kind_params))
+        return ctx_fail(ctx, LFDMI_ERR_ARG, "lfdmi_radon_null: K 1 .. LFDMI_RADON_NULL_MAX, kind LFDMI_RADON_NULL_*, and no kind_params for LINES");
+    if ((uint64_t)s->p.h * (uint64_t)s->p.w >= (1ull << 32))     // (lfdmi_radon_create holds H W to 1e9)
+        return ctx_fail(ctx, LFDMI_ERR_ARG, "lfdmi_radon_null: H * W must be below 2^32");
+    if (kind == LFDMI_RADON_NULL_SHORT) {
+        RadonShortMode m{s};
+        if (kind_params) m.q = *(const lfdmi_radon_short_params *)kind_params; else lfdmi_default_radon_short_params(&m.q);
+        if ((rc = radon_short_check(ctx, s, m.q)) || (rc = c.args(frames, records, dtype, n, loc, sigma))) return rc;
+        if (n == 0) return 0;
+        if ((rc = c.stage()) || (rc = radon_short_alloc(ctx, s))) return rc;
+        m.sd = radon_short_layout(c.p, m.q.min_strip);
+        return radon_null(c, m, seeds, K, (lfdmi_radon_short *)records);
+    }
+    if (kind == LFDMI_RADON_NULL_WIDE) {
+        RadonWideMode m{s};
+        if (kind_params) m.q = *(const lfdmi_radon_wide_params *)kind_params; else lfdmi_default_radon_wide_params(&m.q);
+        if ((rc = radon_wide_check(ctx, s, m.q)) || (rc = c.args(frames, records, dtype, n, loc, sigma))) return rc;
+        if (n == 0) return 0;
+        if ((rc = c.stage()) || (rc = radon_wide_alloc(ctx, s))) return rc;
+        return radon_null(c, m, seeds, K, (lfdmi_radon_wide *)records);
+    }
+    RadonPlainMode m{s};
+    if ((rc = c.args(frames, records, dtype, n, loc, sigma))) return rc;
+    if (n == 0) return 0;
+    if ((rc = c.stage())) return rc;
+    return radon_null(c, m, seeds, K, (lfdmi_radon_result *)records);
 }

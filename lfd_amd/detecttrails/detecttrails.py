@@ -287,11 +287,15 @@ class _RadonStage:
     ``Radon.search_wide``, whose plain records serve as the frame's one line when ``lines`` and ``short`` are None; a frame's
     record is then a ``_WideRecord`` around the record it had, and every found band gets a row in ``wide_out``
     (radon_wide.txt).  With ``prof_out`` the bands' centre-line segments are measured too, their rows end with ``wide`` and
-    the lines' rows with ``lines``."""
+    the lines' rows with ``lines``.  ``null``: K, the realisations of the null peaks (include/lfdmi.h steps 17 - 20): every
+    searched frame also gets the null peaks of each kind that is on (``lines``; ``short`` and ``wide`` where those are), a row
+    per kind in ``null_out`` (radon_null.txt) and a row per found line in ``fap_out`` (radon_fap.txt)."""
 
     def __init__(self, out, params, sigma, lines=None, lines_params=None, seg_out=None, prof_out=None, stack_params=None,
-                 defocus_out=None, defocus_params=None, short=None, short_out=None, lc=None, wide=None, wide_out=None, strip=None):
+                 defocus_out=None, defocus_params=None, short=None, short_out=None, lc=None, wide=None, wide_out=None, strip=None,
+                 null=None, null_out=None, fap_out=None):
         from ..radon import as_params
+        self.null, self.null_out, self.fap_out = null, null_out, fap_out
         self.out, self.params, self.sigma, self._handles = out, as_params(params), float(sigma), {}
         self.wide, self.wide_out = (dict(wide) if wide is not None else None), wide_out
         self.lc, self.last_lc = lc, {}                # an ``_LcStage``; {position: [(record, sections)]} of the last ``batch`` / ``one``
@@ -403,6 +407,59 @@ class _RadonStage:
         self.last_strip = {0: self._strip_part[0]} if self._strip_part is not None else {}
         return rec
 
+    def null_kinds(self):
+        """[(kind, its parameters)] of the null peaks: the searches that are on"""
+        return [("lines", {})] + ([("short", self.short)] if self.short is not None else []) + \
+            ([("wide", self.wide)] if self.wide is not None else [])
+
+    def null_batch(self, ctx, frames, shape, todo, seeds, **where):
+        """the null peaks of the frames ``todo`` (as in ``batch``; seeds: one per entry of todo), where the search left the
+        frames -> {position: {kind: float32 [K]}}"""
+        out, k = {}, 0
+        while k < len(todo):
+            m = k
+            while m + 1 < len(todo) and todo[m + 1] == todo[m] + 1:
+                m += 1
+            a, b = todo[k], todo[m] + 1
+            part = frames.slice(a, b) if isinstance(frames, _native.DeviceFrames) else frames[a:b]
+            handle = self._handle(ctx, shape, min(b - a, 16))
+            for kind, kp in self.null_kinds():
+                snr = handle.null(part, K=self.null, kind=kind, sigma=self.sigma, seeds=seeds[k:m + 1], **kp, **where)["snr"]
+                for j in range(a, b):
+                    out.setdefault(j, {})[kind] = _np.array(snr[j - a], _np.float32)
+            k = m + 1
+        return out
+
+    def null_one(self, img, seed):
+        """one host frame -> its {kind: float32 [K]}"""
+        img = _np.ascontiguousarray(img, _np.float32)
+        with use_context(*img.shape) as ctx:
+            return self.null_batch(ctx, img[None], img.shape, [0], [seed])[0]
+
+    def found_lines(self, rec):
+        """{kind: [(place in peel order, snr)]} of a frame's record: the lines that have rows in the kinds' files"""
+        out = {}
+        if isinstance(rec, _WideRecord):
+            out["wide"] = [(k, rec.recs[k]["snr"]) for k in range(rec.n_lines)]
+            rec = rec.base
+        if isinstance(rec, _ShortRecord):
+            out["short"] = [(k, rec.recs[k]["snr"]) for k in range(rec.n_lines)]
+            rec = rec.base
+        if self.lines is None:
+            out["lines"] = [(0, rec["snr"])] if int(rec["found"]) else []
+        else:
+            out["lines"] = [(k, rec[0][k]["snr"]) for k in range(rec[1])]
+        return out
+
+    def null_rows(self, key, rec, nulls):
+        """a frame's radon_null.txt rows, one per kind, and its radon_fap.txt rows, one per found line"""
+        from ..radon import format_fap_row, format_null_row
+        found = self.found_lines(rec)
+        for kind, _ in self.null_kinds():
+            self.null_out.write(format_null_row(key, kind, nulls[kind]) + "\n")
+            for k, snr in found.get(kind, []):
+                self.fap_out.write(format_fap_row(key, kind, k, snr, nulls[kind]) + "\n")
+
     def row(self, key, rec):
         """the rows of one frame's record: the line if it was found; with ``lines``, every found line in peel order"""
         from ..radon import format_row, format_segment_row
@@ -448,6 +505,9 @@ class _RadonStage:
             self.short_out.flush()
         if self.wide_out is not None:
             self.wide_out.flush()
+        if self.null_out is not None:
+            self.null_out.flush()
+            self.fap_out.flush()
         if self.prof_out is not None:
             self.prof_out.flush()
         if self.defocus_out is not None:
@@ -787,6 +847,8 @@ class _Chunk:
         self.trail_params = trail_params or {}
         self.debug = params_bright.get("debug") or params_dim.get("debug")
         self.rows, self.meas, self.srecs, self.rlines = [None] * n, [None] * n, [None] * n, [None] * n
+        self.keys = [None] * n                        # (run, camcol, filter, field): the seed of a frame's null peaks
+        self.nulls = [None] * n                       # {kind: null peaks} of a searched frame (``radon`` with ``null``), or the exception
         self.gpu_s = 0.0                              # inside the sky + detect calls of the groups that went through
 
 
@@ -842,6 +904,12 @@ def _run_frame(c, i, filter, frame):
                     c.strips[i] = st if isinstance(st, Exception) else ("radon", st)
             except Exception as e:  # noqa: BLE001
                 c.rlines[i] = e
+            if c.radon.null is not None and not isinstance(c.rlines[i], Exception):
+                try:
+                    from ..radon import null_seed
+                    c.nulls[i] = c.radon.null_one(img, null_seed(*c.keys[i]))
+                except Exception as e:  # noqa: BLE001
+                    c.nulls[i] = e
         if c.sub is not None:                         # last: it changes the frame (a copy of it here)
             try:
                 todo = _sub_segments(c, i, c.rows[i][0], c.rows[i][1], c.rlines[i])
@@ -918,6 +986,16 @@ def _run_group(c, idx, filter, shape, inflight, source, second, detect_kw=None, 
                 except Exception as e:  # noqa: BLE001
                     for j in todo:
                         c.rlines[idx[j]] = e
+                else:
+                    if c.radon.null is not None:      # the same frames, while they are where the search read them
+                        try:
+                            from ..radon import null_seed
+                            seeds = [null_seed(*c.keys[idx[j]]) for j in todo]
+                            for j, nulls in c.radon.null_batch(ctx, frames, shape, todo, seeds, **measure_kw).items():
+                                c.nulls[idx[j]] = nulls
+                        except Exception as e:  # noqa: BLE001
+                            for j in todo:
+                                c.nulls[idx[j]] = e
             if c.sub is not None:                     # after every other measurement of the chunk: it changes the frames
                 per_frame = {}
                 try:
@@ -969,6 +1047,10 @@ def _emit(c, i, key, head, shape):
         _log_error(c.errors, key, line, c.debug)
     elif line is not None:
         c.radon.row(key, line)
+        if isinstance(c.nulls[i], Exception):
+            _log_error(c.errors, key, c.nulls[i], c.debug)
+        elif c.nulls[i] is not None:
+            c.radon.null_rows(key, line, c.nulls[i])
     if c.masks is not None:                           # (after the rows above, which it does not touch)
         try:
             shp = c.shapes[i] or tuple(shape)           # (a frame that ran on its own may differ from the chunk's shape)
@@ -1024,6 +1106,7 @@ def process_field(results, errors, run, camcol, filter, field, params_bright, pa
     normalisation, if on), and the frame's stars.txt row is written.  ``masks``: a ``_MaskStage``; a results row, and every found
     faint line of ``radon`` with lines, gets its masks.txt row."""
     c = _Chunk(1, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon, stars, masks, lc, strip, sub)
+    c.keys[0] = (run, camcol, filter, field)
     head = None
     try:
         img, head, cat = _load_frame(run, camcol, filter, field, catalog=stars is None)
@@ -1083,6 +1166,7 @@ def process_loaded(results, errors, loaded, params_bright, params_dim, params_re
     t_in = time.perf_counter()
     n = len(loaded.keys)
     c = _Chunk(n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon, stars, masks, lc, strip, sub)
+    c.keys = list(loaded.keys)
     by_slot = {}
     for i in range(n):
         if loaded.error[i] is not None:
@@ -1176,6 +1260,13 @@ class DetectTrails:
     ey1 ex2 ey2 seg_snr seg_n_pix``; radon.txt and radon_segments.txt stay what they are without it.  With
     ``radon_profiles=True`` (then ``radon_lines`` may be None) the short segments are measured too, and every row of
     radon_profiles.txt ends with its source, ``lines`` or ``short``.
+    ``radon_null=K`` (1 .. 64; needs ``radon=True``): every searched frame also gets its null peaks (include/lfdmi.h: null
+    peaks, steps 17 - 20) of each kind that is on -- lines, and short / wide where ``radon_short`` / ``radon_wide`` are -- while the
+    chunk's frames are on the device, seeded by ``lfd_amd.radon.null_seed(run, camcol, filter, field)``, so resume and any rank
+    split give the same rows.  ``radon_null_file`` (default ``<savepath>/radon_null.txt``) gets one row per frame and kind: ``run
+    camcol filter field kind K null_min null_median null_max``; ``radon_fap_file`` (``<savepath>/radon_fap.txt``) one row per found
+    line: ``run camcol filter field kind line snr n_ge K fap``.  Rank files and resume treat both like radon.txt; every other
+    output stays byte for byte what it is.
     ``radon_wide=True`` or a dict / ``lfd_amd.radon.RadonWideParams`` (needs ``radon=True``): the frames are also searched for
     wide faint trails by scoring sliding bands of the last level's lines (steps 13 - 16 of the definition) and
     ``radon_wide_file`` (default ``<savepath>/radon_wide.txt``) gets one row per found band: ``run camcol filter field line
@@ -1275,6 +1366,15 @@ class DetectTrails:
             from ..radon import RadonParams, as_wide_params
             self.radon_wide = as_wide_params(None if rw is True else rw, RadonParams(**self.radon_params).min_len)
         self.stack_params = {}
+        self.radon_null_file = kwargs.get("radon_null_file", os.path.join(save, "radon_null.txt"))
+        self.radon_fap_file = kwargs.get("radon_fap_file", os.path.join(save, "radon_fap.txt"))
+        self.radon_null = kwargs.get("radon_null")
+        if self.radon_null is not None:
+            if not self.radon:
+                raise ValueError("radon_null needs radon=True: it is a measurement of the faint-trail search")
+            if int(self.radon_null) != self.radon_null or not 1 <= self.radon_null <= _native.RADON_NULL_MAX:
+                raise ValueError("radon_null must be an integer, 1 .. %d" % _native.RADON_NULL_MAX)
+            self.radon_null = int(self.radon_null)
         if self.radon_profiles:
             if not self.radon or (self.radon_lines is None and self.radon_short is None and self.radon_wide is None):
                 raise ValueError("radon_profiles=True needs radon=True and radon_lines=K: the segments it measures are theirs")
@@ -1474,7 +1574,10 @@ class DetectTrails:
                  else contextlib.nullcontext()) as segments_out, \
                 (open(self.radon_short_file + suffix, "a") if self.radon_short is not None else contextlib.nullcontext()) as short_out, \
                 (open(self.radon_wide_file + suffix, "a") if self.radon_wide is not None else contextlib.nullcontext()) as wide_out, \
-                (open(self.radon_profiles_file + suffix, "a") if self.radon_profiles else contextlib.nullcontext()) as rprof_out, \
+                _both(open(self.radon_profiles_file + suffix, "a") if self.radon_profiles else contextlib.nullcontext(),
+                      _both(open(self.radon_null_file + suffix, "a") if self.radon_null is not None else contextlib.nullcontext(),
+                            open(self.radon_fap_file + suffix, "a") if self.radon_null is not None
+                            else contextlib.nullcontext())) as (rprof_out, (null_out, fap_out)), \
                 (open(self.radon_defocus_file + suffix, "a") if self.radon_profiles and self.defocus
                  else contextlib.nullcontext()) as rdef_out, \
                 (open(self.masks_file + suffix, "a") if self.trail_masks else contextlib.nullcontext()) as masks_out, \
@@ -1505,7 +1608,8 @@ class DetectTrails:
                 sigma = _native.make_sky_params(**self.sky_params).target_sigma if self.normalize else 0.025
                 radon = prof_kw["radon"] = _RadonStage(radon_out, self.radon_params, sigma, self.radon_lines, self.radon_lines_params,
                                                        segments_out, rprof_out, self.stack_params, rdef_out, self.defocus_params,
-                                                       self.radon_short, short_out, lc, self.radon_wide, wide_out, strip)
+                                                       self.radon_short, short_out, lc, self.radon_wide, wide_out, strip,
+                                                       self.radon_null, null_out, fap_out)
             masks = None
             if self.trail_masks:
                 masks = prof_kw["masks"] = _MaskStage(masks_out, self.mask_params, self.mask_dir)

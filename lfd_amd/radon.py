@@ -5,7 +5,8 @@ device), a one-call helper and the radon.txt format of ``DetectTrails(radon=True
 the definition): ``RadonLinesParams``, the dyadic path, a segment's end points, ``search_lines`` and the radon_segments.txt format;
 for short trails, scored on every dyadic level (steps 10 - 12): ``RadonShortParams``, ``search_short`` and the radon_short.txt
 format; for wide trails, scored as sliding bands of neighbouring lines (steps 13 - 16): ``RadonWideParams``, ``search_wide``
-and the radon_wide.txt format.
+and the radon_wide.txt format; for a frame's own noise ceiling (null peaks, steps 17 - 20): ``null_peaks``, ``false_alarm``,
+``null_threshold`` and the radon_null.txt and radon_fap.txt formats.
 """
 import dataclasses
 import math
@@ -26,6 +27,9 @@ SHORT_COLUMNS = ("run", "camcol", "filter", "field", "line", "level", "strip", "
                  "seg_n_pix")
 WIDE_COLUMNS = ("run", "camcol", "filter", "field", "line", "width", "width_px", "snr", "n_pix", "ex1", "ey1", "ex2", "ey2", "seg_snr",
                 "seg_n_pix")
+NULL_KINDS = ("lines", "short", "wide")
+NULL_COLUMNS = ("run", "camcol", "filter", "field", "kind", "K", "null_min", "null_median", "null_max")
+FAP_COLUMNS = ("run", "camcol", "filter", "field", "kind", "line", "snr", "n_ge", "K", "fap")
 INT_COLUMNS = frozenset(("run", "camcol", "field", "line", "level", "strip", "width", "n_pix", "seg_n_pix"))   # of every file here
 
 
@@ -286,6 +290,103 @@ def search_frames(ctx, frames, sigma=None, **params):
     """Search (n, h, w) or (h, w) frames on ``ctx``: RADON_DTYPE records, one per frame.  For repeated calls keep a
     ``_native.Radon`` handle instead: this one is created and destroyed per call."""
     return _search(ctx, frames, as_params(params), lambda r, arr: r.search(arr, sigma=sigma))
+
+
+def null_peaks(ctx, frames, K=16, kind="lines", sigma=None, seeds=None, **params):
+    """The null peaks of (n, h, w) or (h, w) frames on ``ctx`` (include/lfdmi.h: faint-trail search, null peaks): float32
+    [n, K], the best score of the ``kind`` search ("lines", "short", "wide") of K scrambled realisations of every frame -- the
+    frame's own noise ceiling.  ``params``: fields of RadonParams and of the kind's parameters.  seeds: None (frame f has seed
+    f) or one uint64 per frame.  A realisation without a candidate has the peak 0.  The handle is created and destroyed per
+    call; ``_native.Radon.null`` returns the whole records."""
+    if kind not in NULL_KINDS:
+        raise ValueError("kind: 'lines', 'short' or 'wide'")
+    if not 1 <= int(K) <= _native.RADON_NULL_MAX:
+        raise ValueError("K must be 1 .. %d" % _native.RADON_NULL_MAX)
+    kp = {}
+    if kind == "short":
+        params, kp = _split(params, RadonShortParams)
+    elif kind == "wide":
+        params, kp = _split(params, RadonWideParams)
+    rp = as_params(params)
+    if kind == "short":
+        kp = as_short_params(kp, rp.get("bin", RadonParams.bin))
+    elif kind == "wide":
+        kp = as_wide_params(kp, rp.get("min_len", RadonParams.min_len))
+    return _search(ctx, frames, rp, lambda r, arr: np.ascontiguousarray(r.null(arr, K=K, kind=kind, sigma=sigma, seeds=seeds, **kp)["snr"]))
+
+
+def false_alarm(snr, null_snr):
+    """(1 + #{null >= snr}) / (K + 1): the standard estimate of the chance that a frame without a trail reaches ``snr``, from
+    that frame's K null peaks; never 0 (K nulls cannot show less than 1 / (K + 1))."""
+    null = np.asarray(null_snr, np.float32).reshape(-1)
+    if null.size < 1:
+        raise ValueError("null_snr: at least one null peak")
+    return (1 + int(np.count_nonzero(null >= np.float32(snr)))) / (null.size + 1)
+
+
+def null_threshold(null_snr, margin=1.5):
+    """``margin`` times the largest null peak: the rule the default thresholds follow on their noise crops (include/lfdmi.h,
+    steps 5 and 12), applied to a frame's (or a set of frames') own null peaks."""
+    null = np.asarray(null_snr, np.float32).reshape(-1)
+    if null.size < 1:
+        raise ValueError("null_snr: at least one null peak")
+    return float(margin) * float(null.max())
+
+
+def null_seed(run, camcol, filter, field):
+    """The seed of a frame's null peaks in ``DetectTrails(radon_null=K)``: a fixed 64-bit mix of (run, camcol, filter index,
+    field), so a resumed run and any rank split give the same rows.  filter: one of 'ugriz' or its index."""
+    fi = "ugriz".index(filter) if isinstance(filter, str) else int(filter)
+    x = 0
+    for v in (int(run), int(camcol), fi, int(field)):
+        x = _splitmix64((x ^ (v & _MASK64)) & _MASK64)
+    return x
+
+
+_MASK64 = (1 << 64) - 1
+
+
+def _splitmix64(x):
+    x = (x + 0x9E3779B97F4A7C15) & _MASK64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _MASK64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _MASK64
+    return x ^ (x >> 31)
+
+
+def format_null_row(meta, kind, null_snr):
+    """One radon_null.txt row: meta = (run, camcol, filter, field), the kind and its K null peaks' minimum, median and maximum
+    (float32 values, floats with repr; the median of an even K is the float32 mean of the middle two)"""
+    null = np.sort(np.asarray(null_snr, np.float32).reshape(-1))
+    return " ".join(str(v) for v in (*meta, kind, null.size, repr(float(null[0])), repr(float(np.median(null))), repr(float(null[-1]))))
+
+
+def format_fap_row(meta, kind, line, snr, null_snr):
+    """One radon_fap.txt row of a found line: meta, the kind, the line's place in peel order, its snr, how many of the frame's K
+    null peaks reach it, K and ``false_alarm``"""
+    null = np.asarray(null_snr, np.float32).reshape(-1)
+    n_ge = int(np.count_nonzero(null >= np.float32(snr)))
+    return " ".join(str(v) for v in (*meta, kind, int(line), repr(float(snr)), n_ge, null.size, repr(false_alarm(snr, null))))
+
+
+def read_null(path):
+    """radon_null.txt (rows only, no header line) -> list of dicts keyed by NULL_COLUMNS"""
+    return _read_kinds(path, NULL_COLUMNS)
+
+
+def read_fap(path):
+    """radon_fap.txt (rows only, no header line) -> list of dicts keyed by FAP_COLUMNS"""
+    return _read_kinds(path, FAP_COLUMNS)
+
+
+def _read_kinds(path, columns):
+    ints = INT_COLUMNS | {"K", "n_ge"}
+    rows = []
+    with open(path) as f:
+        for ln in f:
+            parts = ln.split()
+            if parts:
+                rows.append({k: v if k in ("filter", "kind") else int(v) if k in ints else float(v) for k, v in zip(columns, parts)})
+    return rows
 
 
 def _format(columns, meta, line, rec):

@@ -1,7 +1,7 @@
 """Injection and recovery: add model trails of known line and brightness to frames, detect, and count what comes back -- the
 detector's efficiency as a function of the trail's peak (include/lfdmi.h: trail injection).
 
-    python -m lfd_amd.recovery --synth K0:N --peaks 0.05,0.1,0.2,5 --out DIR [--detector radon | radon-short] [--length-frac F]
+    python -m lfd_amd.recovery --synth K0:N --peaks 0.05,0.1,0.2,5 --out DIR [--detector radon | radon-short] [--length-frac F] [--null K]
 
 The plan (``draw_trails``), the matching (``match``) and the rows use integer RNG draws and IEEE + - * / sqrt only -- cos and sin
 come from ``cos_sin`` below, a fixed sequence of multiplications and additions -- so every machine draws the same plan and
@@ -193,16 +193,21 @@ def radon_records(lines):
 
 
 def run(ctx, frames, cats, rs, trails, tables, table_step, params_bright=None, params_dim=None, subsample=4, profiles=False,
-        k=K_MATCH, detector="hough", radon_params=None, sigma=None, short_params=None):
+        k=K_MATCH, detector="hough", radon_params=None, sigma=None, short_params=None, null=0):
     """Copy ``frames`` ((n, h, w) float32 numpy or torch CUDA), inject the plan ``trails`` (tables of peak 1: see
     ``inject.normalise_peak``), run ``detect_batch`` and match: ROW_DTYPE rows, one per trail.  cats: the frames' catalogues
     (a list of dicts, a packed dict or None) and rs their remove_stars parameters; profiles=True also runs ``measure_trails``
     and fills fwhm.  detector="radon": the stars are removed (``remove_stars``) and the faint-trail search
     (include/lfdmi.h: faint-trail search; ``radon_params``, ``sigma``) takes the detector's place; its line is matched by the
     same rule, with params_bright's houghMethod as the cell.  detector="radon-short": the short-trail search (steps 10 - 12
-    of that definition; ``short_params``) instead, and the parent line of a frame's first record is matched."""
+    of that definition; ``short_params``) instead, and the parent line of a frame's first record is matched.  null=K > 0 (the
+    radon detectors): the frames' null peaks of that search (include/lfdmi.h: null peaks; frame f has seed f) are measured on
+    the same frames, and the call returns (rows, fap): float64 [n trails], ``radon.false_alarm`` of each trail's frame's line
+    among its frame's K null peaks."""
     if detector not in ("hough", "radon", "radon-short"):
         raise ValueError("detector: 'hough', 'radon' or 'radon-short'")
+    if null and detector == "hough":
+        raise ValueError("null: the null peaks belong to the radon detectors")
     from .catalogs import pack_catalogs
     from .detecttrails import default_params
     pb, pd, _ = default_params()
@@ -219,11 +224,16 @@ def run(ctx, frames, cats, rs, trails, tables, table_step, params_bright=None, p
         rp = _radon.as_params(radon_params)
         with _native.Radon(ctx, (h, w), max_frames=min(n, 16), **rp) as search:
             if detector == "radon":
+                kind, sp = "lines", {}
                 lines = search.search(work, sigma=sigma)
             else:
-                sp = _radon.as_short_params(short_params, rp.get("bin", _radon.RadonParams.bin))
+                kind, sp = "short", _radon.as_short_params(short_params, rp.get("bin", _radon.RadonParams.bin))
                 lines = search.search_short(work, sigma=sigma, **sp)[0][:, 0]
-        return make_rows(radon_records(lines), trails, pb, pd, (h, w), k=k)
+            peaks = search.null(work, K=int(null), kind=kind, sigma=sigma, **sp)["snr"] if null else None
+        rows = make_rows(radon_records(lines), trails, pb, pd, (h, w), k=k)
+        if peaks is None:
+            return rows
+        return rows, np.array([_radon.false_alarm(lines["snr"][int(t["frame"])], peaks[int(t["frame"])]) for t in trails], np.float64)
     recs = ctx.detect_batch(work, pb, pd, packed, rs if packed is not None else None)
     measured = None
     if profiles:
@@ -242,8 +252,10 @@ def wilson(recovered, n, z=1.0):
     return mid - half, mid + half
 
 
-def completeness(rows, edges, z=1.0):
-    """Per peak bin [edges[i], edges[i+1]): n, recovered (matched rows), efficiency and its Wilson interval at z sigmas"""
+def completeness(rows, edges, z=1.0, fap=None):
+    """Per peak bin [edges[i], edges[i+1]): n, recovered (matched rows), efficiency and its Wilson interval at z sigmas; with
+    ``fap`` (one false-alarm estimate per row, ``run(..., null=K)``) also median_fap, the median over the bin's recovered
+    trails (NaN without one)"""
     out = []
     for lo, hi in zip(edges[:-1], edges[1:]):
         sel = (rows["peak"] >= lo) & (rows["peak"] < hi)
@@ -251,6 +263,9 @@ def completeness(rows, edges, z=1.0):
         wl, wh = wilson(r, n, z)
         out.append({"lo": float(lo), "hi": float(hi), "n": n, "recovered": r, "efficiency": r / n if n else float("nan"),
                     "wilson_lo": wl, "wilson_hi": wh})
+        if fap is not None:
+            got = np.asarray(fap, np.float64)[sel & (rows["matched"] != 0)]
+            out[-1]["median_fap"] = float(np.median(got)) if got.size else float("nan")
     return out
 
 
@@ -281,10 +296,14 @@ def peak_edges(peaks):
 
 
 def format_table(table):
-    lines = ["%10s %10s %6s %9s %10s %9s %9s" % ("peak_lo", "peak_hi", "n", "recovered", "efficiency", "wilson_lo", "wilson_hi")]
+    """the completeness table as text; a table made with ``fap`` has a last column, median_fap"""
+    fap = bool(table) and "median_fap" in table[0]
+    lines = ["%10s %10s %6s %9s %10s %9s %9s" % ("peak_lo", "peak_hi", "n", "recovered", "efficiency", "wilson_lo", "wilson_hi") +
+             (" %10s" % "median_fap" if fap else "")]
     for b in table:
         lines.append("%10.4g %10.4g %6d %9d %10.4f %9.4f %9.4f" % (b["lo"], b["hi"], b["n"], b["recovered"], b["efficiency"],
-                                                                  b["wilson_lo"], b["wilson_hi"]))
+                                                                  b["wilson_lo"], b["wilson_hi"]) +
+                     (" %10.4f" % b["median_fap"] if fap else ""))
     return "\n".join(lines)
 
 
@@ -306,7 +325,12 @@ def main(argv=None):
     ap.add_argument("--bin", type=int, default=None, help="--detector radon / radon-short: lfdmi_radon_params.bin")
     ap.add_argument("--length-frac", type=float, default=1.0,
                     help="inject every trail over this fraction of its crossing, at a random place along it (default 1: the whole crossing)")
+    ap.add_argument("--null", type=int, default=0, metavar="K",
+                    help="--detector radon / radon-short: also measure K null peaks per frame and add the median false-alarm "
+                         "estimate of the recovered trails to the table")
     a = ap.parse_args(argv)
+    if a.null and a.detector == "hough":
+        ap.error("--null needs --detector radon or radon-short")
     k0, n = (int(v) for v in a.synth.split(":"))
     peaks = [float(v) for v in a.peaks.split(",")]
     frames, cats, truths = synth.make_frames(k0, n, with_truth=True)
@@ -320,10 +344,11 @@ def main(argv=None):
     plan = shorten(draw_trails(len(keep), frames.shape[1:], a.seed, peaks), frames.shape[1:], a.length_frac, a.seed)
     with _native.Context(0, frames.shape[1], frames.shape[2], 16) as ctx:
         rows = run(ctx, frames, cats, rs, plan, _inject.normalise_peak(table), step, pb, pd, profiles=a.profiles,
-                   detector=a.detector, radon_params={"bin": a.bin} if a.bin else None)
+                   detector=a.detector, radon_params={"bin": a.bin} if a.bin else None, null=a.null)
+    rows, fap = rows if a.null else (rows, None)
     os.makedirs(a.out, exist_ok=True)
     write_recovery(os.path.join(a.out, "recovery.txt"), rows)
-    print(format_table(completeness(rows, peak_edges(peaks))))
+    print(format_table(completeness(rows, peak_edges(peaks), fap=fap)))
 
 
 if __name__ == "__main__":
