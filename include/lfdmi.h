@@ -398,6 +398,40 @@ int lfdmi_debug_tail(lfdmi_ctx *ctx, int n, int kmax, const float *h1, const int
  * top of its chunk number `chunk` (0-based; a chunk is the feed's unit for host frames, max_inflight frames otherwise),
  * after the earlier chunks ran normally; -1 disarms.  The context stays usable. */
 int lfdmi_debug_fail_chunk(lfdmi_ctx *ctx, int chunk);
+/* developer hooks for tests of the measurement units' chunk loops (lfdmi_light_curves, lfdmi_mask_trails, lfdmi_trail_strips,
+ * lfdmi_subtract_trails, lfdmi_inject_trails, lfdmi_find_stars, lfdmi_stack_profiles).  Each of these calls goes through the
+ * device in chunks of jobs, staging slots, batches of cells and launches whose sizes are compiled in and far beyond what a quick
+ * test reaches.  lfdmi_debug_unit_limits lowers them for the later unit calls on this context: a field of 0 leaves that limit at
+ * its compiled value, a positive field replaces it where it is smaller (a unit takes the minimum of the two, so no setting makes
+ * an allocation or a launch larger than the default does), a negative field is LFDMI_ERR_ARG and changes nothing; lim == NULL
+ * restores every default.  No result depends on a limit.
+ *   list_pairs        (job, tile) pairs a chunk lists: a chunk holds max(1, list_pairs / tiles) jobs      (default 8 Mi)
+ *   stage_bytes       bytes of host frames and host planes a chunk stages: max(1, stage_bytes / bytes per job) jobs
+ *                     (512 MiB; find_stars and stack_profiles: 1 GiB, frames per chunk or group); no effect on device buffers
+ *   cell_bytes        bytes of 16-byte cells: trail_strips opens a new batch of segments, subtract_trails a new chunk of frames,
+ *                     when the next segment's (frame's) cells no longer fit; one segment (frame) alone always does  (512 MiB)
+ *   render_blocks     persistent blocks that walk a chunk's list: the grid is min(pairs of the chunk, render_blocks)   (2048)
+ *   stars_rec_bytes   find_stars: bytes of records a chunk returns to the host: max(1, bytes / (max_obj * 32)) frames   (256 MiB)
+ *   stack_part_bytes  stack_profiles: bytes of block sums and counts of one launch: whole segments up to
+ *                     max(1, bytes / (8 * bins)) blocks, a single segment that needs more alone                   (128 MiB)
+ *                     (a segment takes (a_last >> 5) - (a_first >> 5) + 2 blocks of 32 columns, its two halves apart)
+ * lfdmi_debug_unit_split writes the split of the context's last unit call to out[0 .. n-1] (entries past
+ * LFDMI_UNIT_SPLIT_COUNTS are 0): out[0] chunks of jobs (find_stars: chunks of frames; stack_profiles: groups of frames),
+ * out[1] batches of cells (trail_strips; 0 elsewhere), out[2] the largest grid of persistent blocks launched (0: the unit has
+ * none), out[3] launches of the first pass of the first group (stack_profiles; 0 elsewhere).  A call that returns before it
+ * splits anything (an error, no job) leaves zeros.  Both refuse (LFDMI_ERR_ARG) while calls are in flight.
+ * The limits and the split belong to the context but are kept beside it (lfd_amd/csrc/limits/), so that this hook changes
+ * nothing of the detection kernels' translation unit.  The first call of either entry with a context (lim != NULL) opens the
+ * context's entry: from then on its unit calls read the limits and record their split (a struct of zeros records and lowers
+ * nothing); before that, and for a context that never calls them, nothing is kept and lfdmi_debug_unit_split's first answer is
+ * zeros.  lfdmi_debug_unit_limits(ctx, NULL) restores every default and closes the entry; whoever opened one calls it before
+ * lfdmi_ctx_destroy, which does not know of the entry (the Python binding's Context.close does). */
+typedef struct lfdmi_unit_limits {
+    int64_t list_pairs, stage_bytes, cell_bytes, render_blocks, stars_rec_bytes, stack_part_bytes;
+} lfdmi_unit_limits;
+#define LFDMI_UNIT_SPLIT_COUNTS 4
+int lfdmi_debug_unit_limits(lfdmi_ctx *ctx, const lfdmi_unit_limits *lim);
+int lfdmi_debug_unit_split(lfdmi_ctx *ctx, int64_t *out, int n);
 /* developer check: the device's float32 results of the three libm calls on minAreaRect's accept / reject path (angle in
  * degrees of atan2(y, x) as cv::minAreaRect rounds it; cos / sin of that angle times 0.5 as RotatedRect::points does), for
  * n host operand pairs -- compared with the host libm by tests/test_gpu_stages.py */

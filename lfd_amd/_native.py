@@ -29,6 +29,7 @@ ERR_ARG, ERR_DTYPE, ERR_HIP, ERR_UNSUPPORTED, ERR_CAPACITY, ERR_NOLINES = -1, -2
 SYMBOLS = (
     "lfdmi_version", "lfdmi_default_caps", "lfdmi_ctx_create", "lfdmi_ctx_create_sized", "lfdmi_ctx_bytes", "lfdmi_spill_count", "lfdmi_get_stats",
     "lfdmi_ctx_destroy", "lfdmi_last_error", "lfdmi_set_stream", "lfdmi_process_multiscale", "lfdmi_debug_frame_profile", "lfdmi_debug_tail", "lfdmi_debug_trig", "lfdmi_debug_fail_chunk",
+    "lfdmi_debug_unit_limits", "lfdmi_debug_unit_split",
     "lfdmi_max_inflight", "lfdmi_prep_u8", "lfdmi_equalize_hist", "lfdmi_dilate", "lfdmi_erode",
     "lfdmi_canny", "lfdmi_gaussian_blur", "lfdmi_fit_min_area_rect", "lfdmi_hough_lines", "lfdmi_hough_accum",
     "lfdmi_hough_dims", "lfdmi_remove_stars", "lfdmi_process_bright", "lfdmi_process_dim",
@@ -68,6 +69,14 @@ class Params(C.Structure):
                 ("erode_kh", C.c_int32), ("erode_kw", C.c_int32), ("erodeKernel", C.c_void_p),
                 ("minFlux", C.c_double), ("addFlux", C.c_double),
                 ("gaussKernel", C.c_int32), ("gaussSigma", C.c_double)]
+
+
+class UnitLimits(C.Structure):
+    """lfdmi_unit_limits: what ``Context.debug_unit_limits`` lowers (0: the compiled default)"""
+    _fields_ = [(k, C.c_int64) for k in ("list_pairs", "stage_bytes", "cell_bytes", "render_blocks", "stars_rec_bytes", "stack_part_bytes")]
+
+
+UNIT_SPLIT_NAMES = ("chunks", "batches", "grid", "launches")
 
 
 class Caps(C.Structure):
@@ -562,6 +571,8 @@ def lib():
         _lib.lfdmi_find_stars.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_int, C.c_void_p]
         _lib.lfdmi_stars_catalog.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p]
+        _lib.lfdmi_debug_unit_limits.argtypes = [C.c_void_p, C.c_void_p]
+        _lib.lfdmi_debug_unit_split.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     return _lib
 
 
@@ -834,6 +845,7 @@ class Context:
                 b.close()
             for k in list(getattr(self, "_skies", ())):       # and so do its sky and radon handles
                 k.close()
+            self._lib.lfdmi_debug_unit_limits(h, None)       # (forgets what debug_unit_limits / a unit call noted beside the context)
             self._h = None
             self._lib.lfdmi_ctx_destroy(h)
 
@@ -895,6 +907,33 @@ class Context:
     def debug_fail_chunk(self, chunk):
         """Developer hook: the next detect_batch fails (ERR_ARG) at the top of chunk ``chunk`` (tests of the error path)."""
         self._chk(self._lib.lfdmi_debug_fail_chunk(self._h, int(chunk)))
+
+    def debug_unit_limits(self, forget=False, **limits):
+        """Developer hook (tests of the measurement units' chunk loops): lower the limits that split a unit's call on this
+        context -- list_pairs, stage_bytes, cell_bytes, render_blocks, stars_rec_bytes, stack_part_bytes (include/lfdmi.h:
+        lfdmi_debug_unit_limits).  A limit that is not named, or 0, is at its compiled default; no argument restores them all.
+        From the first call of this or of ``debug_unit_split`` on, the context's unit calls record their split.
+        A value can only lower a limit; a negative one is refused (ERR_ARG).  ``forget=True`` passes NULL: every default again
+        and no split recorded any more, as on a context that never called this (``close`` does it)."""
+        if forget:
+            if limits:
+                raise TypeError("debug_unit_limits: forget=True takes no limit")
+            self._chk(self._lib.lfdmi_debug_unit_limits(self._h, None))
+            return
+        lim = UnitLimits()                                   # (zeros: every default, and the split goes on being recorded)
+        for k, v in limits.items():
+            if k not in dict(UnitLimits._fields_):
+                raise TypeError(f"debug_unit_limits: unknown limit {k!r}")
+            setattr(lim, k, int(v))
+        self._chk(self._lib.lfdmi_debug_unit_limits(self._h, C.byref(lim)))
+
+    def debug_unit_split(self):
+        """How the last measurement unit call on this context was split: a dict of ``chunks`` (of jobs; find_stars: of frames;
+        stack_profiles: groups of frames), ``batches`` (trail_strips' batches of cells), ``grid`` (the largest grid of persistent
+        blocks) and ``launches`` (stack_profiles: of the first pass of the first group); 0 where the unit has no such count."""
+        out = np.zeros(len(UNIT_SPLIT_NAMES), np.int64)
+        self._chk(self._lib.lfdmi_debug_unit_split(self._h, _ptr(out), len(out)))
+        return dict(zip(UNIT_SPLIT_NAMES, (int(v) for v in out)))
 
     def set_stage_images(self, mode):
         """Which calls keep the 8-bit stage images for get_stage: -1 the per-pass calls do and detect_batch does not

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../unit.h"
+#include "../limits/limits.h"
 #include "k_inject.h"
 
 static_assert(INJ_MAX_TABLE == LFDMI_INJECT_MAX_TABLE, "the LDS table holds the header's cap");
@@ -26,6 +27,8 @@ extern "C" int lfdmi_inject_trails(lfdmi_ctx *ctx, void *frames, int dtype, int 
     if (!ctx) return LFDMI_ERR_ARG;
     int rc = ctx_begin(ctx);
     if (rc) return rc;
+    UnitState *unit = ctx_unit(ctx);   // (one look-up a call: the limits and the split it records)
+    UnitSplit *split = &unit->split;
     if (dtype != LFDMI_F32) return ctx_fail(ctx, LFDMI_ERR_ARG, "lfdmi_inject_trails takes LFDMI_F32 frames");
     if ((rc = unit_loc(ctx, loc))) return rc;
     if (n < 0 || n_trails < 0 || h < 1 || w < 1 || (double)h * w > 1e9)
@@ -75,8 +78,9 @@ extern "C" int lfdmi_inject_trails(lfdmi_ctx *ctx, void *frames, int dtype, int 
 
     // chunks of jobs: the list of a chunk holds at most INJ_LIST_MAX pairs, host frames of a chunk at most INJ_STAGE_BYTES
     const bool in_dev = loc == LFDMI_DEVICE;
-    size_t CH = std::max<size_t>(1, INJ_LIST_MAX / ntiles);
-    if (!in_dev) CH = std::min(CH, std::max<size_t>(1, INJ_STAGE_BYTES / FB));
+    size_t CH = std::max<size_t>(1, unit->limit_of(LIM_LIST_PAIRS, INJ_LIST_MAX) / ntiles);
+    if (!in_dev) CH = std::min(CH, std::max<size_t>(1, unit->limit_of(LIM_STAGE_BYTES, INJ_STAGE_BYTES) / FB));
+    const size_t walk_max = unit->limit_of(LIM_RENDER_BLOCKS, INJ_RENDER_BLOCKS);
     std::vector<InjJob> hj;
     std::vector<int> jframe;
     for (int f = 0; f < n; f++)
@@ -113,11 +117,12 @@ extern "C" int lfdmi_inject_trails(lfdmi_ctx *ctx, void *frames, int dtype, int 
             for (size_t k = 0; k < c; k++)
                 UHIP(hipMemcpyAsync(d_buf + k * N, (const char *)frames + (size_t)jframe[j0 + k] * FB, FB, hipMemcpyHostToDevice, st));
         UHIP(hipMemsetAsync(d_count, 0, sizeof(int), st));
-        const size_t pairs = c * ntiles;
+        const size_t pairs = c * ntiles, walk = std::min(pairs, walk_max);
+        split->chunks++;
+        split->grid = std::max<int64_t>(split->grid, (int64_t)walk);
         k_inject_cull<<<(unsigned)((pairs + INJ_THREADS - 1) / INJ_THREADS), INJ_THREADS, 0, st>>>(d_job + j0, (int)c, d_tr, p, d_list, d_count);
         ULAUNCH("k_inject_cull");
-        k_inject_render<<<(unsigned)std::min<size_t>(pairs, INJ_RENDER_BLOCKS), INJ_THREADS, 0, st>>>(base, d_job + j0, d_tr, d_tab, p, d_list,
-                                                                                                  d_count);
+        k_inject_render<<<(unsigned)walk, INJ_THREADS, 0, st>>>(base, d_job + j0, d_tr, d_tab, p, d_list, d_count);
         ULAUNCH("k_inject_render");
         if (!in_dev)
             for (size_t k = 0; k < c; k++)

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../unit.h"
+#include "../limits/limits.h"
 #include "k_lc.h"
 
 static_assert(sizeof(lfdmi_lc_segment) == 64 && sizeof(lfdmi_lc_params) == 24 && sizeof(lfdmi_lc) == 88 && sizeof(lfdmi_lc_section) == 112,
@@ -123,6 +124,8 @@ extern "C" int lfdmi_light_curves(lfdmi_ctx *ctx, const void *frames, int dtype,
     if (!ctx) return LFDMI_ERR_ARG;
     int rc = ctx_begin(ctx);
     if (rc) return rc;
+    UnitState *unit = ctx_unit(ctx);   // (one look-up a call: the limits and the split it records)
+    UnitSplit *split = &unit->split;
     if ((rc = unit_dtype(ctx, "lfdmi_light_curves", dtype)) || (rc = unit_loc(ctx, loc))) return rc;
     if (n < 0 || n_seg < 0 || h < 1 || w < 1 || h > 65536 || w > 65536 || (double)h * w > 1e9)
         return ctx_fail(ctx, LFDMI_ERR_ARG, "lfdmi_light_curves: n, n_seg >= 0, h and w 1 .. 65536, h * w at most 1e9");
@@ -178,8 +181,9 @@ extern "C" int lfdmi_light_curves(lfdmi_ctx *ctx, const void *frames, int dtype,
 
     // chunks of jobs: the list of a chunk holds at most LC_LIST_MAX pairs, what a chunk stages at most LC_STAGE_BYTES
     const bool stage = loc != LFDMI_DEVICE, m_stage = stage && mask;
-    size_t CH = std::max<size_t>(1, LC_LIST_MAX / ntiles);
-    if (stage) CH = std::min(CH, std::max<size_t>(1, LC_STAGE_BYTES / (FB + (m_stage ? N : 0))));
+    size_t CH = std::max<size_t>(1, unit->limit_of(LIM_LIST_PAIRS, LC_LIST_MAX) / ntiles);
+    if (stage) CH = std::min(CH, std::max<size_t>(1, unit->limit_of(LIM_STAGE_BYTES, LC_STAGE_BYTES) / (FB + (m_stage ? N : 0))));
+    const size_t walk_max = unit->limit_of(LIM_RENDER_BLOCKS, LC_RENDER_BLOCKS);
     std::vector<LcJob> hj;
     std::vector<int> jframe;
     for (int f = 0; f < n; f++)
@@ -229,11 +233,12 @@ extern "C" int lfdmi_light_curves(lfdmi_ctx *ctx, const void *frames, int dtype,
                 if (m_stage) UHIP(hipMemcpyAsync(d_mbuf + k * N, mask + f * N, N, hipMemcpyHostToDevice, st));
             }
             UHIP(hipMemsetAsync(d_count, 0, sizeof(int), st));
-            const size_t pairs = c * ntiles;
+            const size_t pairs = c * ntiles, walk = std::min(pairs, walk_max);
+            split->chunks++;
+            split->grid = std::max<int64_t>(split->grid, (int64_t)walk);
             k_lc_cull<<<(unsigned)((pairs + LC_THREADS - 1) / LC_THREADS), LC_THREADS, 0, st>>>(d_job + j0, (int)c, d_seg, p, d_list, d_count);
             ULAUNCH("k_lc_cull");
-            k_lc_render<<<(unsigned)std::min<size_t>(pairs, LC_RENDER_BLOCKS), LC_THREADS, 0, st>>>(fbase, mbase, d_job + j0, d_seg, p, d_list, d_count,
-                                                                                                d_cnt, d_q);
+            k_lc_render<<<(unsigned)walk, LC_THREADS, 0, st>>>(fbase, mbase, d_job + j0, d_seg, p, d_list, d_count, d_cnt, d_q);
             ULAUNCH("k_lc_render");
         }
         UHIP(hipMemcpyAsync(hcnt.data(), d_cnt, 3 * nsec * sizeof(int32_t), hipMemcpyDeviceToHost, st));

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../unit.h"
+#include "../limits/limits.h"
 #include "k_mask.h"
 
 static_assert(MSK_FILL_NONE == LFDMI_MASK_FILL_NONE && MSK_FILL_ZERO == LFDMI_MASK_FILL_ZERO && MSK_FILL_NAN == LFDMI_MASK_FILL_NAN &&
@@ -53,6 +54,8 @@ extern "C" int lfdmi_mask_trails(lfdmi_ctx *ctx, void *frames, int dtype, int n,
     if (!ctx) return LFDMI_ERR_ARG;
     int rc = ctx_begin(ctx);
     if (rc) return rc;
+    UnitState *unit = ctx_unit(ctx);   // (one look-up a call: the limits and the split it records)
+    UnitSplit *split = &unit->split;
     lfdmi_mask_params mp;
     lfdmi_default_mask_params(&mp);
     if (params) mp = *params;
@@ -107,8 +110,10 @@ extern "C" int lfdmi_mask_trails(lfdmi_ctx *ctx, void *frames, int dtype, int n,
 
     // chunks of jobs: the list of a chunk holds at most MSK_LIST_MAX pairs, what a chunk stages at most MSK_STAGE_BYTES
     const bool f_stage = fill && loc != LFDMI_DEVICE, m_stage = mask && mask_loc != LFDMI_DEVICE;
-    size_t CH = std::max<size_t>(1, MSK_LIST_MAX / ntiles);
-    if (f_stage || m_stage) CH = std::min(CH, std::max<size_t>(1, MSK_STAGE_BYTES / ((f_stage ? FB : 0) + (m_stage ? N : 0))));
+    size_t CH = std::max<size_t>(1, unit->limit_of(LIM_LIST_PAIRS, MSK_LIST_MAX) / ntiles);
+    if (f_stage || m_stage)
+        CH = std::min(CH, std::max<size_t>(1, unit->limit_of(LIM_STAGE_BYTES, MSK_STAGE_BYTES) / ((f_stage ? FB : 0) + (m_stage ? N : 0))));
+    const size_t walk_max = unit->limit_of(LIM_RENDER_BLOCKS, MSK_RENDER_BLOCKS);
     // (a job's staging slot is its index modulo CH; CH is clamped to the number of jobs below, which changes no slot: the clamp
     // only applies when there are fewer jobs than CH, where the modulo does nothing)
     std::vector<MaskJob> hj;
@@ -165,11 +170,12 @@ extern "C" int lfdmi_mask_trails(lfdmi_ctx *ctx, void *frames, int dtype, int n,
             }
             if (m_stage && mp.clear) UHIP(hipMemsetAsync(d_mbuf, 0, c * N, st));
             UHIP(hipMemsetAsync(d_count, 0, sizeof(int), st));
-            const size_t pairs = c * ntiles;
+            const size_t pairs = c * ntiles, walk = std::min(pairs, walk_max);
+            split->chunks++;
+            split->grid = std::max<int64_t>(split->grid, (int64_t)walk);
             k_mask_cull<<<(unsigned)((pairs + MSK_THREADS - 1) / MSK_THREADS), MSK_THREADS, 0, st>>>(d_job + j0, (int)c, d_seg, p, d_list, d_count);
             ULAUNCH("k_mask_cull");
-            k_mask_render<<<(unsigned)std::min<size_t>(pairs, MSK_RENDER_BLOCKS), MSK_THREADS, 0, st>>>(fbase, mbase, d_job + j0, d_seg, p, d_list,
-                                                                                                    d_count, d_cnt, d_jc + j0);
+            k_mask_render<<<(unsigned)walk, MSK_THREADS, 0, st>>>(fbase, mbase, d_job + j0, d_seg, p, d_list, d_count, d_cnt, d_jc + j0);
             ULAUNCH("k_mask_render");
             for (size_t k = 0; k < c; k++) {
                 const size_t f = (size_t)jframe[j0 + k];

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../unit.h"
+#include "../limits/limits.h"
 #include "k_stack.h"
 
 #define STK_STAGE_BYTES (1ull << 30)   // device staging of host frames at a time
@@ -186,6 +187,8 @@ extern "C" int lfdmi_stack_profiles(lfdmi_ctx *ctx, const void *frames, int dtyp
     if (!ctx) return LFDMI_ERR_ARG;
     int rc = ctx_begin(ctx);
     if (rc) return rc;
+    UnitState *unit = ctx_unit(ctx);   // (one look-up a call: the limits and the split it records)
+    UnitSplit *split = &unit->split;
     if ((rc = unit_dtype(ctx, "lfdmi_stack_profiles", dtype)) || (rc = unit_loc(ctx, loc))) return rc;
     if (n < 0 || n_seg < 0 || h < 1 || w < 1 || h > 65536 || w > 65536)
         return ctx_fail(ctx, LFDMI_ERR_ARG, "lfdmi_stack_profiles: n, n_seg >= 0, h and w 1 .. 65536");
@@ -215,7 +218,7 @@ extern "C" int lfdmi_stack_profiles(lfdmi_ctx *ctx, const void *frames, int dtyp
         std::vector<char> used(n, 0);
         for (int i = 0; i < n_seg; i++)
             if (sg[i].status == LFDMI_STACK_OK) used[segs[i].frame] = 1;
-        const size_t per = in_dev ? (size_t)n : std::max<size_t>(1, STK_STAGE_BYTES / FB);
+        const size_t per = in_dev ? (size_t)n : std::max<size_t>(1, unit->limit_of(LIM_STAGE_BYTES, STK_STAGE_BYTES) / FB);
         for (int f = 0; f < n; f++) {
             if (!used[f]) continue;
             if (gframes.empty() || gframes.back().size() >= per) gframes.emplace_back();
@@ -230,7 +233,7 @@ extern "C" int lfdmi_stack_profiles(lfdmi_ctx *ctx, const void *frames, int dtyp
     dp.h = h; dp.w = w; dp.be = dtype == LFDMI_F32_BE; dp.K = K; dp.nb = nb; dp.clip = q.clip;
     dp.inv = 1.0 / q.step; dp.kc = (double)K + 0.5;
     const double reach = q.prof_half + q.step / 2.0;
-    const size_t items_max = std::max<size_t>(1, STK_PART_BYTES / (8 * (size_t)nb));
+    const size_t items_max = std::max<size_t>(1, unit->limit_of(LIM_STACK_PART_BYTES, STK_PART_BYTES) / (8 * (size_t)nb));
 
     hipStream_t st = ctx_stream(ctx);
     for (size_t gi = 0; gi < gframes.size(); gi++) {
@@ -238,6 +241,7 @@ extern "C" int lfdmi_stack_profiles(lfdmi_ctx *ctx, const void *frames, int dtyp
         for (int i = 0; i < n_seg; i++)
             if (sg[i].status == LFDMI_STACK_OK && group_of[segs[i].frame] == (int)gi) active.push_back(i);
         if (active.empty()) continue;
+        split->chunks++;
         // the largest launch of this group: whole segments up to items_max blocks
         size_t cap_items = 0;
         for (int i : active) cap_items = std::max<size_t>(cap_items, (size_t)((sg[i].a_last >> 5) - (sg[i].a_first >> 5) + 2));
@@ -328,6 +332,7 @@ extern "C" int lfdmi_stack_profiles(lfdmi_ctx *ctx, const void *frames, int dtyp
                 }
                 k_stack_combine<<<(unsigned)hv.size(), STK_THREADS, 0, st>>>(d_half + 2 * e0, nb, d_ps, d_pc, d_sum, d_cnt);
                 ULAUNCH("k_stack_combine");
+                if (split->chunks == 1 && pass == 0) split->launches++;
                 e0 = e;
             }
             UHIP(hipMemcpyAsync(pA.data(), d_sum, na * row2 * sizeof(float), hipMemcpyDeviceToHost, st));

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../unit.h"
+#include "../limits/limits.h"
 #include "k_stars.h"
 
 #define STARS_STAGE_BYTES (1ull << 30)   // device staging of host frames at a time
@@ -40,6 +41,8 @@ extern "C" int lfdmi_find_stars(lfdmi_ctx *ctx, const void *frames, int dtype, i
     if (!ctx) return LFDMI_ERR_ARG;
     int rc = ctx_begin(ctx);
     if (rc) return rc;
+    UnitState *unit = ctx_unit(ctx);   // (one look-up a call: the limits and the split it records)
+    UnitSplit *split = &unit->split;
     if ((rc = unit_dtype(ctx, "lfdmi_find_stars", dtype)) || (rc = unit_loc(ctx, loc))) return rc;
     if (out_loc != LFDMI_HOST && out_loc != LFDMI_DEVICE && out_loc != LFDMI_HOST_PINNED) return ctx_fail(ctx, LFDMI_ERR_ARG, "bad out_loc");
     if (n < 0 || h < 1 || w < 1 || h > 65536 || w > 65536) return ctx_fail(ctx, LFDMI_ERR_ARG, "lfdmi_find_stars: n >= 0, h and w 1 .. 65536");
@@ -65,13 +68,15 @@ extern "C" int lfdmi_find_stars(lfdmi_ctx *ctx, const void *frames, int dtype, i
         hE[i] = (float)(q.k_edge * 3.0 * (double)sg[i]);
     }
     size_t chunk = STARS_MAX_CHUNK;
-    if (!in_dev) chunk = std::min(chunk, std::max<size_t>(1, STARS_STAGE_BYTES / FB));
-    if (!out_dev) chunk = std::min(chunk, std::max<size_t>(1, STARS_REC_BYTES / ((size_t)q.max_obj * sizeof(StarRec))));
+    if (!in_dev) chunk = std::min(chunk, std::max<size_t>(1, unit->limit_of(LIM_STAGE_BYTES, STARS_STAGE_BYTES) / FB));
+    if (!out_dev)
+        chunk = std::min(chunk, std::max<size_t>(1, unit->limit_of(LIM_STARS_REC_BYTES, STARS_REC_BYTES) / ((size_t)q.max_obj * sizeof(StarRec))));
 
     hipStream_t st = ctx_stream(ctx);
     std::vector<StarsFrameDev> hrec(n);   // (the queued copies write it: declared ahead of the pools, which wait before they go)
     for (int c0 = 0; c0 < n; c0 += (int)chunk) {
         const int nf = std::min<int>((int)chunk, n - c0);
+        split->chunks++;
         Pool pool(st);
         uint32_t *d_buf = nullptr;
         str_u64 *d_bits = nullptr;

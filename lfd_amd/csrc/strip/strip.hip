@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../unit.h"
+#include "../limits/limits.h"
 #include "k_strip.h"
 #include "k_strip_geo.h"
 
@@ -122,6 +123,8 @@ extern "C" int lfdmi_trail_strips(lfdmi_ctx *ctx, const void *frames, int dtype,
     if (!ctx) return LFDMI_ERR_ARG;
     int rc = ctx_begin(ctx);
     if (rc) return rc;
+    UnitState *unit = ctx_unit(ctx);   // (one look-up a call: the limits and the split it records)
+    UnitSplit *split = &unit->split;
     if ((rc = unit_dtype(ctx, "lfdmi_trail_strips", dtype)) || (rc = unit_loc(ctx, loc))) return rc;
     if (n < 0 || n_seg < 0 || h < 1 || w < 1 || h > 65536 || w > 65536 || (double)h * w > 1e9)
         return ctx_fail(ctx, LFDMI_ERR_ARG, "lfdmi_trail_strips: n, n_seg >= 0, h and w 1 .. 65536, h * w at most 1e9");
@@ -169,14 +172,14 @@ extern "C" int lfdmi_trail_strips(lfdmi_ctx *ctx, const void *frames, int dtype,
     }
     // batches of segments [k0, k1): at most STRIP_CELL_BYTES of cells on the device; StripSeg.base counts from the batch's first cell,
     // first[k] from the call's
-    const size_t cell_max = STRIP_CELL_BYTES / sizeof(StripCell);
+    const size_t cell_max = unit->limit_of(LIM_CELL_BYTES, STRIP_CELL_BYTES) / sizeof(StripCell);
     std::vector<size_t> first(ng + 1, 0);
     std::vector<int> bstart(1, 0);
     {
         size_t in_batch = 0;
         for (int k = 0; k < ng; k++) {
-            const size_t c = (size_t)hs[k].n_sec * hs[k].n_off;   // (at most 1024 * 129: one segment always fits)
-            if (in_batch + c > cell_max) { bstart.push_back(k); in_batch = 0; }
+            const size_t c = (size_t)hs[k].n_sec * hs[k].n_off;   // (at most 1024 * 129: below the compiled limit; a batch's first always fits)
+            if (in_batch > 0 && in_batch + c > cell_max) { bstart.push_back(k); in_batch = 0; }
             hs[k].base = (int64_t)in_batch;
             in_batch += c;
             first[k + 1] = first[k] + c;
@@ -197,8 +200,9 @@ extern "C" int lfdmi_trail_strips(lfdmi_ctx *ctx, const void *frames, int dtype,
 
     // chunks of jobs: the list of a chunk holds at most STRIP_LIST_MAX pairs, what a chunk stages at most STRIP_STAGE_BYTES
     const bool stage = loc != LFDMI_DEVICE, m_stage = stage && mask;
-    size_t CH = std::max<size_t>(1, STRIP_LIST_MAX / ntiles);
-    if (stage) CH = std::min(CH, std::max<size_t>(1, STRIP_STAGE_BYTES / (FB + (m_stage ? N : 0))));
+    size_t CH = std::max<size_t>(1, unit->limit_of(LIM_LIST_PAIRS, STRIP_LIST_MAX) / ntiles);
+    if (stage) CH = std::min(CH, std::max<size_t>(1, unit->limit_of(LIM_STAGE_BYTES, STRIP_STAGE_BYTES) / (FB + (m_stage ? N : 0))));
+    const size_t walk_max = unit->limit_of(LIM_RENDER_BLOCKS, STRIP_RENDER_BLOCKS);
     // the jobs of every batch in a row: a frame whose segments two batches share is a job of both
     std::vector<StripJob> hj;
     std::vector<int> jframe;
@@ -252,6 +256,7 @@ extern "C" int lfdmi_trail_strips(lfdmi_ctx *ctx, const void *frames, int dtype,
         for (size_t b = 0; b + 1 < bstart.size(); b++) {
             const size_t bc = first[bstart[b + 1]] - first[bstart[b]];
             UHIP(hipMemsetAsync(d_cell, 0, bc * sizeof(StripCell), st));
+            split->batches++;
             for (size_t j0 = jstart[b]; j0 < jstart[b + 1]; j0 += CH) {
                 const size_t c = std::min(CH, jstart[b + 1] - j0);
                 for (size_t k = 0; k < c; k++) {
@@ -260,12 +265,13 @@ extern "C" int lfdmi_trail_strips(lfdmi_ctx *ctx, const void *frames, int dtype,
                     if (m_stage) UHIP(hipMemcpyAsync(d_mbuf + k * N, mask + f * N, N, hipMemcpyHostToDevice, st));
                 }
                 UHIP(hipMemsetAsync(d_count, 0, sizeof(int), st));
-                const size_t pairs = c * ntiles;
+                const size_t pairs = c * ntiles, walk = std::min(pairs, walk_max);
+                split->chunks++;
+                split->grid = std::max<int64_t>(split->grid, (int64_t)walk);
                 k_strip_cull<<<(unsigned)((pairs + STRIP_THREADS - 1) / STRIP_THREADS), STRIP_THREADS, 0, st>>>(d_job + j0, (int)c, d_seg, p, d_list,
                                                                                                               d_count);
                 ULAUNCH("k_strip_cull");
-                k_strip_render<<<(unsigned)std::min<size_t>(pairs, STRIP_RENDER_BLOCKS), STRIP_THREADS, 0, st>>>(fbase, mbase, d_job + j0, d_seg, p,
-                                                                                                              d_list, d_count, d_cell);
+                k_strip_render<<<(unsigned)walk, STRIP_THREADS, 0, st>>>(fbase, mbase, d_job + j0, d_seg, p, d_list, d_count, d_cell);
                 ULAUNCH("k_strip_render");
             }
             UHIP(hipMemcpyAsync(hc.data() + first[bstart[b]], d_cell, bc * sizeof(StripCell), hipMemcpyDeviceToHost, st));

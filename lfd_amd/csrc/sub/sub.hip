@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../unit.h"
+#include "../limits/limits.h"
 #include "k_sub.h"
 #include "../strip/k_strip_geo.h"
 
@@ -70,6 +71,8 @@ extern "C" int lfdmi_subtract_trails(lfdmi_ctx *ctx, void *frames, int dtype, in
     if (!ctx) return LFDMI_ERR_ARG;
     int rc = ctx_begin(ctx);
     if (rc) return rc;
+    UnitState *unit = ctx_unit(ctx);   // (one look-up a call: the limits and the split it records)
+    UnitSplit *split = &unit->split;
     if ((rc = unit_dtype(ctx, "lfdmi_subtract_trails", dtype)) || (rc = unit_loc(ctx, loc))) return rc;
     lfdmi_sub_params q;
     if (pp) q = *pp; else lfdmi_default_sub_params(&q);
@@ -130,9 +133,10 @@ extern "C" int lfdmi_subtract_trails(lfdmi_ctx *ctx, void *frames, int dtype, in
     // SUB_LIST_MAX pairs, what it stages at most SUB_STAGE_BYTES, its cells at most SUB_CELL_BYTES (a single job may exceed that).
     // StripSeg.base counts from the chunk's first cell, first[k] from the call's.
     const bool stage = loc != LFDMI_DEVICE, m_stage = stage && mask;
-    size_t CH = std::max<size_t>(1, SUB_LIST_MAX / ntiles);
-    if (stage) CH = std::min(CH, std::max<size_t>(1, SUB_STAGE_BYTES / (FB + (m_stage ? N : 0))));
-    const size_t cell_max = SUB_CELL_BYTES / sizeof(StripCell);
+    size_t CH = std::max<size_t>(1, unit->limit_of(LIM_LIST_PAIRS, SUB_LIST_MAX) / ntiles);
+    if (stage) CH = std::min(CH, std::max<size_t>(1, unit->limit_of(LIM_STAGE_BYTES, SUB_STAGE_BYTES) / (FB + (m_stage ? N : 0))));
+    const size_t cell_max = unit->limit_of(LIM_CELL_BYTES, SUB_CELL_BYTES) / sizeof(StripCell);
+    const size_t walk_max = unit->limit_of(LIM_RENDER_BLOCKS, SUB_RENDER_BLOCKS);
     std::vector<StripJob> hj;
     std::vector<int> jframe;
     std::vector<size_t> cstart(1, 0), first(ng + 1, 0);
@@ -218,7 +222,9 @@ extern "C" int lfdmi_subtract_trails(lfdmi_ctx *ctx, void *frames, int dtype, in
             UHIP(hipMemsetAsync(d_cell, 0, cc * sizeof(StripCell), st));
             UHIP(hipMemsetAsync(d_count, 0, sizeof(int), st));
             const size_t pairs = c * ntiles;
-            const unsigned walk = (unsigned)std::min<size_t>(pairs, SUB_RENDER_BLOCKS);
+            const unsigned walk = (unsigned)std::min(pairs, walk_max);
+            split->chunks++;
+            split->grid = std::max<int64_t>(split->grid, (int64_t)walk);
             k_strip_cull<<<(unsigned)((pairs + STRIP_THREADS - 1) / STRIP_THREADS), STRIP_THREADS, 0, st>>>(d_job + j0, (int)c, d_seg, p, d_list, d_count);
             ULAUNCH("k_strip_cull");
             k_strip_render<<<walk, STRIP_THREADS, 0, st>>>(fbase, mbase, d_job + j0, d_seg, p, d_list, d_count, d_cell);
