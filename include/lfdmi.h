@@ -366,8 +366,9 @@ int lfdmi_get_stage(lfdmi_ctx *ctx, int slot, int which, int h, int w, uint8_t *
  * (LFDMI_COUNTERS int32 values per slot; order: keys, row slots, rectangles, equ list entries, box
  * list entries (pixel chunks the Hough kernels vote with), equ peaks, box peaks, overflow flag,
  * detection, tall keys, candidate words, background words, candidate runs, background runs, medium
- * keys, non-zero pixels of equ, of box_img, active 64 x 16 tiles, entries of the second (longer-chunk) Hough lists of equ / box) */
-#define LFDMI_COUNTERS 20
+ * keys, non-zero pixels of equ, of box_img, active 64 x 16 tiles, entries of the second (longer-chunk) Hough lists of equ / box,
+ * holes the per-frame contour kernel met, holes among them it gave no key (their borders cannot pass the rectangle filter)) */
+#define LFDMI_COUNTERS 22
 int lfdmi_get_counters(lfdmi_ctx *ctx, int slot0, int n, int32_t *dst);
 /* per-kernel timing for bench.py's roofline entry: when enabled, every kernel launch is
  * bracketed by HIP events on the launch stream; lfdmi_get_timing returns, per timing slot,

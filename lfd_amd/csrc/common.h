@@ -27,7 +27,9 @@ enum {
     C_NTILES = 17,   // 64 x 16 tiles of the pass image with anything in reach (work list of k_dilate_canny_t)
     C_NPIXB_EQU = 18, // entries of equ's class-B list (longer chunks for the angle slabs away from the horizontal, see k_pixlist)
     C_NPIXB_BOX = 19,
-    C_COUNT = 20
+    C_NHOLES = 20,   // holes k_frame_contours met (frames the general kernels take: 0)
+    C_NHOLES_PRUNED = 21, // of those, holes whose border the rectangle filter is certain to reject: no key, no slots (hole_prune.h)
+    C_COUNT = 22
 };
 
 #define LFD_WQ(w) (((w) + 63) >> 6)

@@ -21,6 +21,7 @@
 #pragma once
 #include "k_ccl.h"
 #include "k_rect.h"
+#include "hole_prune.h"
 
 // perm[0 .. na) = the slots with active[slot] != 0 in ascending order, perm[na .. n) = the others: kernels whose workgroup ->
 // frame mapping decides which XCD a frame works on (one workgroup per frame; the tile kernel's frame = f(block % 8)) index the
@@ -518,10 +519,14 @@ struct ExtItem { int idx, id0, sbc, sbu, sbd; u64 e, ep, en, c, cp, u, up, d, dp
 //  (3) per-row extremes of every key -- k_extremes;
 // with the background labels and flags read from LDS in (2) and (3) and the key / slot counters
 // kept in LDS.  Same tables, same values (the order of the keys is as arbitrary as before).
+// hole_prune: a hole whose border the rectangle filter (minLen, lwTresh) is certain to reject (hole_prune.h) gets no key, no
+// row slots and no extremes: the hole-extent phase also gathers the hole's pixel count and column span for that test, in the
+// part of the LDS label table behind the labels (a frame whose runs leave no room there keeps every hole).  Counted per frame
+// in C_NHOLES / C_NHOLES_PRUNED.  The general kernels (k_keys / k_extremes) make every hole's key as before.
 __global__ void __launch_bounds__(FRAME_THREADS)
 k_frame_contours(RunTabs t, const int *wl_fg, const int *wl_bg, int *counters, int4 *keys, int *bigkeys, int *medkeys, int2 *rowext,
                  int2 *rsa, int h, int w, int key_cap, int slot_cap, int lds_cap, const int *active, int *fallback, int *pass_flags, long long *prof,
-                 int lds_n, const int *perm, int dbg, const int *fg_keys) {
+                 int lds_n, const int *perm, int dbg, const int *fg_keys, int hole_prune, double minLen, double lwTresh) {
     // fg_keys[frame] != 0: k_frame_fg has made the outer-border keys, their row slots and extremes already (counters C_NKEYS /
     // C_NSLOTS / C_NBIG / C_NMED hold its totals): only the hole borders are left to do here
     // developer profile (prof != nullptr): wall-clock ticks (10 ns) at the end of every phase, per frame
@@ -566,16 +571,34 @@ k_frame_contours(RunTabs t, const int *wl_fg, const int *wl_bg, int *counters, i
     int *XSg = t.PAb + ro; // scratch until the hole keys are made: PAb[root] = first column of the hole
     const u64 *fb = edge + fo;
     const int *sb = scanb + fo, *wl = wl_bg + fo;
-    __shared__ int c_slots, c_keys, c_big, c_med, c_ovf, c_hovf;
-    // holes of the frame, keyed by their root run: (slot of border row 0 minus that row, surrounding component)
+    __shared__ int c_slots, c_keys, c_big, c_med, c_ovf, c_hovf, c_holes, c_pruned;
+    // holes of the frame, keyed by their root run (entered when the root is found): (slot of border row 0 minus that row,
+    // surrounding component)
     __shared__ int hkey[FRAME_HOLECAP];
     __shared__ int2 hval[FRAME_HOLECAP];
+    // rows that belong to the border of a hole with a key: the extremes phase only has hole slots to update there
+    __shared__ unsigned rowm[256]; // (a frame has at most 8 191 rows)
+    // per entry of the hole table, while the holes are measured (the slots' LDS copy takes the space afterwards): pixels, first
+    // and last column of the hole
+    const int nrun2 = (nrun + 1) & ~1;
+    const bool prune = hole_prune != 0 && nrun2 + 3 * FRAME_HOLECAP <= lds_n;
+    int *HN = sm_frame + nrun2, *HX0 = HN + FRAME_HOLECAP, *HX1 = HX0 + FRAME_HOLECAP;
+    auto hole_slot = [&](int id) -> int { // the hole's entry in the table, or -1 (it found no place: c_hovf)
+        unsigned hs = ((unsigned)id * 2654435761u) >> 22; // 10 bits
+        for (int probe = 0; probe < 16; probe++, hs = (hs + 1) & (FRAME_HOLECAP - 1)) {
+            const int kk = hkey[hs];
+            if (kk == id) return (int)hs;
+            if (kk == -1) break;
+        }
+        return -1;
+    };
     if (threadIdx.x == 0) {
         const int *cnt = counters + g * C_COUNT;
         c_slots = fgk ? cnt[C_NSLOTS] : 0; c_keys = fgk ? cnt[C_NKEYS] : 0; c_big = fgk ? cnt[C_NBIG] : 0; c_med = fgk ? cnt[C_NMED] : 0;
-        c_ovf = 0; c_hovf = 0;
+        c_ovf = 0; c_hovf = 0; c_holes = 0; c_pruned = 0;
     }
     for (int i = threadIdx.x; i < FRAME_HOLECAP; i += FRAME_THREADS) hkey[i] = -1;
+    for (int i = threadIdx.x; i < 256; i += FRAME_THREADS) rowm[i] = 0u;
     for (int i = threadIdx.x; i < (nrun + 31) / 32; i += FRAME_THREADS) { FL[i] = 0u; HB[i] = 0u; HL[i] = 0u; HR[i] = 0u; }
     for (int i = threadIdx.x; i < nrun; i += FRAME_THREADS) L[i] = i;
     __syncthreads();
@@ -707,6 +730,14 @@ k_frame_contours(RunTabs t, const int *wl_fg, const int *wl_bg, int *counters, i
                 XSg[id] = (q << 6) + hole_bit(s, k); // column of the hole's raster-first pixel
                 ROWg[id] = y;                        // row / last row: of a hole's root only (a few hundred per frame, not every run)
                 YMg[id] = y;
+                unsigned hs = ((unsigned)id * 2654435761u) >> 22; // 10 bits
+                bool put = false;
+                for (int probe = 0; probe < 16 && !put; probe++, hs = (hs + 1) & (FRAME_HOLECAP - 1))
+                    if (atomicCAS(&hkey[hs], -1, id) == -1) {
+                        if (prune) { HN[hs] = 0; HX0[hs] = 0x7fffffff; HX1[hs] = -1; }
+                        put = true;
+                    }
+                if (!put) c_hovf = 1; // (such a hole is looked up in the global tables, and is not measured: it keeps its key)
             }
         }
     };
@@ -714,12 +745,22 @@ k_frame_contours(RunTabs t, const int *wl_fg, const int *wl_bg, int *counters, i
         int y = t.idx / wq, q = t.idx - y * wq;
         u64 z = ~t.c & valid_mask(q, w);
         u64 s = z & ~((z << 1) | ((~t.cp) >> 63));
-        int n = __popcll(s);
-        for (int k = 0; k < n; k++) {
-            int id = t.id0 + k;
-            if (!((HL[id >> 5] >> (id & 31)) & 1u) || ((HB[id >> 5] >> (id & 31)) & 1u)) continue; // not a hole's run, or one with a run below
+        for (int id = t.id0; s; id++) {
+            const int b = __ffsll((long long)s) - 1;
+            s &= s - 1;
+            if (!((HL[id >> 5] >> (id & 31)) & 1u)) continue; // not a hole's run
             int root = L[id];
-            if (root != id) atomicMax(&YMg[root], y);
+            const int hs = prune ? hole_slot(root) : -1;
+            if (hs >= 0) { // pixels and column span of the hole: every run of it, once, where it starts
+                const u64 inv = ~(z >> b);
+                const int len = inv ? (__ffsll((long long)inv) - 1) : 64;
+                const int xs = (q << 6) + b;
+                const int xe = (b + len == 64 && q + 1 < wq) ? run_end(fb + (size_t)y * wq, xs, 0, w) : xs + len - 1;
+                atomicAdd(&HN[hs], xe - xs + 1);
+                atomicMin(&HX0[hs], xs);
+                atomicMax(&HX1[hs], xe);
+            }
+            if (root != id && !((HB[id >> 5] >> (id & 31)) & 1u)) atomicMax(&YMg[root], y); // (a run with a run below is not the last row)
         }
     };
 #pragma unroll
@@ -806,25 +847,32 @@ k_frame_contours(RunTabs t, const int *wl_fg, const int *wl_bg, int *counters, i
     // 32 background runs of the root bitset: only actual holes cost memory round trips.
     for (int wd = threadIdx.x; wd < (nrun + 31) / 32; wd += FRAME_THREADS) {
         unsigned bits = HR[wd];
+        int seen = 0, pruned = 0;
         while (bits) {
             int id = (wd << 5) + __ffs((int)bits) - 1;
             bits &= bits - 1;
             int y = ROWg[id], x = XSg[id];
             int ymax = __hip_atomic_load(&YMg[id], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            int parent = Lfg[run_id(sf, cb, y - 1, x, 1, wq, w)];
-            int base = new_key(id, y - 1, ymax - y + 3, true);
+            // a border the rectangle filter is certain to reject: no key, no slots; the extremes skip the hole (hval.x == INT_MIN)
+            const int hs = hole_slot(id);
+            const bool rej = prune && hs >= 0 && hole_border_rejected(HN[hs], HX1[hs] - HX0[hs] + 2, ymax - y + 2, minLen, lwTresh);
+            seen++;
+            pruned += rej ? 1 : 0;
+            int parent = rej ? -1 : Lfg[run_id(sf, cb, y - 1, x, 1, wq, w)];
+            int base = rej ? -1 : new_key(id, y - 1, ymax - y + 3, true);
             SBbg[id] = base;
             PAbg[id] = parent; // (overwrites the scratch column)
             // border row yy of this hole lives in slot base + (yy - (y - 1))
-            unsigned hs = ((unsigned)id * 2654435761u) >> 22; // 10 bits
-            bool put = false;
-            for (int probe = 0; probe < 16 && !put; probe++, hs = (hs + 1) & (FRAME_HOLECAP - 1))
-                if (atomicCAS(&hkey[hs], -1, id) == -1) {
-                    hval[hs] = make_int2(base >= 0 ? base - (y - 1) : INT_MIN, parent);
-                    put = true;
+            if (hs >= 0) hval[hs] = make_int2(base >= 0 ? base - (y - 1) : INT_MIN, parent);
+            if (base >= 0)
+                for (int y0 = y - 1; y0 <= ymax + 1;) { // its border rows, a word of the row mask at a time
+                    const int y1 = min(ymax + 1, y0 | 31), nb = y1 - y0 + 1;
+                    atomicOr(&rowm[y0 >> 5], (nb == 32 ? ~0u : ((1u << nb) - 1u)) << (y0 & 31));
+                    y0 = y1 + 1;
                 }
-            if (!put) c_hovf = 1;
         }
+        if (seen) atomicAdd(&c_holes, seen);
+        if (pruned) atomicAdd(&c_pruned, pruned);
     }
     __syncthreads(); // rsa, the hole table, SBb / PAb of this frame are written
     // fgk: which holes have a component INSIDE them.  The edge pixels next to a hole B belong to the component around it (A) or
@@ -908,9 +956,13 @@ k_frame_contours(RunTabs t, const int *wl_fg, const int *wl_bg, int *counters, i
     frame_pipeline<ExtItem>(
         wlf, nwf,
         [&](int idx) {
-            ExtItem k;
+            ExtItem k = {};
             int y = idx / wq, q = idx - y * wq;
             k.idx = idx;
+            // fgk: only hole slots are left to update, and a stretch of row y can only touch the border of a hole in its row y:
+            // where no hole with a key has one (after the pruning: most rows of a sky frame; the phase's median fell from 45 / 91
+            // to 5 / 8 us, bright / dim, but a frame with a trail's ring keeps the rows the ring spans) the word is not even loaded
+            if (fgk && !((rowm[y >> 5] >> (y & 31)) & 1u)) return k; // (e = 0: no stretch)
             word_pair(fb, idx, q > 0, ~0ull, k.ep, k.e); // "edge" left of column 0: no background run continues from there
             k.en = q + 1 < wq ? fb[idx + 1] : 0ull;
             k.c = 0; k.cp = 0; k.id0 = 0;
@@ -1003,6 +1055,8 @@ k_frame_contours(RunTabs t, const int *wl_fg, const int *wl_bg, int *counters, i
         cnt[C_NKEYS] = c_keys < key_cap ? c_keys : key_cap;
         cnt[C_NBIG] = c_big;
         cnt[C_NMED] = c_med;
+        cnt[C_NHOLES] = c_holes;
+        cnt[C_NHOLES_PRUNED] = c_pruned;
         if (c_ovf) cnt[C_OVERFLOW] = 1;
     }
 }

@@ -241,6 +241,7 @@ struct lfdmi_ctx {
     bool general_seen = false, general_on = true;
     bool frame_ccl = true;             // per-frame LDS connectivity kernels (k_frame.h)
     int frame_runcap = FRAME_RUNCAP;   // runs per frame they take (LFDMI_FRAME_RUNCAP lowers it: tests of the fallback path)
+    bool hole_prune = true;            // LFDMI_HOLE_PRUNE=0: k_frame_contours makes a key for every hole, also those the rectangle filter must reject
     int frame_dbg = 0;                 // LFDMI_FRAME_DBG: developer attribution switches of k_frame_contours (wrong results)
     int frame_lds = FRAME_RUNCAP;      // entries of their LDS label table (LFDMI_FRAME_LDS: a smaller table leaves LDS to other kernels
                                        // on the CU; frames with more runs take the general kernels)
@@ -404,6 +405,7 @@ static int create_impl(int device, int max_h, int max_w, int max_inflight, const
     if (const char *e = getenv("LFDMI_VOTE_AW")) { int v = atoi(e); if (*e && v >= 0 && v <= 6) ctx->vote_aw = v; }
     if (const char *e = getenv("LFDMI_PE_ROWS")) { int v = atoi(e); if (v >= 2 && v <= 64) ctx->pe_rows = v; }
     if (const char *e = getenv("LFDMI_FRAME_DBG")) ctx->frame_dbg = atoi(e);
+    if (const char *e = getenv("LFDMI_HOLE_PRUNE")) ctx->hole_prune = atoi(e) != 0;
     if (const char *e = getenv("LFDMI_FRAME_RUNCAP")) { int v = atoi(e); if (v >= 0 && v < FRAME_RUNCAP) ctx->frame_runcap = v; }
     if (const char *e = getenv("LFDMI_FRAME_LDS")) {
         int v = atoi(e);
@@ -1220,7 +1222,8 @@ static int run_rects(lfdmi_ctx *ctx, int nc, int h, int w, int mode, int method,
         k_frame_contours<<<nc, FRAME_THREADS, lds, ctx->stream>>>(rt, ctx->wl_fg, ctx->wl_bg, ctx->counters, ctx->keys, ctx->bigkeys,
                                                                   ctx->medkeys, ctx->rowext, ctx->rsa, h, w, ctx->key_cap, ctx->slot_cap,
                                                                   ctx->frame_runcap, active, ctx->fb_bg, ctx->pass_flags, ctx->dc_profile ? nullptr : ctx->prof,
-                                                                  ctx->frame_lds, active ? ctx->perm_cur : nullptr, ctx->frame_dbg, ctx->fg_keys);
+                                                                  ctx->frame_lds, active ? ctx->perm_cur : nullptr, ctx->frame_dbg, ctx->fg_keys,
+                                                                  ctx->hole_prune ? 1 : 0, minLen, lwTresh);
         KCHK("k_frame_contours");
         gen = ctx->fb_bg;
     }
