@@ -1360,8 +1360,33 @@ int lfdmi_radon_search_wide(lfdmi_ctx *ctx, lfdmi_radon *radon, const void *fram
  *    record with found = 1 has its segment (steps 12, 16), which at the default thresholds a null record should never be.
  *    With the null peaks snr_0 .. snr_K-1 of a frame, a line of that frame with score x has the false-alarm estimate
  *    (1 + #{snr_r >= x}) / (K + 1), which is never 0, and margin * max snr_r is the rule the default thresholds follow.
- *    Not covered: a null that keeps the noise's spatial correlation, sign-flip or row-shift nulls, nulls of peel rounds after
- *    the first; no default threshold changes on these numbers. */
+ *    Not covered: a null that keeps two-dimensional noise correlation, peel-round nulls for schemes that move pixels; no
+ *    default threshold changes on these numbers.
+ *
+ * lfdmi_radon_null_scheme makes the null frame X' in other ways than the scramble, which keeps the frame's mean in every line
+ * (a trail's or a star's leftover flux lifts the whole null), spreads the invalid pixels evenly (the frame's blots and bleed
+ * columns cut particular lines short) and destroys the noise's correlation.  tests/radon_null_schemes_ref.py restates steps
+ * 21 and 22.  With u(i) = fmix32(fmix32(i * 0x9E3779B1 + lo32(k)) ^ hi32(k)), step 18's u for an index i and step 17's key k:
+ * 21. Schemes.  X is the buffer, r and c its row and column before step 1's flip.
+ *    LFDMI_RADON_NULL_SCRAMBLE: steps 18 - 19; with n_peel = 0 the records are lfdmi_radon_null's bit for bit.
+ *    LFDMI_RADON_NULL_SIGNFLIP: X'[i], i = r W + c, is X[i] with the value's sign bit inverted where u(i) >> 31 is 1 (of a
+ *    big-endian frame: the sign bit of the value after step 1's swap); every other bit is kept.  Step 1's validity ignores
+ *    the sign (finite, not +-0, |x| <= clip), so M of X' is M of X exactly: every line keeps its N, and every pixel its
+ *    place.  What it does not do: it removes the frame's mean from the null, so a badly subtracted sky lowers the null and
+ *    does not lower the search; and it does not keep the sign structure of correlated noise.
+ *    LFDMI_RADON_NULL_ROWSHIFT: o(r) = (uint32)(((uint64)u(r) * W) >> 32) < W and X'[r][c] = X[r][(c + o(r)) mod W]: a
+ *    permutation inside every row, which keeps the frame's values, its mean, every row's content and the correlation along
+ *    rows.  What it does not do: it leaves a trail along the rows whole.
+ *    LFDMI_RADON_NULL_COLSHIFT: the same along columns, o(c) = (uint32)(((uint64)u(c) * H) >> 32) < H and
+ *    X'[r][c] = X[(r + o(c)) mod H][c].  What it does not do: it leaves a trail along the columns whole.  For a found line of
+ *    orientation q, COLSHIFT is the scheme for q = 0, 1, whose lines cross the columns, and ROWSHIFT for q = 2, 3.
+ * 22. Rounds.  Peel records are allowed only with SIGNFLIP, which keeps positions: under the other schemes the trail's pixels
+ *    are no longer under its band.  peel holds n * n_peel records, frame f's at peel[f * n_peel ..], n_peel = 0 ..
+ *    LFDMI_RADON_MAX_LINES.  V', M' are step 2's binning of X'.  Every record with width >= 1 has its band blotted out of V',
+ *    M' exactly as step 8 does it (width = 1) or step 16 (width = k, a power of two up to LFDMI_RADON_MAX_WIDTH), with
+ *    hw = ceil(peel_halfwidth / bin) of the kind's parameters; a record of width 0 is no line and is not looked at.  The
+ *    kind's search of step 20 then runs on the result (a found short or wide record has its segment on it).  The null of
+ *    round k of a frame is the call with that frame's lines 0 .. k-1. */
 enum { LFDMI_RADON_NULL_LINES = 0, LFDMI_RADON_NULL_SHORT = 1, LFDMI_RADON_NULL_WIDE = 2 };
 #define LFDMI_RADON_NULL_MAX 64
 /* The null records of n frames: frames, dtype, n, loc and sigma as in lfdmi_radon_search.  seeds: n uint64 (host); NULL: frame
@@ -1375,6 +1400,19 @@ enum { LFDMI_RADON_NULL_LINES = 0, LFDMI_RADON_NULL_SHORT = 1, LFDMI_RADON_NULL_
  * parameters out of range, runs on the context's stream and waits for it once, at its end. */
 int lfdmi_radon_null(lfdmi_ctx *ctx, lfdmi_radon *radon, const void *frames, int dtype, int n, int loc, const float *sigma,
                      const uint64_t *seeds, int K, int kind, const void *kind_params, void *records);
+enum { LFDMI_RADON_NULL_SCRAMBLE = 0, LFDMI_RADON_NULL_SIGNFLIP = 1, LFDMI_RADON_NULL_ROWSHIFT = 2, LFDMI_RADON_NULL_COLSHIFT = 3 };
+typedef struct { int32_t q, y0, s, width; } lfdmi_radon_peel;   /* width 0: no line in this place */
+/* lfdmi_radon_null with steps 21 and 22: everything up to kind_params as there, but that LINES takes NULL or an
+ * lfdmi_radon_lines_params (checked as lfdmi_radon_search_lines checks it; its peel_halfwidth is step 22's), and the peel_halfwidth
+ * of the short and wide parameters is used.  scheme: LFDMI_RADON_NULL_SCRAMBLE .. COLSHIFT.  peel: n * n_peel records (host), or
+ * NULL with n_peel = 0.  LFDMI_ERR_ARG, with nothing run and nothing written: scheme out of range; n_peel outside 0 ..
+ * LFDMI_RADON_MAX_LINES; n_peel > 0 with peel NULL or with a scheme other than SIGNFLIP; of a record, width not 0 or a power of
+ * two up to 16, and with width >= 1, q outside 0 .. 3, s outside 0 .. P-1 or y0 outside [-(P-1), R-1] of its orientation;
+ * everything lfdmi_radon_null refuses.  Slots, chunks, seeds, sigma, the allocations of the first call (with n_peel > 0 the
+ * second V, M set too), the refusal while calls are in flight and the single wait at the end are lfdmi_radon_null's. */
+int lfdmi_radon_null_scheme(lfdmi_ctx *ctx, lfdmi_radon *radon, const void *frames, int dtype, int n, int loc, const float *sigma,
+                            const uint64_t *seeds, int K, int kind, const void *kind_params, int scheme,
+                            const lfdmi_radon_peel *peel, int n_peel, void *records);
 
 /* ---- stacked cross-sections -------------------------------------------------------------------------------------------------
  * lfdmi_measure_trails needs every 64-position piece of a trail to stand 5 sigma on its own; a trail of the faint-trail search

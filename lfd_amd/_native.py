@@ -49,7 +49,7 @@ SYMBOLS = (
     "lfdmi_default_radon_lines_params", "lfdmi_radon_search_lines",
     "lfdmi_default_radon_short_params", "lfdmi_radon_search_short",
     "lfdmi_default_radon_wide_params", "lfdmi_radon_search_wide",
-    "lfdmi_radon_null",
+    "lfdmi_radon_null", "lfdmi_radon_null_scheme",
     "lfdmi_default_stack_params", "lfdmi_stack_profiles",
     "lfdmi_default_stars_params", "lfdmi_find_stars", "lfdmi_stars_catalog",
 )
@@ -406,6 +406,17 @@ RADON_MAX_WIDTH = 16
 RADON_NULL_LINES, RADON_NULL_SHORT, RADON_NULL_WIDE = 0, 1, 2
 RADON_NULL_MAX = 64
 RADON_NULL_KINDS = {"lines": RADON_NULL_LINES, "short": RADON_NULL_SHORT, "wide": RADON_NULL_WIDE}
+RADON_NULL_SCRAMBLE, RADON_NULL_SIGNFLIP, RADON_NULL_ROWSHIFT, RADON_NULL_COLSHIFT = 0, 1, 2, 3
+RADON_NULL_SCHEMES = {"scramble": RADON_NULL_SCRAMBLE, "signflip": RADON_NULL_SIGNFLIP, "rowshift": RADON_NULL_ROWSHIFT,
+                      "colshift": RADON_NULL_COLSHIFT}
+
+
+class RadonPeel(C.Structure):
+    """lfdmi_radon_peel: a line whose band lfdmi_radon_null_scheme blots before it searches (width 0: no line in this place)."""
+    _fields_ = [("q", C.c_int32), ("y0", C.c_int32), ("s", C.c_int32), ("width", C.c_int32)]
+
+
+RADON_PEEL_DTYPE = np.dtype([("q", "<i4"), ("y0", "<i4"), ("s", "<i4"), ("width", "<i4")])
 
 
 def make_radon_wide_params(**params):
@@ -560,6 +571,8 @@ def lib():
                                                  C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.lfdmi_radon_null.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                           C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        _lib.lfdmi_radon_null_scheme.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                 C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         _lib.lfdmi_radon_search_short.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.lfdmi_default_stack_params.restype = None
@@ -1727,18 +1740,29 @@ class Radon(_Handle):
         return self._peel("search_wide", make_radon_wide_params, params, RADON_WIDE_DTYPE, bool(plain), frames, sigma, pinned,
                           native_device)
 
-    def null(self, frames, K=16, kind="lines", sigma=None, seeds=None, pinned=False, native_device=False, **kind_params):
-        """The null peaks of every frame: record 0 of the ``kind`` search ("lines", "short" or "wide") of K scrambled
-        realisations of each frame (include/lfdmi.h: faint-trail search, null peaks, steps 17 - 20); frames and sigma as in
-        ``search``.  seeds: None (frame f has seed f) or n uint64.  ``kind_params``: the fields of lfdmi_radon_short_params /
-        lfdmi_radon_wide_params; "lines" takes none.  Returns records [n, K]: RADON_DTYPE, RADON_SHORT_DTYPE or
-        RADON_WIDE_DTYPE.  The first call of a kind allocates what that kind's search does; ``dims()`` counts it."""
+    def null(self, frames, K=16, kind="lines", sigma=None, seeds=None, pinned=False, native_device=False, scheme="scramble", peel=None,
+             **kind_params):
+        """The null peaks of every frame: record 0 of the ``kind`` search ("lines", "short" or "wide") of K null realisations
+        of each frame (include/lfdmi.h: faint-trail search, null peaks, steps 17 - 22); frames and sigma as in ``search``.
+        seeds: None (frame f has seed f) or n uint64.  ``kind_params``: the fields of lfdmi_radon_short_params /
+        lfdmi_radon_wide_params; "lines" takes none, but with another ``scheme`` or with ``peel`` those of
+        lfdmi_radon_lines_params.  scheme: "scramble" (every pixel drawn from the frame), "signflip" (every pixel in its place,
+        its sign by a coin), "rowshift" / "colshift" (every row / column rotated by its own offset).  peel ("signflip" only):
+        RADON_PEEL_DTYPE records [n, n_peel], the lines of each frame whose bands are blotted before the search (width 0: none
+        in this place).  Returns records [n, K]: RADON_DTYPE, RADON_SHORT_DTYPE or RADON_WIDE_DTYPE.  The first call of a kind
+        allocates what that kind's search does; ``dims()`` counts it.  The defaults run lfdmi_radon_null, anything else
+        lfdmi_radon_null_scheme."""
         r, ctx = self._open(), self.ctx
         if kind not in RADON_NULL_KINDS:
             raise ValueError("kind: 'lines', 'short' or 'wide'")
-        if kind == "lines" and kind_params:
+        if scheme not in RADON_NULL_SCHEMES:
+            raise ValueError("scheme: 'scramble', 'signflip', 'rowshift' or 'colshift'")
+        old = scheme == "scramble" and peel is None
+        if kind == "lines" and kind_params and old:
             raise TypeError(f"unknown radon null parameter {sorted(kind_params)[0]!r}: kind 'lines' takes none")
-        p = {"lines": lambda: None, "short": make_radon_short_params, "wide": make_radon_wide_params}[kind](**kind_params)
+        make = {"lines": make_radon_lines_params if kind_params else lambda: None, "short": make_radon_short_params,
+                "wide": make_radon_wide_params}[kind]
+        p = make(**kind_params)
         dtype = {"lines": RADON_DTYPE, "short": RADON_SHORT_DTYPE, "wide": RADON_WIDE_DTYPE}[kind]
         frames, code, n, h, w, loc = self._frames(frames, pinned, "Radon.null", native_device=native_device)
         sg = _sigma(sigma, n)
@@ -1748,6 +1772,17 @@ class Radon(_Handle):
                 raise ValueError("seeds: one uint64 per frame")
         K = int(K)
         res = np.zeros((n, max(1, min(K, RADON_NULL_MAX))), dtype)       # (out of range: the library refuses before it writes)
-        ctx._chk(self._lib.lfdmi_radon_null(ctx._h, r, _ptr(frames), code, n, loc, _ptr(sg), _ptr(seeds), K, RADON_NULL_KINDS[kind],
-                                            None if p is None else C.byref(p), _ptr(res)))
+        if old:
+            ctx._chk(self._lib.lfdmi_radon_null(ctx._h, r, _ptr(frames), code, n, loc, _ptr(sg), _ptr(seeds), K, RADON_NULL_KINDS[kind],
+                                                None if p is None else C.byref(p), _ptr(res)))
+            return res
+        n_peel = 0
+        if peel is not None:
+            peel = np.ascontiguousarray(peel, RADON_PEEL_DTYPE)
+            if peel.ndim != 2 or peel.shape[0] != n:
+                raise ValueError("peel: RADON_PEEL_DTYPE records [n, n_peel]")
+            n_peel = peel.shape[1]
+        ctx._chk(self._lib.lfdmi_radon_null_scheme(ctx._h, r, _ptr(frames), code, n, loc, _ptr(sg), _ptr(seeds), K, RADON_NULL_KINDS[kind],
+                                                   None if p is None else C.byref(p), RADON_NULL_SCHEMES[scheme],
+                                                   _ptr(peel) if n_peel else None, n_peel, _ptr(res)))
         return res

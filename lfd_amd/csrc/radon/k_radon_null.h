@@ -1,10 +1,16 @@
-// k_radon_null.h -- kernels of the null peaks (include/lfdmi.h: faint-trail search, null peaks, steps 17 - 20; host side in
+// k_radon_null.h -- kernels of the null peaks (include/lfdmi.h: faint-trail search, null peaks, steps 17 - 22; host side in
 // radon.hip).  The transform and the scoring of a scrambled frame run k_radon_first .. k_radon_finish and the short and wide
 // kernels unchanged.
 //   k_radon_prep_null   k_radon_prep of the scrambled frame X'[i] = X[j(i)] (step 18) that is never stored: every binned cell
 //                       reads its b x b source pixels through the gather.  Slot blockIdx.z is one realisation of one frame of the
 //                       chunk (its key and the frame's place come from `slots`), so the K realisations of a frame sit in
 //                       neighbouring slots and gather from the same 4 H W bytes
+//   k_radon_prep_scheme<SCHEME>  k_radon_prep of an in-place null frame (step 21) that is never stored: the same binning loop,
+//                       validity test and accumulator, a thread per binned cell with neighbouring lanes on neighbouring
+//                       columns.  SIGNFLIP reads the cell's own pixels and flips the sign bit by the pixel's hash; ROWSHIFT
+//                       reads its row from column (c + o(r)) mod W on, so a wavefront's loads are consecutive addresses that
+//                       wrap once; COLSHIFT reads every column from a row of its own, (r + o(c)) mod H: 4-byte loads a row
+//                       stride apart
 //   k_radon_null_lines  the found records of a chunk as lines for k_radon_extent (the short and wide kinds: steps 12 and 16
 //                       give a found record its segment), so the call needs no wait in between; a slot without a found record
 //                       gets a line whose extent is computed and ignored
@@ -52,6 +58,56 @@ __global__ __launch_bounds__(RAD_THREADS) void k_radon_prep_null(const uint32_t 
             if (x >= p.w) break;
             uint32_t bits = fr[rad_null_source(row + (uint32_t)x, sl.klo, sl.khi, npix)];
             if (p.be) bits = __builtin_bswap32(bits);
+            const float v = __uint_as_float(bits);
+            const bool valid = (bits & 0x7F800000u) != 0x7F800000u && (bits & 0x7FFFFFFFu) != 0u && fabsf(v) <= p.clip;
+            acc = acc + (valid ? v : 0.0f);
+            cnt += valid;
+        }
+    }
+    const size_t o = ((size_t)a * p.hb + j) * p.wb + i;
+    V[o] = acc;
+    M[o] = (uint16_t)cnt;
+}
+
+// definition steps 18 and 21: u(i) of key (klo, khi)
+__device__ __forceinline__ uint32_t rad_null_u(uint32_t i, uint32_t klo, uint32_t khi) {
+    return rad_fmix32(rad_fmix32(i * 0x9E3779B1u + klo) ^ khi);
+}
+
+#define RADN_SIGNFLIP 1     // LFDMI_RADON_NULL_SIGNFLIP .. COLSHIFT (radon.hip asserts it)
+#define RADN_ROWSHIFT 2
+#define RADN_COLSHIFT 3
+
+template <int SCHEME>
+__global__ __launch_bounds__(RAD_THREADS) void k_radon_prep_scheme(const uint32_t *__restrict__ src, RadonDev p,
+                                                                   const RadonNullSlot *__restrict__ slots, float *__restrict__ V,
+                                                                   uint16_t *__restrict__ M) {
+    static_assert(SCHEME == RADN_SIGNFLIP || SCHEME == RADN_ROWSHIFT || SCHEME == RADN_COLSHIFT, "an in-place scheme");
+    const int i = blockIdx.x * RAD_THREADS + threadIdx.x, j = blockIdx.y, a = blockIdx.z;
+    if (i >= p.wb) return;
+    const RadonNullSlot sl = slots[a];
+    const uint32_t H = (uint32_t)p.h, W = (uint32_t)p.w;
+    const uint32_t *fr = src + (size_t)sl.frame * H * W;
+    uint32_t oc[4] = {0, 0, 0, 0};          // COLSHIFT: o(c) of the cell's columns (b <= 4)
+    if (SCHEME == RADN_COLSHIFT)
+        for (int dx = 0; dx < p.b; dx++) oc[dx] = (uint32_t)(((uint64_t)rad_null_u((uint32_t)(i * p.b + dx), sl.klo, sl.khi) * H) >> 32);
+    float acc = 0.0f;
+    int cnt = 0;
+    for (int dy = 0; dy < p.b; dy++) {
+        const int y = j * p.b + dy;
+        if (y >= p.h) break;
+        const uint32_t r = (uint32_t)(p.h - 1 - y);
+        uint32_t orow = 0;
+        if (SCHEME == RADN_ROWSHIFT) orow = (uint32_t)(((uint64_t)rad_null_u(r, sl.klo, sl.khi) * W) >> 32);     // < W
+        for (int dx = 0; dx < p.b; dx++) {
+            const int x = i * p.b + dx;
+            if (x >= p.w) break;
+            uint32_t rs = r, cs = (uint32_t)x;
+            if (SCHEME == RADN_ROWSHIFT) { cs += orow; cs -= cs >= W ? W : 0u; }            // x < W and o < W: one wrap at most
+            if (SCHEME == RADN_COLSHIFT) { rs += oc[dx]; rs -= rs >= H ? H : 0u; }
+            uint32_t bits = fr[(size_t)rs * W + cs];
+            if (p.be) bits = __builtin_bswap32(bits);
+            if (SCHEME == RADN_SIGNFLIP) bits ^= rad_null_u(r * W + (uint32_t)x, sl.klo, sl.khi) & 0x80000000u;
             const float v = __uint_as_float(bits);
             const bool valid = (bits & 0x7F800000u) != 0x7F800000u && (bits & 0x7FFFFFFFu) != 0u && fabsf(v) <= p.clip;
             acc = acc + (valid ? v : 0.0f);

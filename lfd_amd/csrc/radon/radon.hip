@@ -46,8 +46,11 @@ struct lfdmi_radon {
     RadonWidePart *wpart = nullptr;
     RadonWideRec *wrec = nullptr;
     int *wid = nullptr;
-    // lfdmi_radon_null only, allocated on its first call: the key and the frame of every slot
+    // lfdmi_radon_null only, allocated on its first call: the key and the frame of every slot; with peel records
+    // (lfdmi_radon_null_scheme) a pass's line and width of every slot
     RadonNullSlot *nslot = nullptr;
+    RadonLineDev *nline = nullptr;
+    int *nwid = nullptr;
     int64_t bytes = 0;
 };
 
@@ -129,7 +132,7 @@ extern "C" void lfdmi_radon_destroy(lfdmi_radon *s) {
     for (void *x : {(void *)s->V, (void *)s->M, (void *)s->S[0], (void *)s->S[1], (void *)s->N[0], (void *)s->N[1], (void *)s->sigma,
                     (void *)s->stage, (void *)s->part, (void *)s->rec, (void *)s->V2, (void *)s->M2, (void *)s->pre, (void *)s->cnt,
                     (void *)s->lnd, (void *)s->ext, (void *)s->spart, (void *)s->srec, (void *)s->wpart, (void *)s->wrec, (void *)s->wid,
-                    (void *)s->nslot})
+                    (void *)s->nslot, (void *)s->nline, (void *)s->nwid})
         if (x) hipFree(x);
     delete s;
 }
@@ -560,6 +563,11 @@ static int radon_short_check(lfdmi_ctx *ctx, const lfdmi_radon *s, const lfdmi_r
         return ctx_fail(ctx, LFDMI_ERR_ARG, "radon short params out of range (include/lfdmi.h: lfdmi_radon_short_params)");
     return 0;
 }
+static int radon_lines_check(lfdmi_ctx *ctx, const lfdmi_radon *s, const lfdmi_radon_lines_params &lq) {
+    if (lq.max_lines < 1 || lq.max_lines > LFDMI_RADON_MAX_LINES || lq.peel_halfwidth < 0 || lq.min_seg < 1 || lq.min_seg > s->par.min_len)
+        return ctx_fail(ctx, LFDMI_ERR_ARG, "radon lines params out of range (include/lfdmi.h: lfdmi_radon_lines_params)");
+    return 0;
+}
 static int radon_wide_check(lfdmi_ctx *ctx, const lfdmi_radon *s, const lfdmi_radon_wide_params &wq) {
     if (wq.max_width < 1 || wq.max_width > LFDMI_RADON_MAX_WIDTH || (wq.max_width & (wq.max_width - 1)) || wq.max_lines < 1 ||
         wq.max_lines > LFDMI_RADON_MAX_LINES || wq.peel_halfwidth < 0 || wq.min_seg < 1 || wq.min_seg > s->par.min_len ||
@@ -592,8 +600,7 @@ extern "C" int lfdmi_radon_search_lines(lfdmi_ctx *ctx, lfdmi_radon *s, const vo
     if (rc) return rc;
     RadonLinesMode m{s};
     if (lp) m.q = *lp; else lfdmi_default_radon_lines_params(&m.q);
-    if (m.q.max_lines < 1 || m.q.max_lines > LFDMI_RADON_MAX_LINES || m.q.peel_halfwidth < 0 || m.q.min_seg < 1 || m.q.min_seg > s->par.min_len)
-        return ctx_fail(ctx, LFDMI_ERR_ARG, "radon lines params out of range (include/lfdmi.h: lfdmi_radon_lines_params)");
+    if ((rc = radon_lines_check(ctx, s, m.q))) return rc;
     if ((rc = c.args(frames, lines && n_lines, dtype, n, loc, sigma))) return rc;
     if (n == 0) return 0;
     if ((rc = c.stage()) || (rc = radon_rounds_alloc(ctx, s))) return rc;
@@ -645,7 +652,7 @@ extern "C" int lfdmi_radon_search_wide(lfdmi_ctx *ctx, lfdmi_radon *s, const voi
     return radon_rounds(c, m, lines, n_lines, plain);
 }
 
-// ---- null peaks (definition steps 17 - 20) ----------------------------------------------------------------------------------------------
+// ---- null peaks (definition steps 17 - 22) ----------------------------------------------------------------------------------------------
 // The plain search as a Mode: what lfdmi_radon_null needs of one
 struct LFD_HIDDEN RadonPlainMode {
     static constexpr int null_wfield = -2;      // (no segment: lfdmi_radon_result has none)
@@ -674,12 +681,20 @@ static uint64_t radon_splitmix64(uint64_t x) {
     return x ^ (x >> 31);
 }
 
-// The chunks of lfdmi_radon_null after the entry point's checks, c.stage() and the lazy allocations.  Slot g = f K + r is
-// realisation r of frame f; a chunk is max_frames consecutive slots, so it reads at most that many frames (which fit the staging
-// buffer) and a frame's realisations may continue in the next chunk, which then uploads the frame again.  Everything is queued;
-// the host buffers live until the one wait at the end.
+// The chunks of lfdmi_radon_null and lfdmi_radon_null_scheme after the entry point's checks, c.stage() and the lazy allocations.
+// Slot g = f K + r is realisation r of frame f; a chunk is max_frames consecutive slots, so it reads at most that many frames
+// (which fit the staging buffer) and a frame's realisations may continue in the next chunk, which then uploads the frame again.
+// scheme: how the slots' V', M' are made (step 21).  peel, n_peel (step 22; checked by the caller): pass j blots record j of
+// every slot's frame from one V, M set into the other with k_radon_peel, slot a to slot a; a slot whose frame has no line in
+// that place (width 0) gets a line whose band lies outside every frame, so it is copied as it is.  A chunk runs as many passes
+// as its longest list.  Everything is queued; the host buffers live until the one wait at the end.
+static_assert(LFDMI_RADON_NULL_SIGNFLIP == RADN_SIGNFLIP && LFDMI_RADON_NULL_ROWSHIFT == RADN_ROWSHIFT &&
+                  LFDMI_RADON_NULL_COLSHIFT == RADN_COLSHIFT, "k_radon_null.h names the schemes by the header's values");
+#define RADN_HW_MAX (1 << 20)     // a half-width beyond any frame (a working row is below 2^18 in magnitude) blots what this one does
+#define RADN_NO_LINE (1 << 28)    // y0 of the line that blots nothing: farther from every cell than RADN_HW_MAX + LFDMI_RADON_MAX_WIDTH
 template <class Mode>
-static int radon_null(RadonCall &c, const Mode &m, const uint64_t *seeds, int K, typename Mode::Out *records) {
+static int radon_null(RadonCall &c, const Mode &m, const uint64_t *seeds, int K, typename Mode::Out *records,
+                      int scheme = LFDMI_RADON_NULL_SCRAMBLE, const lfdmi_radon_peel *peel = nullptr, int n_peel = 0) {
     typedef typename Mode::Rec Rec;
     static_assert(sizeof(Rec) % sizeof(int) == 0, "k_radon_null_lines reads records as ints");
     constexpr bool SEG = Mode::null_wfield >= -1;
@@ -691,10 +706,29 @@ static int radon_null(RadonCall &c, const Mode &m, const uint64_t *seeds, int K,
     const int CH = c.CH;
     int rc;
     if ((rc = radon_lazy(ctx, s, &s->nslot, (size_t)CH))) return rc;
+    // the frames' peel passes: a frame's records of width >= 1, in their order
+    int passes = 0;
+    std::vector<int> npeel(peel ? c.n : 0, 0);
+    for (int f = 0; f < (int)npeel.size(); f++) {
+        for (int e = 0; e < n_peel; e++) npeel[f] += peel[(size_t)f * n_peel + e].width >= 1;
+        passes = std::max(passes, npeel[f]);
+    }
+    if (passes) {
+        const size_t F = (size_t)CH, px = (size_t)p.hb * p.wb;
+        if ((rc = radon_lazy(ctx, s, &s->V2, F * px)) || (rc = radon_lazy(ctx, s, &s->M2, F * px)) || (rc = radon_lazy(ctx, s, &s->nline, F)) ||
+            (rc = radon_lazy(ctx, s, &s->nwid, F)))
+            return rc;
+    }
+    const int hw = (int)std::min<int64_t>(((int64_t)m.q.peel_halfwidth + p.b - 1) / p.b, RADN_HW_MAX);
     std::vector<RadonNullSlot> hslot((size_t)total);
     std::vector<float> hsg((size_t)total);
     std::vector<Rec> hrec((size_t)total);
     std::vector<RadonExtDev> hext(SEG ? (size_t)total : 0);
+    std::vector<RadonLineDev> hline((size_t)total * passes);     // [chunk][pass][slot], filled as the chunks are queued
+    std::vector<int> hwid((size_t)total * passes);
+    size_t lused = 0;
+    float *Vs[2] = {s->V, s->V2};
+    uint16_t *Ms[2] = {s->M, s->M2};
     for (int64_t g0 = 0; g0 < total; g0 += CH) {
         const int ns = (int)std::min<int64_t>(CH, total - g0), f0 = (int)(g0 / K), nfr = (int)((g0 + ns - 1) / K) - f0 + 1;
         for (int a = 0; a < ns; a++) {
@@ -710,16 +744,54 @@ static int radon_null(RadonCall &c, const Mode &m, const uint64_t *seeds, int K,
         }
         UHIP(hipMemcpyAsync(s->sigma, hsg.data() + g0, (size_t)ns * sizeof(float), hipMemcpyHostToDevice, st));
         UHIP(hipMemcpyAsync(s->nslot, hslot.data() + g0, (size_t)ns * sizeof(RadonNullSlot), hipMemcpyHostToDevice, st));
-        k_radon_prep_null<<<dim3(ceil_div(p.wb, RAD_THREADS), p.hb, ns), RAD_THREADS, 0, st>>>(src, p, s->nslot, s->V, s->M);
+        const dim3 pgrid(ceil_div(p.wb, RAD_THREADS), p.hb, ns);
+        if (scheme == LFDMI_RADON_NULL_SIGNFLIP)
+            k_radon_prep_scheme<RADN_SIGNFLIP><<<pgrid, RAD_THREADS, 0, st>>>(src, p, s->nslot, s->V, s->M);
+        else if (scheme == LFDMI_RADON_NULL_ROWSHIFT)
+            k_radon_prep_scheme<RADN_ROWSHIFT><<<pgrid, RAD_THREADS, 0, st>>>(src, p, s->nslot, s->V, s->M);
+        else if (scheme == LFDMI_RADON_NULL_COLSHIFT)
+            k_radon_prep_scheme<RADN_COLSHIFT><<<pgrid, RAD_THREADS, 0, st>>>(src, p, s->nslot, s->V, s->M);
+        else
+            k_radon_prep_null<<<pgrid, RAD_THREADS, 0, st>>>(src, p, s->nslot, s->V, s->M);
         ULAUNCH("k_radon_prep_null");
-        if ((rc = m.transform(c, s->V, s->M, ns, 0))) return rc;
+        int cur = 0, cpass = 0;
+        for (int f = f0; f < f0 + nfr && passes; f++) cpass = std::max(cpass, npeel[f]);
+        for (int j = 0; j < cpass; j++, cur ^= 1) {
+            RadonLineDev *hl = hline.data() + lused;
+            int *hwd = hwid.data() + lused;
+            lused += (size_t)ns;
+            for (int a = 0; a < ns; a++) {
+                const int f = (int)((g0 + a) / K);
+                hl[a] = RadonLineDev{a, 0, RADN_NO_LINE, 0};
+                hwd[a] = 1;
+                for (int e = 0, seen = 0; e < n_peel; e++) {
+                    const lfdmi_radon_peel &r = peel[(size_t)f * n_peel + e];
+                    if (r.width >= 1 && seen++ == j) {
+                        hl[a] = RadonLineDev{a, r.q, r.y0, r.s};
+                        hwd[a] = r.width;
+                        break;
+                    }
+                }
+            }
+            UHIP(hipMemcpyAsync(s->nline, hl, (size_t)ns * sizeof(RadonLineDev), hipMemcpyHostToDevice, st));
+            UHIP(hipMemcpyAsync(s->nwid, hwd, (size_t)ns * sizeof(int), hipMemcpyHostToDevice, st));
+            if (p.wb % 8 == 0) {
+                const dim3 grid(ceil_div(p.wb, RAD_THREADS * 8), ceil_div(p.hb, RADL_ROWS), ns);
+                k_radon_peel<8><<<grid, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->nline, hw, Vs[cur ^ 1], Ms[cur ^ 1], s->nwid);
+            } else {
+                const dim3 grid(ceil_div(p.wb, RAD_THREADS), ceil_div(p.hb, RADL_ROWS), ns);
+                k_radon_peel<1><<<grid, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->nline, hw, Vs[cur ^ 1], Ms[cur ^ 1], s->nwid);
+            }
+            ULAUNCH("k_radon_peel");
+        }
+        if ((rc = m.transform(c, Vs[cur], Ms[cur], ns, 0))) return rc;
         UHIP(hipMemcpyAsync(hrec.data() + g0, m.rec(), (size_t)ns * sizeof(Rec), hipMemcpyDeviceToHost, st));
         if constexpr (SEG) {
             int *wid = Mode::null_wfield >= 0 ? s->wid : nullptr;
             k_radon_null_lines<<<ceil_div(ns, RAD_THREADS), RAD_THREADS, 0, st>>>((const int *)m.rec(), (int)(sizeof(Rec) / sizeof(int)),
                                                                                   Mode::null_wfield, m.threshold(), ns, s->lnd, wid);
             ULAUNCH("k_radon_null_lines");
-            k_radon_extent<<<ns, RAD_THREADS, 0, st>>>(s->V, s->M, p, s->lnd, s->sigma, m.q.min_seg, s->pre, s->cnt, radon_pstride(p), s->ext, wid);
+            k_radon_extent<<<ns, RAD_THREADS, 0, st>>>(Vs[cur], Ms[cur], p, s->lnd, s->sigma, m.q.min_seg, s->pre, s->cnt, radon_pstride(p), s->ext, wid);
             ULAUNCH("k_radon_extent");
             UHIP(hipMemcpyAsync(hext.data() + g0, s->ext, (size_t)ns * sizeof(RadonExtDev), hipMemcpyDeviceToHost, st));
         }
@@ -735,16 +807,42 @@ static int radon_null(RadonCall &c, const Mode &m, const uint64_t *seeds, int K,
     return 0;
 }
 
-extern "C" int lfdmi_radon_null(lfdmi_ctx *ctx, lfdmi_radon *s, const void *frames, int dtype, int n, int loc, const float *sigma,
-                                const uint64_t *seeds, int K, int kind, const void *kind_params, void *records) {
-    RadonCall c{ctx, s, "lfdmi_radon_null"};
+// step 22's rules for the peel records of a call on handle s
+static int radon_peel_check(lfdmi_ctx *ctx, const lfdmi_radon *s, int scheme, const lfdmi_radon_peel *peel, int n, int n_peel) {
+    if (scheme < LFDMI_RADON_NULL_SCRAMBLE || scheme > LFDMI_RADON_NULL_COLSHIFT || n_peel < 0 || n_peel > LFDMI_RADON_MAX_LINES ||
+        (n_peel > 0 && (!peel || scheme != LFDMI_RADON_NULL_SIGNFLIP)))
+        return ctx_fail(ctx, LFDMI_ERR_ARG, "lfdmi_radon_null_scheme: scheme LFDMI_RADON_NULL_SCRAMBLE .. COLSHIFT, n_peel 0 .. "
+                                            "LFDMI_RADON_MAX_LINES, and peel records with LFDMI_RADON_NULL_SIGNFLIP only");
+    for (int64_t e = 0; e < (int64_t)std::max(n, 0) * n_peel; e++) {
+        const lfdmi_radon_peel &r = peel[e];
+        if (r.width == 0) continue;
+        if (r.width < 1 || r.width > LFDMI_RADON_MAX_WIDTH || (r.width & (r.width - 1)) || r.q < 0 || r.q > 3)
+            return ctx_fail(ctx, LFDMI_ERR_ARG, "lfdmi_radon_null_scheme: a peel record's width is 0 or a power of two up to 16, its q 0 .. 3");
+        const int P = s->p.P[r.q >> 1], R = s->p.R[r.q >> 1];
+        if (r.s < 0 || r.s > P - 1 || r.y0 < -(P - 1) || r.y0 > R - 1)
+            return ctx_fail(ctx, LFDMI_ERR_ARG, "lfdmi_radon_null_scheme: a peel record's s is 0 .. P-1, its y0 -(P-1) .. R-1");
+    }
+    return 0;
+}
+
+// the plain search as the LINES kind of lfdmi_radon_null_scheme: its peel_halfwidth comes from an lfdmi_radon_lines_params
+struct LFD_HIDDEN RadonPlainPeelMode : RadonPlainMode {
+    lfdmi_radon_lines_params q;
+};
+
+// what both entry points do; `scheme_call`: lfdmi_radon_null_scheme, whose LINES kind takes an lfdmi_radon_lines_params
+static int radon_null_call(lfdmi_ctx *ctx, lfdmi_radon *s, const char *fn, bool scheme_call, const void *frames, int dtype, int n, int loc,
+                           const float *sigma, const uint64_t *seeds, int K, int kind, const void *kind_params, int scheme,
+                           const lfdmi_radon_peel *peel, int n_peel, void *records) {
+    RadonCall c{ctx, s, fn};
     int rc = c.begin();
     if (rc) return rc;
     if (K < 1 || K > LFDMI_RADON_NULL_MAX || kind < LFDMI_RADON_NULL_LINES || kind > LFDMI_RADON_NULL_WIDE ||
-        (kind == LFDMI_RADON_NULL_LINES && kind_params))
-        return ctx_fail(ctx, LFDMI_ERR_ARG, "lfdmi_radon_null: K 1 .. LFDMI_RADON_NULL_MAX, kind LFDMI_RADON_NULL_*, and no kind_params for LINES");
+        (kind == LFDMI_RADON_NULL_LINES && kind_params && !scheme_call))
+        return ctx_fail(ctx, LFDMI_ERR_ARG, std::string(fn) + ": K 1 .. LFDMI_RADON_NULL_MAX, kind LFDMI_RADON_NULL_*, and no kind_params for LINES");
     if ((uint64_t)s->p.h * (uint64_t)s->p.w >= (1ull << 32))     // (lfdmi_radon_create holds H W to 1e9)
-        return ctx_fail(ctx, LFDMI_ERR_ARG, "lfdmi_radon_null: H * W must be below 2^32");
+        return ctx_fail(ctx, LFDMI_ERR_ARG, std::string(fn) + ": H * W must be below 2^32");
+    if ((rc = radon_peel_check(ctx, s, scheme, peel, n, n_peel))) return rc;
     if (kind == LFDMI_RADON_NULL_SHORT) {
         RadonShortMode m{s};
         if (kind_params) m.q = *(const lfdmi_radon_short_params *)kind_params; else lfdmi_default_radon_short_params(&m.q);
@@ -752,7 +850,7 @@ extern "C" int lfdmi_radon_null(lfdmi_ctx *ctx, lfdmi_radon *s, const void *fram
         if (n == 0) return 0;
         if ((rc = c.stage()) || (rc = radon_short_alloc(ctx, s))) return rc;
         m.sd = radon_short_layout(c.p, m.q.min_strip);
-        return radon_null(c, m, seeds, K, (lfdmi_radon_short *)records);
+        return radon_null(c, m, seeds, K, (lfdmi_radon_short *)records, scheme, peel, n_peel);
     }
     if (kind == LFDMI_RADON_NULL_WIDE) {
         RadonWideMode m{s};
@@ -760,11 +858,30 @@ extern "C" int lfdmi_radon_null(lfdmi_ctx *ctx, lfdmi_radon *s, const void *fram
         if ((rc = radon_wide_check(ctx, s, m.q)) || (rc = c.args(frames, records, dtype, n, loc, sigma))) return rc;
         if (n == 0) return 0;
         if ((rc = c.stage()) || (rc = radon_wide_alloc(ctx, s))) return rc;
-        return radon_null(c, m, seeds, K, (lfdmi_radon_wide *)records);
+        return radon_null(c, m, seeds, K, (lfdmi_radon_wide *)records, scheme, peel, n_peel);
     }
-    RadonPlainMode m{s};
+    RadonPlainPeelMode m{{s}};
+    // (without parameters only the default peel_halfwidth is used: a handle whose min_len is below the default min_seg is served)
+    lfdmi_default_radon_lines_params(&m.q);
+    if (kind_params) {
+        m.q = *(const lfdmi_radon_lines_params *)kind_params;
+        if ((rc = radon_lines_check(ctx, s, m.q))) return rc;
+    }
     if ((rc = c.args(frames, records, dtype, n, loc, sigma))) return rc;
     if (n == 0) return 0;
     if ((rc = c.stage())) return rc;
-    return radon_null(c, m, seeds, K, (lfdmi_radon_result *)records);
+    return radon_null(c, m, seeds, K, (lfdmi_radon_result *)records, scheme, peel, n_peel);
+}
+
+extern "C" int lfdmi_radon_null(lfdmi_ctx *ctx, lfdmi_radon *s, const void *frames, int dtype, int n, int loc, const float *sigma,
+                                const uint64_t *seeds, int K, int kind, const void *kind_params, void *records) {
+    return radon_null_call(ctx, s, "lfdmi_radon_null", false, frames, dtype, n, loc, sigma, seeds, K, kind, kind_params,
+                           LFDMI_RADON_NULL_SCRAMBLE, nullptr, 0, records);
+}
+
+extern "C" int lfdmi_radon_null_scheme(lfdmi_ctx *ctx, lfdmi_radon *s, const void *frames, int dtype, int n, int loc, const float *sigma,
+                                       const uint64_t *seeds, int K, int kind, const void *kind_params, int scheme,
+                                       const lfdmi_radon_peel *peel, int n_peel, void *records) {
+    return radon_null_call(ctx, s, "lfdmi_radon_null_scheme", true, frames, dtype, n, loc, sigma, seeds, K, kind, kind_params, scheme, peel,
+                           n_peel, records);
 }

@@ -289,13 +289,17 @@ class _RadonStage:
     (radon_wide.txt).  With ``prof_out`` the bands' centre-line segments are measured too, their rows end with ``wide`` and
     the lines' rows with ``lines``.  ``null``: K, the realisations of the null peaks (include/lfdmi.h steps 17 - 20): every
     searched frame also gets the null peaks of each kind that is on (``lines``; ``short`` and ``wide`` where those are), a row
-    per kind in ``null_out`` (radon_null.txt) and a row per found line in ``fap_out`` (radon_fap.txt)."""
+    per kind in ``null_out`` (radon_null.txt) and a row per found line in ``fap_out`` (radon_fap.txt).  ``null_scheme``: how
+    the null frames are made (steps 21 - 22: "scramble", "signflip", "rowshift", "colshift").  ``rounds_out``
+    (radon_null_rounds.txt; "signflip" only): every peel round k >= 1 that a frame's search of a kind ran also gets its null
+    -- the frame with that search's lines 0 .. k-1 blotted -- a row there, and line k's radon_fap.txt row comes from it."""
 
     def __init__(self, out, params, sigma, lines=None, lines_params=None, seg_out=None, prof_out=None, stack_params=None,
                  defocus_out=None, defocus_params=None, short=None, short_out=None, lc=None, wide=None, wide_out=None, strip=None,
-                 null=None, null_out=None, fap_out=None):
+                 null=None, null_out=None, fap_out=None, null_scheme="scramble", rounds_out=None):
         from ..radon import as_params
         self.null, self.null_out, self.fap_out = null, null_out, fap_out
+        self.null_scheme, self.rounds_out = null_scheme, rounds_out
         self.out, self.params, self.sigma, self._handles = out, as_params(params), float(sigma), {}
         self.wide, self.wide_out = (dict(wide) if wide is not None else None), wide_out
         self.lc, self.last_lc = lc, {}                # an ``_LcStage``; {position: [(record, sections)]} of the last ``batch`` / ``one``
@@ -412,9 +416,24 @@ class _RadonStage:
         return [("lines", {})] + ([("short", self.short)] if self.short is not None else []) + \
             ([("wide", self.wide)] if self.wide is not None else [])
 
-    def null_batch(self, ctx, frames, shape, todo, seeds, **where):
+    def peeled_lines(self, rec):
+        """{kind: (records [max_lines], n_lines)} of a frame's record: what the peeling searches that are on found"""
+        out = {}
+        if isinstance(rec, _WideRecord):
+            out["wide"] = (rec.recs, rec.n_lines)
+            rec = rec.base
+        if isinstance(rec, _ShortRecord):
+            out["short"] = (rec.recs, rec.n_lines)
+            rec = rec.base
+        if self.lines is not None:
+            out["lines"] = (rec[0], rec[1])
+        return out
+
+    def null_batch(self, ctx, frames, shape, todo, seeds, recs=None, **where):
         """the null peaks of the frames ``todo`` (as in ``batch``; seeds: one per entry of todo), where the search left the
-        frames -> {position: {kind: float32 [K]}}"""
+        frames -> {position: {kind: float32 [K]}}; with ``rounds_out`` and the frames' records ``recs`` ({position: record})
+        also "rounds": {kind: {k: float32 [K]}} for the rounds k >= 1 the kind's search ran on the frame"""
+        from ..radon import peel_from_lines
         out, k = {}, 0
         while k < len(todo):
             m = k
@@ -424,17 +443,34 @@ class _RadonStage:
             part = frames.slice(a, b) if isinstance(frames, _native.DeviceFrames) else frames[a:b]
             handle = self._handle(ctx, shape, min(b - a, 16))
             for kind, kp in self.null_kinds():
-                snr = handle.null(part, K=self.null, kind=kind, sigma=self.sigma, seeds=seeds[k:m + 1], **kp, **where)["snr"]
+                if kind == "lines" and self.rounds_out is not None and self.lines is not None:
+                    kp = self.lines_params                # (its peel_halfwidth is the rounds')
+                snr = handle.null(part, K=self.null, kind=kind, sigma=self.sigma, seeds=seeds[k:m + 1], scheme=self.null_scheme, **kp,
+                                  **where)["snr"]
                 for j in range(a, b):
                     out.setdefault(j, {})[kind] = _np.array(snr[j - a], _np.float32)
+                if self.rounds_out is None or recs is None:
+                    continue
+                # every frame of the run goes through every round some frame ran; a frame keeps the rounds it ran itself
+                found = [self.peeled_lines(recs[j]).get(kind) for j in range(a, b)]
+                if any(f is None for f in found):
+                    continue
+                lines, nl = _np.stack([f[0] for f in found]), _np.array([f[1] for f in found])
+                ran = _np.minimum(nl, lines.shape[1] - 1)        # the last round a frame ran
+                for rnd in range(1, int(ran.max()) + 1):
+                    snr = handle.null(part, K=self.null, kind=kind, sigma=self.sigma, seeds=seeds[k:m + 1], scheme="signflip",
+                                      peel=peel_from_lines(lines, nl, rnd), **kp, **where)["snr"]
+                    for j in range(a, b):
+                        if rnd <= ran[j - a]:
+                            out[j].setdefault("rounds", {}).setdefault(kind, {})[rnd] = _np.array(snr[j - a], _np.float32)
             k = m + 1
         return out
 
-    def null_one(self, img, seed):
-        """one host frame -> its {kind: float32 [K]}"""
+    def null_one(self, img, seed, rec=None):
+        """one host frame (and its record) -> its {kind: float32 [K]}"""
         img = _np.ascontiguousarray(img, _np.float32)
         with use_context(*img.shape) as ctx:
-            return self.null_batch(ctx, img[None], img.shape, [0], [seed])[0]
+            return self.null_batch(ctx, img[None], img.shape, [0], [seed], None if rec is None else {0: rec})[0]
 
     def found_lines(self, rec):
         """{kind: [(place in peel order, snr)]} of a frame's record: the lines that have rows in the kinds' files"""
@@ -453,12 +489,15 @@ class _RadonStage:
 
     def null_rows(self, key, rec, nulls):
         """a frame's radon_null.txt rows, one per kind, and its radon_fap.txt rows, one per found line"""
-        from ..radon import format_fap_row, format_null_row
+        from ..radon import format_fap_row, format_null_row, format_null_rounds_row
         found = self.found_lines(rec)
         for kind, _ in self.null_kinds():
             self.null_out.write(format_null_row(key, kind, nulls[kind]) + "\n")
-            for k, snr in found.get(kind, []):
-                self.fap_out.write(format_fap_row(key, kind, k, snr, nulls[kind]) + "\n")
+            rounds = nulls.get("rounds", {}).get(kind, {})
+            for k in sorted(rounds):
+                self.rounds_out.write(format_null_rounds_row(key, kind, k, rounds[k]) + "\n")
+            for k, snr in found.get(kind, []):                   # (line k was found in round k: its null is that round's)
+                self.fap_out.write(format_fap_row(key, kind, k, snr, rounds.get(k, nulls[kind])) + "\n")
 
     def row(self, key, rec):
         """the rows of one frame's record: the line if it was found; with ``lines``, every found line in peel order"""
@@ -508,6 +547,8 @@ class _RadonStage:
         if self.null_out is not None:
             self.null_out.flush()
             self.fap_out.flush()
+        if self.rounds_out is not None:
+            self.rounds_out.flush()
         if self.prof_out is not None:
             self.prof_out.flush()
         if self.defocus_out is not None:
@@ -907,7 +948,7 @@ def _run_frame(c, i, filter, frame):
             if c.radon.null is not None and not isinstance(c.rlines[i], Exception):
                 try:
                     from ..radon import null_seed
-                    c.nulls[i] = c.radon.null_one(img, null_seed(*c.keys[i]))
+                    c.nulls[i] = c.radon.null_one(img, null_seed(*c.keys[i]), c.rlines[i])
                 except Exception as e:  # noqa: BLE001
                     c.nulls[i] = e
         if c.sub is not None:                         # last: it changes the frame (a copy of it here)
@@ -991,7 +1032,8 @@ def _run_group(c, idx, filter, shape, inflight, source, second, detect_kw=None, 
                         try:
                             from ..radon import null_seed
                             seeds = [null_seed(*c.keys[idx[j]]) for j in todo]
-                            for j, nulls in c.radon.null_batch(ctx, frames, shape, todo, seeds, **measure_kw).items():
+                            rl = {j: c.rlines[idx[j]] for j in todo}
+                            for j, nulls in c.radon.null_batch(ctx, frames, shape, todo, seeds, rl, **measure_kw).items():
                                 c.nulls[idx[j]] = nulls
                         except Exception as e:  # noqa: BLE001
                             for j in todo:
@@ -1266,7 +1308,13 @@ class DetectTrails:
     split give the same rows.  ``radon_null_file`` (default ``<savepath>/radon_null.txt``) gets one row per frame and kind: ``run
     camcol filter field kind K null_min null_median null_max``; ``radon_fap_file`` (``<savepath>/radon_fap.txt``) one row per found
     line: ``run camcol filter field kind line snr n_ge K fap``.  Rank files and resume treat both like radon.txt; every other
-    output stays byte for byte what it is.
+    output stays byte for byte what it is.  ``radon_null_scheme`` ("scramble", the default; "signflip", "rowshift", "colshift":
+    include/lfdmi.h steps 21 - 22) fills both files with that scheme's peaks, in the same columns.
+    ``radon_null_rounds=True`` (needs ``radon_null_scheme="signflip"``): every peel round k >= 1 that a frame's search of a kind
+    ran also gets its own null, the frame with that search's lines 0 .. k-1 blotted as the search blotted them;
+    ``radon_null_rounds_file`` (default ``<savepath>/radon_null_rounds.txt``) gets one row per frame, kind and such round: ``run
+    camcol filter field kind round K null_min null_median null_max``, and the radon_fap.txt row of line k >= 1 is taken from
+    round k's peaks, not round 0's.  Rank files and resume treat the file like radon_null.txt.
     ``radon_wide=True`` or a dict / ``lfd_amd.radon.RadonWideParams`` (needs ``radon=True``): the frames are also searched for
     wide faint trails by scoring sliding bands of the last level's lines (steps 13 - 16 of the definition) and
     ``radon_wide_file`` (default ``<savepath>/radon_wide.txt``) gets one row per found band: ``run camcol filter field line
@@ -1375,6 +1423,18 @@ class DetectTrails:
             if int(self.radon_null) != self.radon_null or not 1 <= self.radon_null <= _native.RADON_NULL_MAX:
                 raise ValueError("radon_null must be an integer, 1 .. %d" % _native.RADON_NULL_MAX)
             self.radon_null = int(self.radon_null)
+        self.radon_null_rounds_file = kwargs.get("radon_null_rounds_file", os.path.join(save, "radon_null_rounds.txt"))
+        self.radon_null_scheme = kwargs.get("radon_null_scheme", "scramble")
+        self.radon_null_rounds = kwargs.get("radon_null_rounds", False)
+        if self.radon_null_scheme not in _native.RADON_NULL_SCHEMES:
+            raise ValueError("radon_null_scheme must be one of %s" % ", ".join(_native.RADON_NULL_SCHEMES))
+        if self.radon_null_rounds not in (True, False):
+            raise ValueError("radon_null_rounds must be True or False")
+        if (self.radon_null_scheme != "scramble" or self.radon_null_rounds) and self.radon_null is None:
+            raise ValueError("radon_null_scheme and radon_null_rounds need radon_null=K")
+        if self.radon_null_rounds and self.radon_null_scheme != "signflip":
+            raise ValueError("radon_null_rounds needs radon_null_scheme='signflip': the other schemes move the pixels from under a "
+                             "peeled line's band")
         if self.radon_profiles:
             if not self.radon or (self.radon_lines is None and self.radon_short is None and self.radon_wide is None):
                 raise ValueError("radon_profiles=True needs radon=True and radon_lines=K: the segments it measures are theirs")
@@ -1576,8 +1636,10 @@ class DetectTrails:
                 (open(self.radon_wide_file + suffix, "a") if self.radon_wide is not None else contextlib.nullcontext()) as wide_out, \
                 _both(open(self.radon_profiles_file + suffix, "a") if self.radon_profiles else contextlib.nullcontext(),
                       _both(open(self.radon_null_file + suffix, "a") if self.radon_null is not None else contextlib.nullcontext(),
-                            open(self.radon_fap_file + suffix, "a") if self.radon_null is not None
-                            else contextlib.nullcontext())) as (rprof_out, (null_out, fap_out)), \
+                            _both(open(self.radon_fap_file + suffix, "a") if self.radon_null is not None
+                                  else contextlib.nullcontext(),
+                                  open(self.radon_null_rounds_file + suffix, "a") if self.radon_null_rounds
+                                  else contextlib.nullcontext()))) as (rprof_out, (null_out, (fap_out, rounds_out))), \
                 (open(self.radon_defocus_file + suffix, "a") if self.radon_profiles and self.defocus
                  else contextlib.nullcontext()) as rdef_out, \
                 (open(self.masks_file + suffix, "a") if self.trail_masks else contextlib.nullcontext()) as masks_out, \
@@ -1609,7 +1671,7 @@ class DetectTrails:
                 radon = prof_kw["radon"] = _RadonStage(radon_out, self.radon_params, sigma, self.radon_lines, self.radon_lines_params,
                                                        segments_out, rprof_out, self.stack_params, rdef_out, self.defocus_params,
                                                        self.radon_short, short_out, lc, self.radon_wide, wide_out, strip,
-                                                       self.radon_null, null_out, fap_out)
+                                                       self.radon_null, null_out, fap_out, self.radon_null_scheme, rounds_out)
             masks = None
             if self.trail_masks:
                 masks = prof_kw["masks"] = _MaskStage(masks_out, self.mask_params, self.mask_dir)

@@ -52,7 +52,8 @@ class Jobs:
     and with ``normalize=True`` / ``find_stars=True`` their sky.txt / stars.txt files too, and with ``trail_masks=True``
     their masks.txt files, with ``light_curves=True`` (``lc_params``, ``lightcurves_file``, ``lightcurve_summary_file``) their
     lightcurves.txt and lightcurve_summary.txt files, with ``trail_strips=True`` (``strips_params``, ``strips_file``,
-    ``strips_dir``) their strips.txt files, with ``radon_null=K`` their radon_null.txt and radon_fap.txt files (rows in selection order)."""
+    ``strips_dir``) their strips.txt files, with ``radon_null=K`` their radon_null.txt and radon_fap.txt files and with
+    ``radon_null_rounds=True`` their radon_null_rounds.txt files (rows in selection order)."""
 
     def __init__(self, n_workers, devices=None, python=None, **detecttrails_kwargs):
         self.n = int(n_workers)
@@ -84,7 +85,8 @@ class Jobs:
             ([probe.sky_file] if probe.normalize else []) + ([probe.stars_file] if probe.find_stars else []) + ([probe.masks_file] if probe.trail_masks else []) + \
             ([probe.lightcurves_file, probe.lightcurve_summary_file] if probe.light_curves else []) + \
             ([probe.strips_file] if probe.trail_strips else []) + ([probe.subtracted_file] if probe.subtract_trails else []) + \
-            ([probe.radon_null_file, probe.radon_fap_file] if probe.radon_null is not None else [])
+            ([probe.radon_null_file, probe.radon_fap_file] if probe.radon_null is not None else []) + \
+            ([probe.radon_null_rounds_file] if probe.radon_null_rounds else [])
         if not resume:
             for path in joined:                           # the joined files are rewritten by this launch
                 if self.n > 1 and os.path.exists(path):

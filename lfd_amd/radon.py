@@ -6,7 +6,9 @@ the definition): ``RadonLinesParams``, the dyadic path, a segment's end points, 
 for short trails, scored on every dyadic level (steps 10 - 12): ``RadonShortParams``, ``search_short`` and the radon_short.txt
 format; for wide trails, scored as sliding bands of neighbouring lines (steps 13 - 16): ``RadonWideParams``, ``search_wide``
 and the radon_wide.txt format; for a frame's own noise ceiling (null peaks, steps 17 - 20): ``null_peaks``, ``false_alarm``,
-``null_threshold`` and the radon_null.txt and radon_fap.txt formats.
+``null_threshold`` and the radon_null.txt and radon_fap.txt formats; for nulls that leave the pixels in place and the nulls of
+the peel rounds (steps 21 - 22): the ``scheme`` and ``peel`` arguments of ``null_peaks``, ``shift_scheme_for``, ``peel_from_lines``,
+``null_rounds`` and the radon_null_rounds.txt format.
 """
 import dataclasses
 import math
@@ -28,6 +30,9 @@ SHORT_COLUMNS = ("run", "camcol", "filter", "field", "line", "level", "strip", "
 WIDE_COLUMNS = ("run", "camcol", "filter", "field", "line", "width", "width_px", "snr", "n_pix", "ex1", "ey1", "ex2", "ey2", "seg_snr",
                 "seg_n_pix")
 NULL_KINDS = ("lines", "short", "wide")
+NULL_SCHEMES = tuple(_native.RADON_NULL_SCHEMES)
+RADON_PEEL_DTYPE = _native.RADON_PEEL_DTYPE
+NULL_ROUNDS_COLUMNS = ("run", "camcol", "filter", "field", "kind", "round", "K", "null_min", "null_median", "null_max")
 NULL_COLUMNS = ("run", "camcol", "filter", "field", "kind", "K", "null_min", "null_median", "null_max")
 FAP_COLUMNS = ("run", "camcol", "filter", "field", "kind", "line", "snr", "n_ge", "K", "fap")
 INT_COLUMNS = frozenset(("run", "camcol", "field", "line", "level", "strip", "width", "n_pix", "seg_n_pix"))   # of every file here
@@ -292,27 +297,107 @@ def search_frames(ctx, frames, sigma=None, **params):
     return _search(ctx, frames, as_params(params), lambda r, arr: r.search(arr, sigma=sigma))
 
 
-def null_peaks(ctx, frames, K=16, kind="lines", sigma=None, seeds=None, **params):
-    """The null peaks of (n, h, w) or (h, w) frames on ``ctx`` (include/lfdmi.h: faint-trail search, null peaks): float32
-    [n, K], the best score of the ``kind`` search ("lines", "short", "wide") of K scrambled realisations of every frame -- the
-    frame's own noise ceiling.  ``params``: fields of RadonParams and of the kind's parameters.  seeds: None (frame f has seed
-    f) or one uint64 per frame.  A realisation without a candidate has the peak 0.  The handle is created and destroyed per
-    call; ``_native.Radon.null`` returns the whole records."""
+def _null_params(K, kind, scheme, peel, params):
+    """the checks ``null_peaks`` makes before the device: (RadonParams fields, the kind's parameters)"""
     if kind not in NULL_KINDS:
         raise ValueError("kind: 'lines', 'short' or 'wide'")
+    if scheme not in NULL_SCHEMES:
+        raise ValueError("scheme: 'scramble', 'signflip', 'rowshift' or 'colshift'")
     if not 1 <= int(K) <= _native.RADON_NULL_MAX:
         raise ValueError("K must be 1 .. %d" % _native.RADON_NULL_MAX)
+    if peel is not None and scheme != "signflip":
+        raise ValueError("peel records need scheme='signflip': the other schemes move the pixels from under the band")
     kp = {}
     if kind == "short":
         params, kp = _split(params, RadonShortParams)
     elif kind == "wide":
         params, kp = _split(params, RadonWideParams)
+    elif scheme != "scramble" or peel is not None:       # (the scramble without peel records takes no lines parameters)
+        params, kp = _split(params, RadonLinesParams)
     rp = as_params(params)
     if kind == "short":
         kp = as_short_params(kp, rp.get("bin", RadonParams.bin))
     elif kind == "wide":
         kp = as_wide_params(kp, rp.get("min_len", RadonParams.min_len))
-    return _search(ctx, frames, rp, lambda r, arr: np.ascontiguousarray(r.null(arr, K=K, kind=kind, sigma=sigma, seeds=seeds, **kp)["snr"]))
+    elif kp:
+        kp = as_lines_params(kp, rp.get("min_len", RadonParams.min_len))
+    return rp, kp
+
+
+def null_peaks(ctx, frames, K=16, kind="lines", sigma=None, seeds=None, scheme="scramble", peel=None, **params):
+    """The null peaks of (n, h, w) or (h, w) frames on ``ctx`` (include/lfdmi.h: faint-trail search, null peaks): float32
+    [n, K], the best score of the ``kind`` search ("lines", "short", "wide") of K null realisations of every frame -- the
+    frame's own noise ceiling.  ``params``: fields of RadonParams and of the kind's parameters.  seeds: None (frame f has seed
+    f) or one uint64 per frame.  scheme: "scramble" (every pixel drawn from the whole frame), "signflip" (every pixel in its
+    place, its sign by a coin), "rowshift" / "colshift" (every row / column rotated by its own offset; ``shift_scheme_for``).
+    peel (signflip only): RADON_PEEL_DTYPE records [n, n_peel] (``peel_from_lines``), blotted before the search with the
+    kind's ``peel_halfwidth`` (kind "lines": a field of RadonLinesParams).  A realisation without a candidate has the peak 0.
+    The handle is created and destroyed per call; ``_native.Radon.null`` returns the whole records."""
+    rp, kp = _null_params(K, kind, scheme, peel, params)
+    return _search(ctx, frames, rp, lambda r, arr: np.ascontiguousarray(
+        r.null(arr, K=K, kind=kind, sigma=sigma, seeds=seeds, scheme=scheme, peel=peel, **kp)["snr"]))
+
+
+def shift_scheme_for(q):
+    """The shift scheme that destroys a line of orientation q: "colshift" for q = 0, 1, whose lines cross the columns (the row
+    shift would leave a trail along the rows whole), "rowshift" for q = 2, 3."""
+    if q not in (0, 1, 2, 3):
+        raise ValueError("q must be 0 .. 3")
+    return "colshift" if q < 2 else "rowshift"
+
+
+def peel_from_lines(lines, n_lines, upto):
+    """RADON_PEEL_DTYPE [n, upto]: the first min(n_lines, upto) found lines of every frame from the records [n, max_lines] of
+    ``search_lines``, ``search_short`` or ``search_wide`` (width: the band's, 1 where the record has none); the places after
+    them have width 0, no line."""
+    lines = np.asarray(lines)
+    n_lines = np.asarray(n_lines).reshape(-1)
+    upto = int(upto)
+    if lines.ndim != 2 or len(n_lines) != lines.shape[0] or not 0 <= upto <= min(lines.shape[1], _native.RADON_MAX_LINES):
+        raise ValueError("lines: records [n, max_lines], n_lines: [n], upto: 0 .. max_lines")
+    out = np.zeros((lines.shape[0], upto), RADON_PEEL_DTYPE)
+    has = np.arange(upto)[None, :] < n_lines[:, None]
+    for k in ("q", "y0", "s"):
+        out[k] = np.where(has, lines[k][:, :upto], 0)
+    out["width"] = np.where(has, lines["width"][:, :upto] if "width" in lines.dtype.names else 1, 0)
+    return out
+
+
+def null_rounds(ctx, frames, lines, n_lines, K=16, kind="lines", sigma=None, seeds=None, **params):
+    """The null peaks of every peel round of (n, h, w) frames on ``ctx``: float32 [n, max_lines, K] from the records
+    ``lines`` [n, max_lines] and ``n_lines`` of the kind's search of these frames.  Round k is the "signflip" null with the
+    frame's lines 0 .. k-1 blotted as the search blotted them (``params`` must be that search's: ``peel_halfwidth`` among
+    them), which is the null the search's round k -- line k -- has to be held against.  NaN where the frame never ran round
+    k: the search ran it iff k <= n_lines.  One handle and one call per round; the frames of a round keep their seeds."""
+    lines = np.asarray(lines)
+    n_lines = np.asarray(n_lines).reshape(-1)
+    rp, kp = _null_params(K, kind, "signflip", lines, params)
+    n, max_lines = lines.shape
+
+    def run(r, arr):
+        if arr.ndim == 2:
+            arr = arr[None]
+        sg = None if sigma is None else np.broadcast_to(np.asarray(sigma, np.float32), (n,))
+        sd = np.arange(n, dtype=np.uint64) if seeds is None else np.asarray(seeds, np.uint64).reshape(-1)
+        out = np.full((n, max_lines, int(K)), np.nan, np.float32)
+        for k in range(max_lines):
+            ran = np.flatnonzero(n_lines >= k)
+            if not len(ran):
+                break
+            part = arr if len(ran) == n else arr[torch_index(arr, ran)]
+            pl = peel_from_lines(lines[ran], n_lines[ran], k) if k else None
+            out[ran, k] = r.null(part, K=K, kind=kind, sigma=None if sg is None else np.ascontiguousarray(sg[ran]), seeds=sd[ran],
+                                 scheme="signflip", peel=pl, **kp)["snr"]
+        return out
+    return _search(ctx, frames, rp, run)
+
+
+def torch_index(arr, idx):
+    """``idx`` as an index of the frames ``arr``: a device tensor takes a tensor on its device"""
+    if _native._is_dev(arr):
+        import torch
+        return torch.as_tensor(idx, device=arr.device)
+    return idx
 
 
 def false_alarm(snr, null_snr):
@@ -368,6 +453,18 @@ def format_fap_row(meta, kind, line, snr, null_snr):
     return " ".join(str(v) for v in (*meta, kind, int(line), repr(float(snr)), n_ge, null.size, repr(false_alarm(snr, null))))
 
 
+def format_null_rounds_row(meta, kind, round, null_snr):
+    """One radon_null_rounds.txt row: ``format_null_row`` with the peel round after the kind"""
+    null = np.sort(np.asarray(null_snr, np.float32).reshape(-1))
+    return " ".join(str(v) for v in (*meta, kind, int(round), null.size, repr(float(null[0])), repr(float(np.median(null))),
+                                     repr(float(null[-1]))))
+
+
+def read_null_rounds(path):
+    """radon_null_rounds.txt (rows only, no header line) -> list of dicts keyed by NULL_ROUNDS_COLUMNS"""
+    return _read_kinds(path, NULL_ROUNDS_COLUMNS)
+
+
 def read_null(path):
     """radon_null.txt (rows only, no header line) -> list of dicts keyed by NULL_COLUMNS"""
     return _read_kinds(path, NULL_COLUMNS)
@@ -379,7 +476,7 @@ def read_fap(path):
 
 
 def _read_kinds(path, columns):
-    ints = INT_COLUMNS | {"K", "n_ge"}
+    ints = INT_COLUMNS | {"K", "n_ge", "round"}
     rows = []
     with open(path) as f:
         for ln in f:

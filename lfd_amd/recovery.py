@@ -1,7 +1,7 @@
 """Injection and recovery: add model trails of known line and brightness to frames, detect, and count what comes back -- the
 detector's efficiency as a function of the trail's peak (include/lfdmi.h: trail injection).
 
-    python -m lfd_amd.recovery --synth K0:N --peaks 0.05,0.1,0.2,5 --out DIR [--detector radon | radon-short] [--length-frac F] [--null K]
+    python -m lfd_amd.recovery --synth K0:N --peaks 0.05,0.1,0.2,5 --out DIR [--detector radon | radon-short] [--length-frac F] [--null K [--null-scheme S]]
 
 The plan (``draw_trails``), the matching (``match``) and the rows use integer RNG draws and IEEE + - * / sqrt only -- cos and sin
 come from ``cos_sin`` below, a fixed sequence of multiplications and additions -- so every machine draws the same plan and
@@ -193,7 +193,7 @@ def radon_records(lines):
 
 
 def run(ctx, frames, cats, rs, trails, tables, table_step, params_bright=None, params_dim=None, subsample=4, profiles=False,
-        k=K_MATCH, detector="hough", radon_params=None, sigma=None, short_params=None, null=0):
+        k=K_MATCH, detector="hough", radon_params=None, sigma=None, short_params=None, null=0, null_scheme="scramble"):
     """Copy ``frames`` ((n, h, w) float32 numpy or torch CUDA), inject the plan ``trails`` (tables of peak 1: see
     ``inject.normalise_peak``), run ``detect_batch`` and match: ROW_DTYPE rows, one per trail.  cats: the frames' catalogues
     (a list of dicts, a packed dict or None) and rs their remove_stars parameters; profiles=True also runs ``measure_trails``
@@ -203,7 +203,10 @@ def run(ctx, frames, cats, rs, trails, tables, table_step, params_bright=None, p
     of that definition; ``short_params``) instead, and the parent line of a frame's first record is matched.  null=K > 0 (the
     radon detectors): the frames' null peaks of that search (include/lfdmi.h: null peaks; frame f has seed f) are measured on
     the same frames, and the call returns (rows, fap): float64 [n trails], ``radon.false_alarm`` of each trail's frame's line
-    among its frame's K null peaks."""
+    among its frame's K null peaks; ``null_scheme``: how the null frames are made ("scramble", "signflip", "rowshift",
+    "colshift": steps 21 - 22 of that definition)."""
+    if null_scheme not in _native.RADON_NULL_SCHEMES:
+        raise ValueError("null_scheme: one of %s" % ", ".join(_native.RADON_NULL_SCHEMES))
     if detector not in ("hough", "radon", "radon-short"):
         raise ValueError("detector: 'hough', 'radon' or 'radon-short'")
     if null and detector == "hough":
@@ -229,7 +232,7 @@ def run(ctx, frames, cats, rs, trails, tables, table_step, params_bright=None, p
             else:
                 kind, sp = "short", _radon.as_short_params(short_params, rp.get("bin", _radon.RadonParams.bin))
                 lines = search.search_short(work, sigma=sigma, **sp)[0][:, 0]
-            peaks = search.null(work, K=int(null), kind=kind, sigma=sigma, **sp)["snr"] if null else None
+            peaks = search.null(work, K=int(null), kind=kind, sigma=sigma, scheme=null_scheme, **sp)["snr"] if null else None
         rows = make_rows(radon_records(lines), trails, pb, pd, (h, w), k=k)
         if peaks is None:
             return rows
@@ -328,6 +331,9 @@ def main(argv=None):
     ap.add_argument("--null", type=int, default=0, metavar="K",
                     help="--detector radon / radon-short: also measure K null peaks per frame and add the median false-alarm "
                          "estimate of the recovered trails to the table")
+    ap.add_argument("--null-scheme", default="scramble", choices=tuple(_native.RADON_NULL_SCHEMES),
+                    help="--null K: how the null frames are made (default scramble; signflip, rowshift and colshift leave every "
+                         "pixel in its place, row or column)")
     a = ap.parse_args(argv)
     if a.null and a.detector == "hough":
         ap.error("--null needs --detector radon or radon-short")
@@ -344,7 +350,7 @@ def main(argv=None):
     plan = shorten(draw_trails(len(keep), frames.shape[1:], a.seed, peaks), frames.shape[1:], a.length_frac, a.seed)
     with _native.Context(0, frames.shape[1], frames.shape[2], 16) as ctx:
         rows = run(ctx, frames, cats, rs, plan, _inject.normalise_peak(table), step, pb, pd, profiles=a.profiles,
-                   detector=a.detector, radon_params={"bin": a.bin} if a.bin else None, null=a.null)
+                   detector=a.detector, radon_params={"bin": a.bin} if a.bin else None, null=a.null, null_scheme=a.null_scheme)
     rows, fap = rows if a.null else (rows, None)
     os.makedirs(a.out, exist_ok=True)
     write_recovery(os.path.join(a.out, "recovery.txt"), rows)

@@ -5,7 +5,13 @@ HIP events.  Also records the first full-frame figures of the false-alarm ceilin
 null peak over those frames for every kind, and the same for ``synth.make_frame`` frames after remove_stars (each of which
 carries its recipe's streak, so their unscrambled peak is a trail's, not a ceiling).  Writes profiles/radon_null_probe.txt.
 
+``--scheme a,b,..`` (or ``all``): the same for lfdmi_radon_null_scheme under each named scheme in one run -- ms per call against K
+searches and against the scramble, and both sets of ceilings per scheme; ``--rounds R``: also the sign-flip call with R peel
+records per frame (what a round R of ``radon.null_rounds`` costs).  Then the default output is
+profiles/radon_null_schemes_probe.txt.
+
     python tools/radon_null_probe.py [--reps 20] [--frames 256] [--max-frames 16] [--K 8] [--synth 16] [--out FILE]
+                                     [--scheme all] [--rounds R]
 
 The GPU step is a child process under its own `timeout`.
 """
@@ -41,7 +47,7 @@ def stats(ms):
     return {"median": float(np.median(ms)), "min": float(min(ms)), "max": float(max(ms))}
 
 
-def ceilings(r, frames, K):
+def ceilings(r, frames, K, scheme="scramble"):
     """per kind: the largest unscrambled peak and the largest null peak over ``frames``"""
     out = {}
     for kind in KINDS:
@@ -49,7 +55,7 @@ def ceilings(r, frames, K):
             peak = r.search(frames)["snr"]
         else:
             peak = getattr(r, "search_" + kind)(frames, max_lines=1)[0][:, 0]["snr"]
-        null = r.null(frames, K=K, kind=kind)["snr"]
+        null = r.null(frames, K=K, kind=kind, scheme=scheme)["snr"]
         out[kind] = {"unscrambled_max": float(peak.max()), "null_max": float(null.max()), "null_min": float(null.min()),
                      "frames_above_own_null_max": int((peak > null.max(axis=1)).sum()), "frames": int(len(peak)), "K": K}
     return out
@@ -71,13 +77,29 @@ def child(a):
                "extra_ms_per_call": null["median"] - a.K * search["median"],
                "extra_us_per_realisation": 1e3 * (null["median"] - a.K * search["median"]) / (a.K * a.frames),
                "noise": ceilings(r, frames, a.K)}
+        schemes = list(_native.RADON_NULL_SCHEMES) if a.scheme == "all" else [s for s in a.scheme.split(",") if s]
+        if schemes:
+            doc["schemes"] = {}
+            for sch in schemes:
+                ms = stats(timed(lambda: r.null(frames, K=a.K, scheme=sch), a.reps))
+                doc["schemes"][sch] = {"ms": ms, "ratio_over_K_searches": ms["median"] / (a.K * search["median"]),
+                                       "ratio_over_scramble": ms["median"] / null["median"], "noise": ceilings(r, frames, a.K, sch)}
+        if a.rounds:
+            peel = np.zeros((a.frames, a.rounds), _native.RADON_PEEL_DTYPE)
+            for k in range(a.rounds):                     # lines of orientation 0 spread over the frame, one cell wide
+                peel[:, k] = (0, 50 + 90 * k, 100 + 37 * k, 1)
+            ms = stats(timed(lambda: r.null(frames, K=a.K, scheme="signflip", peel=peel), a.reps))
+            doc["rounds"] = {"n_peel": a.rounds, "ms": ms, "ratio_over_K_searches": ms["median"] / (a.K * search["median"])}
         if a.synth:
             _, _, prs = default_params()
             imgs, cats = zip(*(synth.make_frame(k)[:2] for k in range(a.synth)))
             sf = np.ascontiguousarray(np.stack(imgs), np.float32)
             rs = _native.make_rs_params("r", **{k: v for k, v in prs.items() if k != "debug"})
             ctx.remove_stars(sf, synth.pack_catalogs(list(cats)), rs)
-            doc["synth_after_remove_stars"] = ceilings(r, torch.from_numpy(sf).cuda(), a.K)
+            dev = torch.from_numpy(sf).cuda()
+            doc["synth_after_remove_stars"] = ceilings(r, dev, a.K)
+            for sch in schemes:
+                doc["schemes"][sch]["synth_after_remove_stars"] = ceilings(r, dev, a.K, sch)
     print("RESULT " + json.dumps(doc), flush=True)
 
 
@@ -88,14 +110,18 @@ def main():
     ap.add_argument("--max-frames", type=int, default=16)
     ap.add_argument("--K", type=int, default=8)
     ap.add_argument("--synth", type=int, default=16)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "radon_null_probe.txt"))
+    ap.add_argument("--scheme", default="", help="schemes to time and measure beside the scramble, comma separated, or 'all'")
+    ap.add_argument("--rounds", type=int, default=0, metavar="R", help="also time the sign-flip call with R peel records per frame")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--child", action="store_true")
     a = ap.parse_args()
     if a.child:
         child(a)
         return
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "radon_null_schemes_probe.txt" if a.scheme or a.rounds else "radon_null_probe.txt")
     cmd = ["timeout", "-k", "10", "540", sys.executable, os.path.abspath(__file__), "--child", "--reps", str(a.reps), "--frames",
-           str(a.frames), "--max-frames", str(a.max_frames), "--K", str(a.K), "--synth", str(a.synth)]
+           str(a.frames), "--max-frames", str(a.max_frames), "--K", str(a.K), "--synth", str(a.synth), "--scheme", a.scheme, "--rounds", str(a.rounds)]
     p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
     if p.returncode:
         raise SystemExit("radon_null_probe: %s ended with status %d" % (" ".join(cmd), p.returncode))
@@ -112,6 +138,19 @@ def main():
             lines.append("%s, %s: %d frames, K = %d: largest unscrambled peak %.3f, null peaks %.3f .. %.3f, frames above their own "
                          "null maximum: %d" % (name, kind, c["frames"], c["K"], c["unscrambled_max"], c["null_min"], c["null_max"],
                                                c["frames_above_own_null_max"]))
+    for sch, d in doc.get("schemes", {}).items():
+        lines.append("scheme %s: ms per call: median %.2f (range %.2f .. %.2f); / (K searches): %.3f; / scramble in this run: %.3f "
+                     "(what bounds its prep kernel: unmeasured)" % (sch, d["ms"]["median"], d["ms"]["min"], d["ms"]["max"],
+                                                                    d["ratio_over_K_searches"], d["ratio_over_scramble"]))
+        for name in ("noise", "synth_after_remove_stars"):
+            for kind, c in d.get(name, {}).items():
+                lines.append("scheme %s: %s, %s: %d frames, K = %d: largest unscrambled peak %.3f, null peaks %.3f .. %.3f, frames above "
+                             "their own null maximum: %d" % (sch, name, kind, c["frames"], c["K"], c["unscrambled_max"], c["null_min"],
+                                                             c["null_max"], c["frames_above_own_null_max"]))
+    if "rounds" in doc:
+        d = doc["rounds"]
+        lines.append("signflip with %d peel records per frame: ms per call: median %.2f (range %.2f .. %.2f); / (K searches): %.3f"
+                     % (d["n_peel"], d["ms"]["median"], d["ms"]["min"], d["ms"]["max"], d["ratio_over_K_searches"]))
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         f.write("\n".join(lines) + "\n")
