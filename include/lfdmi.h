@@ -413,6 +413,8 @@ int lfdmi_debug_fail_chunk(lfdmi_ctx *ctx, int chunk);
  *                     when the next segment's (frame's) cells no longer fit; one segment (frame) alone always does  (512 MiB)
  *   render_blocks     persistent blocks that walk a chunk's list: the grid is min(pairs of the chunk, render_blocks)   (2048)
  *   stars_rec_bytes   find_stars: bytes of records a chunk returns to the host: max(1, bytes / (max_obj * 32)) frames   (256 MiB)
+ *                     (measure_seeing: bytes of per-record sums of a chunk: max(1, bytes / (max_obj * 64)) frames; its host
+ *                     frames by stage_bytes as find_stars', its chunks of frames in out[0])
  *   stack_part_bytes  stack_profiles: bytes of block sums and counts of one launch: whole segments up to
  *                     max(1, bytes / (8 * bins)) blocks, a single segment that needs more alone                   (128 MiB)
  *                     (a segment takes (a_last >> 5) - (a_first >> 5) + 2 blocks of 32 columns, its two halves apart)
@@ -1585,6 +1587,89 @@ int lfdmi_find_stars(lfdmi_ctx *ctx, const void *frames, int dtype, int n, int h
  * cat->max_obj == max_obj) from n x max_obj records at rec_loc and the n frame records (host).  n at most 32768. */
 int lfdmi_stars_catalog(lfdmi_ctx *ctx, const lfdmi_star *records, int rec_loc, const lfdmi_stars_frame *frame_records, int n,
                         int max_obj, double pixscale, const lfdmi_catalog *cat);
+
+/* ---- frame seeing -------------------------------------------------------------------------------------------------------------
+ * The defocus fit takes a per-trail seeing (lfdmi_fit_defocus: NaN leaves it free), and one cross-section cannot tell seeing
+ * from defocus: both widen it alike.  The frame's stars can: each is an image of the seeing disc.  lfdmi_measure_seeing
+ * measures the second moments of the frame's good stars, as the source finder's records name them, before remove_stars blots
+ * them.  The reference has no such step.  The procedure below is the definition; tests/psf_ref.py restates it in numpy.
+ * Everything that leaves the device is an integer, so the device matches the restatement in every bit; the few doubles of the
+ * host step (5) have a fixed order.
+ *
+ * Input: the frames lfdmi_find_stars saw (buffer rows, not flipped), per frame max_obj records of lfdmi_star and the frame's
+ * lfdmi_stars_frame record (its n_out, 0 .. max_obj, is the number of records read), and the sky sigma of the finder.
+ *
+ * 1. Pixels.  A pixel v enters as q = llrint((double)v * 2^30), as in the light curves (step 1 there).  A pixel is bad when it is
+ *    not finite, is +-0 (what remove_stars or a mask fill blotted) or has |v| > sat.  sat <= 4096, so |q| <= 2^42 and |q - b|
+ *    <= 2^43; with dx^2, dy^2 <= 2^8 and at most 33^2 < 2^11 pixels in a window, every int64 sum below stays under 2^43 * 2^8 *
+ *    2^11 = 2^62 < 2^63 (the ring's sum: at most 65^2 < 2^13 pixels, under 2^55).
+ * 2. Status of record i of a frame, the first rule that applies; H = win + gap + ring:
+ *      LFDMI_PSF_NOT_CANDIDATE  flags != 0, rad == 0, rad > rad_max, or not s_peak >= (float)(k_peak * 3.0 * (double)sigma)
+ *      LFDMI_PSF_CLIPPED        the square |dx|, |dy| <= H around the peak (x, y) leaves the frame
+ *      LFDMI_PSF_CROWDED        another record j < n_out of the frame (whatever its flags) has max(|x_j - x|, |y_j - y|) <= iso
+ *      LFDMI_PSF_BAD_PIXEL      a pixel of the square is bad
+ *      LFDMI_PSF_OK             otherwise
+ * 3. Sums of an OK record, d = max(|dx|, |dy|) the Chebyshev distance from the peak.  Ring, win + gap < d <= H: n_ring pixels,
+ *    Q_ring = sum q, b = Q_ring / n_ring as C divides (towards zero).  Window, d <= win, p = q - b: Q0 = sum p, Qx = sum p dx,
+ *    Qy = sum p dy, Qxx = sum p dx^2, Qyy = sum p dy^2, Qxy = sum p dx dy.  All int64: no order matters.
+ * 4. Frame.  The first max_used OK records in record order are packed into the output (lfdmi_psf_star, index = i; rows past
+ *    n_packed are zero).  n_ok counts the OK records, n_cand those that are not NOT_CANDIDATE, and every status is counted.
+ * 5. Host, in double, every operation rounded (no FMA), for the packed stars in their order:
+ *      mx = Qx / Q0, my = Qy / Q0 (each sum converted to double first); sxx = Qxx / Q0 - mx * mx, syy = Qyy / Q0 - my * my,
+ *      sxy = Qxy / Q0 - mx * my; t = sxx + syy, d = sxx - syy, e = sqrt(d * d + 4.0 * (sxy * sxy)) / t.
+ *    A star is used when Q0 > 0, sxx > 0, syy > 0 and e <= e_max; its width is 2.3548200450309493 * sqrt(t / 2.0)
+ *    (2 sqrt(2 ln 2) times the mean sigma).  fwhm_px = the lower median of the used widths (sorted ascending, element
+ *    (n_used - 1) / 2); scatter = 1.4826 times the lower median of |width - fwhm_px|; ell = the lower median of e.  All three
+ *    are NaN when n_used = 0.  status = LFDMI_SEEING_FEW when n_used < min_stars (fwhm_px is reported all the same; whoever
+ *    hands a seeing to the fit leaves it free then), otherwise LFDMI_SEEING_OK.
+ *    The window truncates a star's wings and the pixel widens it, so fwhm_px is not the seeing FWHM the defocus bank is
+ *    built on: lfd_amd/psf.py (to_bank_seeing) applies this very measurement to noise-free renderings of the bank's S and
+ *    inverts the table.
+ *
+ * The device runs one wavefront per record (k_psf_measure: the rules of step 2 in order, the crowding test with a lane per
+ * other record, the square row by row with the byte swap on load, seven int64 sums added across the wave by shuffles) and one
+ * workgroup per frame for step 4 (k_psf_pack: ballot and prefix count).  No kernel uses an atomic, a transcendental or float
+ * arithmetic beyond the comparison of s_peak.  What bounds either kernel has not been measured. */
+enum { LFDMI_PSF_OK = 0, LFDMI_PSF_NOT_CANDIDATE = 1, LFDMI_PSF_CLIPPED = 2, LFDMI_PSF_CROWDED = 3, LFDMI_PSF_BAD_PIXEL = 4 };
+enum { LFDMI_SEEING_OK = 0, LFDMI_SEEING_FEW = 1 };
+#define LFDMI_PSF_MAX_SAT 4096.0
+typedef struct {
+    double k_peak;            /* a candidate's s_peak in sigmas of S (> 0); default 50 */
+    double e_max;             /* largest ellipticity of a used star (0 .. 1); default 0.2 */
+    double sat;               /* a pixel with |v| above it is bad (> 0, at most LFDMI_PSF_MAX_SAT = the default: off) */
+    int32_t win;              /* half-width of the moment window (1 .. 16); default 7 */
+    int32_t gap;              /* pixels between window and ring (0 .. 8); default 2 */
+    int32_t ring;             /* width of the background ring (1 .. 8); default 3 */
+    int32_t iso;              /* no other record within this Chebyshev distance (1 .. 64); default 12 */
+    int32_t rad_max;          /* largest finder radius of a candidate (1 .. 32); default 16 */
+    int32_t min_stars;        /* fewer used stars: LFDMI_SEEING_FEW (1 .. 1024); default 5 */
+    int32_t max_used;         /* packed stars per frame (1 .. 1024); default 256 */
+    int32_t pad;
+} lfdmi_psf_params;
+typedef struct {
+    int32_t index;            /* the record's index in its frame */
+    int32_t n_ring;
+    int64_t Q0, Qx, Qy, Qxx, Qyy, Qxy, Q_ring;
+} lfdmi_psf_star;
+typedef struct {
+    int32_t status;           /* LFDMI_SEEING_* */
+    int32_t n_cand, n_ok, n_packed, n_used;
+    int32_t n_not_candidate, n_clipped, n_crowded, n_bad_pixel;   /* with n_ok: the frame's n_out records by status */
+    int32_t pad;
+    double fwhm_px, scatter, ell;
+} lfdmi_seeing_frame;
+void lfdmi_default_psf_params(lfdmi_psf_params *out);
+/* frames, dtype, loc, sigma: as lfdmi_find_stars takes them; only read.  records: n x max_obj lfdmi_star at rec_loc (host or
+ * device: the finder's out_loc, so the chain stays on the device); frame_records: the finder's n records, always on the host,
+ * where lfdmi_find_stars writes them and lfdmi_stars_catalog reads them (rec_loc says nothing about them).  p NULL: the
+ * defaults.  out_stars: n x max_used records (host); out_frames: n records (host).  Out-of-range parameters, a sigma that is not
+ * positive, an n_out outside [0, max_obj]: LFDMI_ERR_ARG, and nothing runs.  The call keeps no state (its device memory comes
+ * from the stream's pool and goes back before it returns), refuses while calls are in flight, runs on the context's stream and
+ * waits for it once per chunk of frames.  Chunks: host frames by stage_bytes (1 GiB), host records and the per-record sums by
+ * stars_rec_bytes (256 MiB: max(1, bytes / (max_obj * 64)) frames); lfdmi_debug_unit_split's out[0] counts them. */
+int lfdmi_measure_seeing(lfdmi_ctx *ctx, const void *frames, int dtype, int n, int h, int w, int loc, const float *sigma,
+                         const lfdmi_star *records, int rec_loc, const lfdmi_stars_frame *frame_records, int max_obj,
+                         const lfdmi_psf_params *p, lfdmi_psf_star *out_stars, lfdmi_seeing_frame *out_frames);
 
 #ifdef __cplusplus
 }

@@ -52,6 +52,7 @@ SYMBOLS = (
     "lfdmi_radon_null", "lfdmi_radon_null_scheme",
     "lfdmi_default_stack_params", "lfdmi_stack_profiles",
     "lfdmi_default_stars_params", "lfdmi_find_stars", "lfdmi_stars_catalog",
+    "lfdmi_default_psf_params", "lfdmi_measure_seeing",
 )
 
 
@@ -474,6 +475,30 @@ def make_stars_params(**params):
     return _make_params(StarsParamsStruct, "lfdmi_default_stars_params", "stars", params)
 
 
+class PsfParamsStruct(C.Structure):
+    """lfdmi_psf_params (include/lfdmi.h: frame seeing)."""
+    _fields_ = [("k_peak", C.c_double), ("e_max", C.c_double), ("sat", C.c_double),
+                ("win", C.c_int32), ("gap", C.c_int32), ("ring", C.c_int32), ("iso", C.c_int32), ("rad_max", C.c_int32),
+                ("min_stars", C.c_int32), ("max_used", C.c_int32), ("pad", C.c_int32)]
+
+
+# lfdmi_psf_star: one packed record per OK star of lfdmi_measure_seeing; lfdmi_seeing_frame: one per frame
+PSF_STAR_DTYPE = np.dtype([("index", "<i4"), ("n_ring", "<i4"), ("Q0", "<i8"), ("Qx", "<i8"), ("Qy", "<i8"), ("Qxx", "<i8"),
+                           ("Qyy", "<i8"), ("Qxy", "<i8"), ("Q_ring", "<i8")])
+SEEING_FRAME_DTYPE = np.dtype([("status", "<i4"), ("n_cand", "<i4"), ("n_ok", "<i4"), ("n_packed", "<i4"), ("n_used", "<i4"),
+                               ("n_not_candidate", "<i4"), ("n_clipped", "<i4"), ("n_crowded", "<i4"), ("n_bad_pixel", "<i4"),
+                               ("pad", "<i4"), ("fwhm_px", "<f8"), ("scatter", "<f8"), ("ell", "<f8")])
+PSF_OK, PSF_NOT_CANDIDATE, PSF_CLIPPED, PSF_CROWDED, PSF_BAD_PIXEL = 0, 1, 2, 3, 4
+SEEING_OK, SEEING_FEW = 0, 1
+PSF_MAX_SAT = 4096.0
+PSF_MAX_USED = 1024
+
+
+def make_psf_params(**params):
+    """lfdmi_default_psf_params with the given fields replaced (unknown names raise)."""
+    return _make_params(PsfParamsStruct, "lfdmi_default_psf_params", "psf", params)
+
+
 def make_radon_params(**params):
     """lfdmi_default_radon_params with the given fields replaced (unknown names raise)."""
     return _make_params(RadonParamsStruct, "lfdmi_default_radon_params", "radon", params)
@@ -584,6 +609,10 @@ def lib():
         _lib.lfdmi_find_stars.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_int, C.c_void_p]
         _lib.lfdmi_stars_catalog.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p]
+        _lib.lfdmi_default_psf_params.restype = None
+        _lib.lfdmi_default_psf_params.argtypes = [C.c_void_p]
+        _lib.lfdmi_measure_seeing.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.lfdmi_debug_unit_limits.argtypes = [C.c_void_p, C.c_void_p]
         _lib.lfdmi_debug_unit_split.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     return _lib
@@ -1560,6 +1589,32 @@ class Context:
         self._chk(self._lib.lfdmi_stars_catalog(self._h, _ptr(records), DEVICE if _is_dev(records) else HOST, _ptr(frec), n, m,
                                                 float(pixscale), C.byref(c)))
         return cat
+
+    # -- frame seeing (lfdmi_measure_seeing) ---------------------------------------------------------------------------------------
+    def measure_seeing(self, frames, records, frame_records, sigma=None, pinned=False, native_device=False, **params):
+        """The second moments of every frame's good stars and the frame's PSF width (include/lfdmi.h: frame seeing).  frames,
+        sigma: what ``find_stars`` took; records, frame_records: what it returned (numpy, or its device tensor with
+        device_out=True).  Returns (PSF_STAR_DTYPE records [n, max_used], SEEING_FRAME_DTYPE records [n])."""
+        frames, code, n, h, w, loc = self._frames(frames, pinned, "measure_seeing", native_device=native_device)
+        p = make_psf_params(**params)
+        sig = _sigma(sigma, n)
+        frec = np.ascontiguousarray(frame_records, STARS_FRAME_DTYPE).reshape(-1)
+        if len(frec) != n:
+            raise ValueError("measure_seeing: one frame record per frame")
+        if _is_dev(records):
+            if int(records.shape[0]) != n:
+                raise ValueError("measure_seeing: records of another number of frames")
+            m = int(records.shape[1])
+        else:
+            records = np.ascontiguousarray(records, STAR_DTYPE)
+            records = records.reshape(n, -1) if n else records.reshape(0, 1)
+            m = records.shape[1]
+        mu = max(1, min(int(p.max_used), PSF_MAX_USED))
+        out = np.zeros((n, mu), PSF_STAR_DTYPE)
+        ofr = np.zeros(n, SEEING_FRAME_DTYPE)
+        self._chk(self._lib.lfdmi_measure_seeing(self._h, _ptr(frames), code, n, h, w, loc, _ptr(sig), _ptr(records),
+                                                 DEVICE if _is_dev(records) else HOST, _ptr(frec), m, C.byref(p), _ptr(out), _ptr(ofr)))
+        return out, ofr
 
     def pinned_buffer(self, nbytes):
         """Page-locked host memory next to this context's GPU (lfdmi_host_alloc) as a ``PinnedBuffer``."""

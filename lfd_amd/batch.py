@@ -378,3 +378,14 @@ class BatchDetector:
         while self.ctx.calls_in_flight():
             self.ctx._end_oldest()
         return self.ctx.fit_defocus(bank, trails, profiles, seeing, **kw)
+
+    def measure_seeing(self, frames, sigma=None, stars_params=None, **params):
+        """``psf.measure_seeing`` (the source finder with its records left on the device, then ``Context.measure_seeing``) on the
+        first lane's context.  With calls in flight it runs after them, as ``fit_defocus`` does."""
+        from . import psf
+        for f in list(self._pending):
+            f.result()
+        self._pending = []
+        while self.ctx.calls_in_flight():
+            self.ctx._end_oldest()
+        return psf.measure_seeing(self.ctx, frames, sigma=sigma, stars_params=stars_params, **params)

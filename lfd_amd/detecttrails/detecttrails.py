@@ -152,9 +152,10 @@ class _DefocusTee:
     (defocus.txt beside it) every row is also fitted (include/lfdmi.h: defocus fit): the rows added since the last ``flush``
     are fitted in one call and their defocus rows written in the same order."""
 
-    def __init__(self, profiles, out, defocus_params, trail_params):
+    def __init__(self, profiles, out, defocus_params, trail_params, seeing=None):
         self.profiles, self.out = profiles, out
         self.defocus_params, self.trail_params = defocus_params, trail_params
+        self.seeing = seeing                          # a ``_SeeingStage``: every fit gets its frame's seeing (NaN: free)
         self.pending = []
 
     def add(self, key, trail, profile):
@@ -167,7 +168,8 @@ class _DefocusTee:
         if self.pending:
             ctx, bank = defocus_bank(self.defocus_params, self.trail_params)
             trails = _np.array([t for _, t, _ in self.pending], _native.TRAIL_DTYPE)
-            fit = ctx.fit_defocus(bank, trails, _np.stack([p for _, _, p in self.pending]))
+            see = None if self.seeing is None else [self.seeing.seeing_of(k) for k, _, _ in self.pending]
+            fit = ctx.fit_defocus(bank, trails, _np.stack([p for _, _, p in self.pending]), see)
             self.out.write("".join(defocus.format_row(k, f) + "\n" for (k, _, _), f in zip(self.pending, fit)))
             self.pending = []
         self.profiles.flush()
@@ -231,6 +233,7 @@ class _StarsStage:
     def batch(self, ctx, frames, pixscale, **where):
         """the frames where the detect call will read them -> (device-resident catalogue, [(frame record, n_extended)])"""
         rec, frec = ctx.find_stars(frames, sigma=self.sigma, device_out=True, **where, **self.params)
+        self.last = (rec, frec)                       # (``_SeeingStage`` measures on them)
         import torch
         n_ext = (rec.view(torch.int32).reshape(len(frec), -1, 8)[:, :, 3] & _native.STAR_EXTENDED).sum(1).cpu().numpy()
         return ctx.stars_catalog(rec, frec, pixscale, device=True), [(frec[j], int(n_ext[j])) for j in range(len(frec))]
@@ -240,6 +243,7 @@ class _StarsStage:
         from ..stars import n_extended, to_catalog
         with use_context(*img.shape) as ctx:
             rec, frec = ctx.find_stars(img, sigma=self.sigma, **self.params)
+        self.last = (rec, frec)
         cat = to_catalog(rec, frec, pixscale)
         k = int(cat["count"][0])
         return {key: v[0, :k] for key, v in cat.items() if key != "count"}, (frec[0], int(n_extended(rec, frec)[0]))
@@ -250,6 +254,58 @@ class _StarsStage:
 
     def flush(self):
         self.out.flush()
+
+
+class _SeeingStage:
+    """The frame seeing in front of detection for ``DetectTrails(seeing=True)`` (include/lfdmi.h: frame seeing): each chunk's
+    stars are measured before remove_stars blots them (after the sky normalisation when that is on), on the records the source
+    finder left on the device -- ``_StarsStage``'s with ``find_stars=True``, otherwise a finder run of its own -- and seeing.txt
+    gets a row per frame.  ``seeing_of(key)`` is what the defocus fits of that frame get: the width as the bank's seeing, NaN
+    for a frame with too few stars or without a measurement."""
+
+    def __init__(self, out, params, sigma, stars_params, pixscale, seeings):
+        from ..psf import PsfParams, as_params
+        from ..stars import as_params as stars_as_params
+        self.out, self.params, self.sigma = out, as_params(params), float(sigma)
+        self.stars_params, self.pixscale = stars_as_params(stars_params), float(pixscale)
+        self.grid = _np.sort(_np.asarray(seeings, _np.float64).reshape(-1))
+        self.full = PsfParams(**self.params)
+        self.by_key = {}
+
+    def _records(self, frec):
+        from ..psf import SEEING_FEW, to_bank_seeing
+        see = _np.atleast_1d(to_bank_seeing(frec["fwhm_px"], self.pixscale, self.full.win, self.grid, self.full.gap, self.full.ring))
+        see = _np.where(frec["status"] == SEEING_FEW, _np.nan, see)
+        return [(frec[j], float(see[j])) for j in range(len(frec))]
+
+    def batch(self, ctx, frames, found=None, **where):
+        """the frames where the detect call will read them, before it blots them -> [(frame record, seeing_arcsec)]"""
+        if found is None:
+            found = ctx.find_stars(frames, sigma=self.sigma, device_out=True, **where, **self.stars_params)
+        return self._records(ctx.measure_seeing(frames, found[0], found[1], sigma=self.sigma, **where, **self.params)[1])
+
+    def one(self, img, found=None):
+        """one host frame, not blotted yet -> (frame record, seeing_arcsec)"""
+        img = _np.ascontiguousarray(img, _np.float32)
+        with use_context(*img.shape) as ctx:
+            if found is None:
+                found = ctx.find_stars(img, sigma=self.sigma, **self.stars_params)
+            return self._records(ctx.measure_seeing(img, found[0], found[1], sigma=self.sigma, **self.params)[1])[0]
+
+    def note(self, key, rec):
+        self.by_key[tuple(key)] = rec[1]
+
+    def seeing_of(self, key):
+        return self.by_key.get(tuple(key)[:4], float("nan"))
+
+    def row(self, key, frec, see):
+        from ..psf import format_row
+        self.out.write(format_row(key, frec, self.pixscale, see) + "\n")
+
+    def flush(self):
+        """after the chunk's fits: its frames' seeings are no longer needed"""
+        self.out.flush()
+        self.by_key = {}
 
 
 class _ShortRecord:
@@ -309,6 +365,7 @@ class _RadonStage:
         self.lines_params = dict(lines_params or {}, max_lines=lines) if lines is not None else None
         self.prof_out, self.stack_params = prof_out, dict(stack_params or {})
         self.defocus_out, self.defocus_params, self.pending = defocus_out, defocus_params, []
+        self.seeing = None                            # a ``_SeeingStage``, set by the driver: the fits get their frame's seeing
 
     def _search(self, handle, frames, **where):
         """the records of a run of frames; with ``lc`` the found lines' light curves too, measured here, where the search and the
@@ -559,7 +616,8 @@ class _RadonStage:
                       "wing": self.stack_params.get("wing", 8), "pixscale": self.stack_params.get("pixscale", 0.396)}
                 ctx, bank = defocus_bank(self.defocus_params, tp)
                 trails = to_trails(_np.array([r for _, r, _ in self.pending], _native.STACK_DTYPE))
-                fit = ctx.fit_defocus(bank, trails, _np.stack([p for _, _, p in self.pending]))
+                see = None if self.seeing is None else [self.seeing.seeing_of(k) for k, _, _ in self.pending]
+                fit = ctx.fit_defocus(bank, trails, _np.stack([p for _, _, p in self.pending]), see)
                 self.defocus_out.write("".join(defocus.format_row(k, f) + "\n" for (k, _, _), f in zip(self.pending, fit)))
                 self.pending = []
             self.defocus_out.flush()
@@ -873,8 +931,10 @@ class _Chunk:
     per-frame product gets a slot here, a step in ``_run_group`` and ``_run_frame``, and its row in ``_emit``."""
 
     def __init__(self, n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon=None,
-                 stars=None, masks=None, lc=None, strip=None, sub=None):
+                 stars=None, masks=None, lc=None, strip=None, sub=None, seeing=None):
         self.results, self.errors, self.profiles, self.sky, self.radon, self.stars = results, errors, profiles, sky, radon, stars
+        self.seeing = seeing                          # a ``_SeeingStage``; ``seerecs[i]``: (frame record, seeing_arcsec) or the exception
+        self.seerecs = [None] * n
         self.sub = sub                                # a ``_SubStage``; ``subs[i]``: (source, [(record, segment)], frame) or the exception
         self.subs = [None] * n
         self.masks = masks                            # a ``_MaskStage``: its rows are made in ``_emit``, from the slots below
@@ -914,6 +974,12 @@ def _run_frame(c, i, filter, frame):
             img, c.srecs[i] = c.sky.one(img)
         if c.stars is not None:
             cat, c.strecs[i] = c.stars.one(img, c.params_removestars["pixscale"])
+        if c.seeing is not None:                      # before the frame is blotted
+            try:
+                c.seerecs[i] = c.seeing.one(img, c.stars.last if c.stars is not None else None)
+                c.seeing.note(c.keys[i], c.seerecs[i])
+            except Exception as e:  # noqa: BLE001
+                c.seerecs[i] = e
         c.rows[i] = process_frame_arrays(img, cat, filter, c.params_bright, c.params_dim, c.params_removestars)
         if c.profiles is not None and c.rows[i][0]:
             try:
@@ -987,6 +1053,15 @@ def _run_group(c, idx, filter, shape, inflight, source, second, detect_kw=None, 
                 packed, strecs = c.stars.batch(ctx, frames, rs.pixscale, **detect_kw)
                 for j, i in enumerate(idx):
                     c.strecs[i] = strecs[j]
+            if c.seeing is not None:                  # before the detect call blots the frames
+                try:
+                    seerecs = c.seeing.batch(ctx, frames, c.stars.last if c.stars is not None else None, **detect_kw)
+                    for j, i in enumerate(idx):
+                        c.seerecs[i] = seerecs[j]
+                        c.seeing.note(c.keys[i], seerecs[j])
+                except Exception as e:  # noqa: BLE001
+                    for i in idx:
+                        c.seerecs[i] = e
             recs = ctx.detect_batch(frames, c.params_bright, c.params_dim, packed, rs, **detect_kw)
             c.gpu_s += time.perf_counter() - t0
             if c.profiles is not None:
@@ -1072,6 +1147,10 @@ def _emit(c, i, key, head, shape):
         c.sky.row(key, c.srecs[i])
     if c.strecs[i] is not None:
         c.stars.row(key, *c.strecs[i])
+    if isinstance(c.seerecs[i], Exception):
+        _log_error(c.errors, key, c.seerecs[i], c.debug)
+    elif c.seerecs[i] is not None:
+        c.seeing.row(key, *c.seerecs[i])
     try:
         row = c.rows[i]
         if isinstance(row, Exception):
@@ -1136,7 +1215,7 @@ def _emit(c, i, key, head, shape):
 
 def process_field(results, errors, run, camcol, filter, field, params_bright, params_dim,
                   params_removestars, profiles=None, trail_params=None, sky=None, radon=None, stars=None, masks=None, lc=None,
-                  strip=None, sub=None):
+                  strip=None, sub=None, seeing=None):
     """One frame end to end (reference: detecttrails.py:30-143): locate the frame (or its .bz2),
     read image + header + photoObj, detect, append ``run camcol filter field tai crpix1 crpix2
     crval1 crval2 cd11 cd12 cd21 cd22 x1 y1 x2 y2`` to ``results``; every exception is logged
@@ -1147,7 +1226,8 @@ def process_field(results, errors, run, camcol, filter, field, params_bright, pa
     ``_StarsStage``; the photoObj file is not opened, the catalogue is what the source finder finds in the frame (after the
     normalisation, if on), and the frame's stars.txt row is written.  ``masks``: a ``_MaskStage``; a results row, and every found
     faint line of ``radon`` with lines, gets its masks.txt row."""
-    c = _Chunk(1, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon, stars, masks, lc, strip, sub)
+    c = _Chunk(1, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon, stars, masks, lc, strip, sub,
+               seeing)
     c.keys[0] = (run, camcol, filter, field)
     head = None
     try:
@@ -1192,7 +1272,7 @@ def process_fields_batched(results, errors, ids, params_bright, params_dim, para
 
 
 def process_loaded(results, errors, loaded, params_bright, params_dim, params_removestars, profiles=None, trail_params=None, sky=None,
-                   radon=None, stars=None, masks=None, lc=None, strip=None, sub=None):
+                   radon=None, stars=None, masks=None, lc=None, strip=None, sub=None, seeing=None):
     """process_fields_batched for a chunk the loader has read (``loader.Loaded``): the frames that sit in pinned memory go to
     the GPU as contiguous same-filter slices of that memory with the matching rows of the padded catalogue arrays (no copy
     of a frame on the host, no per-frame Python), the others take the per-frame path; rows and errors entries come out in
@@ -1207,7 +1287,8 @@ def process_loaded(results, errors, loaded, params_bright, params_dim, params_re
     import time
     t_in = time.perf_counter()
     n = len(loaded.keys)
-    c = _Chunk(n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon, stars, masks, lc, strip, sub)
+    c = _Chunk(n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon, stars, masks, lc, strip, sub,
+               seeing)
     c.keys = list(loaded.keys)
     by_slot = {}
     for i in range(n):
@@ -1280,6 +1361,13 @@ class DetectTrails:
     otherwise 0.025).  ``stars_file`` (default ``<savepath>/stars.txt``) gets one row per frame that loaded: ``run camcol
     filter field status n_found n_out n_extended``; rank files, resume and ``Jobs`` treat it like sky.txt.  Every other output of
     a run without ``find_stars`` stays byte for byte what it is.
+    ``seeing=True`` (default off): every chunk's stars are measured before detection blots them (include/lfdmi.h: frame
+    seeing; ``seeing_params``: dict or ``lfd_amd.psf.PsfParams``), on the finder's device records with ``find_stars=True`` and
+    on a finder run of its own (``stars_params``) otherwise.  ``seeing_file`` (default ``<savepath>/seeing.txt``) gets one row
+    per frame that loaded: ``run camcol filter field status n_cand n_ok n_used fwhm_px fwhm_arcsec seeing_arcsec scatter
+    ell``.  With ``defocus=True`` every fit behind defocus.txt and radon_defocus.txt gets its frame's ``seeing_arcsec`` as
+    ``fit_defocus``'s ``seeing`` (NaN, a free fit, for a frame with too few stars).  Rank files, resume and ``Jobs`` treat
+    seeing.txt like stars.txt; a run without ``seeing`` stays byte for byte what it is.
     ``radon=True`` (default off): after each chunk's detection call the frames WITHOUT a detection are searched for a trail that
     is faint in every pixel but long (include/lfdmi.h: faint-trail search; ``radon_params``: dict or
     ``lfd_amd.radon.RadonParams``), with the sky sigma ``target_sigma`` under ``normalize=True`` and 0.025 otherwise.  A line
@@ -1382,6 +1470,10 @@ class DetectTrails:
         self.stars_file = kwargs.get("stars_file", os.path.join(save, "stars.txt"))
         from ..stars import as_params as stars_as_params
         self.stars_params = stars_as_params(kwargs.get("stars_params"))    # (out-of-range values raise here, not per frame)
+        self.seeing = bool(kwargs.get("seeing", False))
+        self.seeing_file = kwargs.get("seeing_file", os.path.join(save, "seeing.txt"))
+        from ..psf import as_params as psf_as_params
+        self.seeing_params = psf_as_params(kwargs.get("seeing_params"))  # (likewise)
         self.radon = bool(kwargs.get("radon", False))
         self.radon_file = kwargs.get("radon_file", os.path.join(save, "radon.txt"))
         from ..radon import as_params as radon_as_params
@@ -1628,7 +1720,8 @@ class DetectTrails:
                 (open(self.profiles + suffix, "a") if self.trail_profiles else contextlib.nullcontext()) as profiles, \
                 (open(self.defocus_file + suffix, "a") if self.defocus else contextlib.nullcontext()) as defocus_out, \
                 (open(self.sky_file + suffix, "a") if self.normalize else contextlib.nullcontext()) as sky_out, \
-                (open(self.stars_file + suffix, "a") if self.find_stars else contextlib.nullcontext()) as stars_out, \
+                _both(open(self.stars_file + suffix, "a") if self.find_stars else contextlib.nullcontext(),
+                      open(self.seeing_file + suffix, "a") if self.seeing else contextlib.nullcontext()) as (stars_out, seeing_out), \
                 (open(self.radon_file + suffix, "a") if self.radon else contextlib.nullcontext()) as radon_out, \
                 (open(self.radon_segments_file + suffix, "a") if self.radon and self.radon_lines is not None
                  else contextlib.nullcontext()) as segments_out, \
@@ -1647,8 +1740,16 @@ class DetectTrails:
                 (open(self.lightcurve_summary_file + suffix, "a") if self.light_curves else contextlib.nullcontext()) as lcsum_out, \
                 _both(open(self.strips_file + suffix, "a") if self.trail_strips else contextlib.nullcontext(),
                       open(self.subtracted_file + suffix, "a") if self.subtract_trails else contextlib.nullcontext()) as (strips_out, sub_out):
+            seeing = None
+            if self.seeing:
+                sigma = _native.make_sky_params(**self.sky_params).target_sigma if self.normalize else 0.025
+                grid = self.defocus_params.get("seeings")
+                if grid is None:
+                    from ..defocus import default_params as defocus_defaults
+                    grid = defocus_defaults()["seeings"]
+                seeing = _SeeingStage(seeing_out, self.seeing_params, sigma, self.stars_params, self.params_removestars["pixscale"], grid)
             if self.trail_profiles:
-                profiles = _DefocusTee(profiles, defocus_out, self.defocus_params, self.trail_params)
+                profiles = _DefocusTee(profiles, defocus_out, self.defocus_params, self.trail_params, seeing)
             prof_kw = {"profiles": profiles, "trail_params": self.trail_params} if self.trail_profiles else {}
             sky = _SkyStage(sky_out, self.sky_params) if self.normalize else None
             if sky is not None:
@@ -1672,6 +1773,10 @@ class DetectTrails:
                                                        segments_out, rprof_out, self.stack_params, rdef_out, self.defocus_params,
                                                        self.radon_short, short_out, lc, self.radon_wide, wide_out, strip,
                                                        self.radon_null, null_out, fap_out, self.radon_null_scheme, rounds_out)
+            if seeing is not None:
+                prof_kw["seeing"] = seeing
+                if radon is not None:
+                    radon.seeing = seeing
             masks = None
             if self.trail_masks:
                 masks = prof_kw["masks"] = _MaskStage(masks_out, self.mask_params, self.mask_dir)
@@ -1693,6 +1798,8 @@ class DetectTrails:
                     stars.flush()
                 if radon is not None:
                     radon.flush()
+                if seeing is not None:                # (after the fits of profiles and radon, which ask it for their frames' seeing)
+                    seeing.flush()
                 if masks is not None:
                     masks.flush()
                 if lc is not None:
