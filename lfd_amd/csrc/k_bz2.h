@@ -588,8 +588,9 @@ k_bz2_rle_tiles(const BzBlockInfo *info, const uint8_t *prebuf, int4 *meta, int4
     if (t == 1023) tile_fn[ti] = make_int4(c0, c1, z0, z1);
 }
 
-// per block: the tiles in order -> every tile's entry state and output offset inside the block, and the block's size
-__global__ void k_bz2_rle_blocks(const BzBlockInfo *info, const int4 *tile_fn, int2 *tile_in, int *blk_size, int nblocks) {
+// per block: the tiles in order -> every tile's entry state and output offset inside the block, and the block's size.  A block
+// whose last tile leaves c = 1 ends right after four equal bytes, with no count behind them: libbz2 rejects that, so it is declined.
+__global__ void k_bz2_rle_blocks(BzBlockInfo *info, const int4 *tile_fn, int2 *tile_in, int *blk_size, int nblocks) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= nblocks) return;
     int c = 0, off = 0;
@@ -602,6 +603,7 @@ __global__ void k_bz2_rle_blocks(const BzBlockInfo *info, const int4 *tile_fn, i
             off += c ? f.w : f.z;
             c = c ? f.y : f.x;
         }
+        if (c) info[b].status = BZ_E_DATA;
     }
     blk_size[b] = off;
 }

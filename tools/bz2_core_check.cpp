@@ -89,7 +89,10 @@ int main(int argc, char **argv) {
             out.push_back(v);
             int kk = 1;
             while (p < n && kk < 4 && pre[p] == v) { out.push_back(v); p++; kk++; }
-            if (kk == 4 && p < n) out.insert(out.end(), pre[p++], v);
+            if (kk == 4) {
+                if (p >= n) { fprintf(stderr, "block %zu: ends after four equal bytes, no count\n", b); return 4; } // (libbz2 rejects it)
+                out.insert(out.end(), pre[p++], v);
+            }
         }
         uint32_t c = 0xffffffffu;
         for (uint8_t x : out) c = (c << 8) ^ crc_tab[(c >> 24) ^ x];
