@@ -1671,6 +1671,64 @@ int lfdmi_measure_seeing(lfdmi_ctx *ctx, const void *frames, int dtype, int n, i
                          const lfdmi_star *records, int rec_loc, const lfdmi_stars_frame *frame_records, int max_obj,
                          const lfdmi_psf_params *p, lfdmi_psf_star *out_stars, lfdmi_seeing_frame *out_frames);
 
+/* ---- detection rounds -------------------------------------------------------------------------------------------------------
+ * lfdmi_detect_batch* reports at most one trail per frame: process_field_bright / _dim stop at the first line set that passes,
+ * as the reference does.  lfdmi_detect_rounds reports up to max_trails: it detects, blots the band of every line found so far
+ * on a work copy of the frame, and detects again, until a round finds nothing.  It is built from pieces that exist: a round is
+ * the plain lfdmi_detect_batch_raw; a band is the trail masks' band (steps 2 and 3 there); a pixel set to +0 is blotted for the
+ * detector exactly as a remove_stars square is.  The reference has no such step.  The procedure below is the definition;
+ * tests/rounds_ref.py restates it with the oracle's detector and tests/mask_ref.py's membership, and the device reproduces it
+ * field for field.
+ *
+ * params = {max_trails 1 .. LFDMI_ROUNDS_MAX_TRAILS (default 4); half, finite and >= 0 (default 10.0: masks.half_width without a
+ * measurement); dup_dist, finite and >= 0 (default 20.0)}; NULL: the defaults.  Outputs, all on the host: records
+ * [n][max_trails] lfdmi_result, n_found [n] int32, dup_of [n][max_trails] int32.
+ *
+ * 1. Round 0 is lfdmi_detect_batch_raw(ctx, frames, dtype, n, h, w, cat, rs, bright, dim, ., loc), unchanged: records[i][0] is
+ *    its record, byte for byte, and the caller's frames end the whole call in exactly the state that plain call leaves them in
+ *    (blotted, swapped in place or untouched, by dtype and loc).  No band is ever written into the caller's frames.
+ * 2. A record counts as found when status == 0 && found != 0.  Frame i continues into round k >= 1 when its records 0 .. k-1
+ *    are all found and k < max_trails.  n_found[i] = the number of leading found records.  The record at n_found[i], if there
+ *    is one, is the round that found nothing (or failed), kept as returned; the records after it are zero-filled.
+ * 3. records[i][k] of a frame that continues is exactly what lfdmi_detect_batch_raw returns for the modified frame i and the
+ *    same catalogue entry.  The modified frame is frame i as native float32 with every pixel inside the band of any line
+ *    0 .. k-1 set to +0.0f.  Band j has the trail masks' geometry and membership (steps 2 and 3 of that section) for the
+ *    segment (x1, y1) - (x2, y2) of record j converted to double (flipped-frame coordinates), with this call's half and
+ *    cap = +inf: the whole line.  A record whose segment the masks would call bad (L == 0, a coordinate beyond 1e6) has no band.
+ * 4. dup_of[i][k], for a found record k >= 1: the smallest j < k such that both end points (x1, y1) and (x2, y2) of record k
+ *    satisfy |u| <= dup_dist, u the trail masks' step-3 expression against record j's segment, evaluated on the host in double;
+ *    -1 when there is none, for k = 0 and for every record that is not found.  The end points of a record lie about 1000 px off
+ *    the image along the line, so the test means "nearly the same line, within a fraction of a degree": what the wings of a
+ *    trail give once the band is narrower than the trail.  dup_of is a label only; it changes no control flow.
+ * 5. max_trails == 1 is the plain call and allocates nothing.  Refused before any work, the call named in the message and no
+ *    output written: with LFDMI_ERR_ARG a bad params field, NULL outputs, a dtype other than LFDMI_F32 / LFDMI_F32_BE, calls in
+ *    flight; with its own code everything lfdmi_detect_batch_raw refuses (its message follows "lfdmi_detect_rounds: ").
+ *
+ * Every round k >= 1 gathers from the caller's frames with all bands 0 .. k-1 (k_rounds_gather): the m frames that continue go
+ * to work slots 0 .. m-1 in frame order, byte-swapped when the source is big-endian, +0 where a band holds the pixel centre, in
+ * one pass of 4 B read and 4 B written per pixel.  No slot is compacted onto another.  Host and pinned frames: only the frames
+ * that continue are uploaded, straight into their slots, and the kernel runs in place.  The band geometry (x1, y1, e, nrm, half,
+ * at most 7 per slot) comes from the host as doubles; the device evaluates no division and no transcendental function.  A
+ * workgroup owns a 256 x 16 tile, tests it conservatively against each band as k_mask_cull does, copies a tile no band reaches
+ * with 16 B accesses and evaluates the membership per pixel, in double, left to right, uncontracted, in the others.  Rows that
+ * start off a 16 B boundary (h * w % 4 != 0) get their head and tail with 4 B accesses.  The round then calls
+ * lfdmi_detect_batch_raw(ctx, work, LFDMI_F32, m, h, w, cat_m, rs, bright, dim, ., LFDMI_DEVICE) with the catalogue compacted to
+ * the m frames where it lives (a host gather or device copies); blotting a blotted pixel again changes nothing, so this one
+ * route serves every dtype and loc.  The work buffer and the compacted device arrays come from the stream's pool, sized by m,
+ * and go back after the round.  Later rounds cost what the frames still alive cost.  The call refuses while calls are in
+ * flight and is synchronous; there is no non-blocking twin and no multi-scale form. */
+#define LFDMI_ROUNDS_MAX_TRAILS 8
+typedef struct {
+    int32_t max_trails;       /* 1 .. LFDMI_ROUNDS_MAX_TRAILS; default 4 */
+    int32_t pad;
+    double half;              /* half-width of a found line's band in px (finite, >= 0); default 10.0 */
+    double dup_dist;          /* step 4 (finite, >= 0); default 20.0 */
+} lfdmi_rounds_params;
+void lfdmi_default_rounds_params(lfdmi_rounds_params *out);
+int lfdmi_detect_rounds(lfdmi_ctx *ctx, void *frames, int dtype, int n, int h, int w, const lfdmi_catalog *cat,
+                        const lfdmi_rs_params *rs, const lfdmi_params *bright, const lfdmi_params *dim,
+                        const lfdmi_rounds_params *params, lfdmi_result *records, int32_t *n_found, int32_t *dup_of, int loc);
+
 #ifdef __cplusplus
 }
 #endif

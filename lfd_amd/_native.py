@@ -53,6 +53,7 @@ SYMBOLS = (
     "lfdmi_default_stack_params", "lfdmi_stack_profiles",
     "lfdmi_default_stars_params", "lfdmi_find_stars", "lfdmi_stars_catalog",
     "lfdmi_default_psf_params", "lfdmi_measure_seeing",
+    "lfdmi_default_rounds_params", "lfdmi_detect_rounds",
 )
 
 
@@ -499,6 +500,19 @@ def make_psf_params(**params):
     return _make_params(PsfParamsStruct, "lfdmi_default_psf_params", "psf", params)
 
 
+class RoundsParamsStruct(C.Structure):
+    """lfdmi_rounds_params (include/lfdmi.h: detection rounds)."""
+    _fields_ = [("max_trails", C.c_int32), ("pad", C.c_int32), ("half", C.c_double), ("dup_dist", C.c_double)]
+
+
+ROUNDS_MAX_TRAILS = 8
+
+
+def make_rounds_params(**params):
+    """lfdmi_rounds_params: the library's defaults with the given fields replaced (unknown names raise)"""
+    return _make_params(RoundsParamsStruct, "lfdmi_default_rounds_params", "rounds", params)
+
+
 def make_radon_params(**params):
     """lfdmi_default_radon_params with the given fields replaced (unknown names raise)."""
     return _make_params(RadonParamsStruct, "lfdmi_default_radon_params", "radon", params)
@@ -613,6 +627,10 @@ def lib():
         _lib.lfdmi_default_psf_params.argtypes = [C.c_void_p]
         _lib.lfdmi_measure_seeing.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                               C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.lfdmi_default_rounds_params.restype = None
+        _lib.lfdmi_default_rounds_params.argtypes = [C.c_void_p]
+        _lib.lfdmi_detect_rounds.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         _lib.lfdmi_debug_unit_limits.argtypes = [C.c_void_p, C.c_void_p]
         _lib.lfdmi_debug_unit_split.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     return _lib
@@ -1246,6 +1264,27 @@ class Context:
                                                    C.byref(rs) if rs is not None else None,
                                                    C.byref(pb), C.byref(pd), _ptr(res), loc))
         return res
+
+    # -- detection rounds (lfdmi_detect_rounds) --------------------------------------------------------------------------------
+    def detect_rounds(self, frames, params_bright, params_dim, cat=None, rs=None, pinned=False, **params):
+        """Up to ``max_trails`` trails per frame (include/lfdmi.h: detection rounds): ``detect_batch``, then the band of every
+        line found so far blotted on a work copy of the frames that found one, and ``detect_batch`` again.  frames, cat, rs,
+        pinned: as ``detect_batch`` takes them, and the frames are left as it leaves them.  params: max_trails, half, dup_dist.
+        Returns (RESULT_DTYPE records [n, max_trails], int32 n_found [n], int32 dup_of [n, max_trails])."""
+        frames, code, n, h, w, loc = self._frames(frames, pinned, "detect_rounds")
+        p = make_rounds_params(**params)
+        pb, k1 = make_params(params_bright)
+        pd, k2 = make_params(params_dim, dim=True)
+        c, k3 = self._catalog(cat)
+        K = max(1, int(p.max_trails))
+        rec = np.zeros((n, K), RESULT_DTYPE)
+        n_found = np.zeros(n, np.int32)
+        dup_of = np.full((n, K), -1, np.int32)
+        self._chk(self._lib.lfdmi_detect_rounds(self._h, _ptr(frames), code, n, h, w,
+                                                C.byref(c) if c is not None else None,
+                                                C.byref(rs) if rs is not None else None,
+                                                C.byref(pb), C.byref(pd), C.byref(p), _ptr(rec), _ptr(n_found), _ptr(dup_of), loc))
+        return rec, n_found, dup_of
 
     # -- calls in flight (lfdmi_detect_batch_begin / lfdmi_process_multiscale_begin / lfdmi_end_oldest) ---------------------------
     def calls_in_flight(self):

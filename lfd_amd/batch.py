@@ -337,6 +337,28 @@ class BatchDetector:
                 for c, (a, b) in zip(self.ctxs, bounds) if b > a]
         return np.concatenate([f.result() for f in futs])
 
+    def detect_rounds(self, frames, params_bright, params_dim, catalogs=None, rs=None, pinned=False, rounds_params=None):
+        """``detect`` for up to ``max_trails`` trails per frame (include/lfdmi.h: detection rounds; rounds_params: a dict of
+        lfdmi_rounds_params fields, None = the defaults): (records [n, max_trails], n_found [n], dup_of [n, max_trails]), record
+        0 being ``detect``'s.  Sharded over the lanes like ``detect``; with calls in flight it runs after them.  Not routed
+        through ``sky=``."""
+        from .rounds import as_params
+        rp = as_params(rounds_params)
+        if self.sky is not None:
+            raise RuntimeError("detect_rounds is not routed through sky=: normalise the frames first")
+        if self._finds(catalogs, rs):
+            catalogs, self.last_stars = self._found_catalog(frames, rs)
+        if self.lanes == 1:
+            self._drain()
+            return self.ctx.detect_rounds(frames, params_bright, params_dim, catalogs, rs, pinned=pinned, **rp)
+        n = frames.shape[0]
+        bounds = shard_bounds(n, self.lanes)
+        futs = [self.pool.submit(lambda c=c, a=a, b=b: c.detect_rounds(frames[a:b], params_bright, params_dim,
+                                                                      self._slice_cat(catalogs, a, b), rs, pinned=pinned, **rp))
+                for c, (a, b) in zip(self.ctxs, bounds) if b > a]
+        res = [f.result() for f in futs]
+        return tuple(np.concatenate([r[j] for r in res]) for j in range(3))
+
     def measure_trails(self, frames, records, catalogs=None, rs=None, **params):
         """``Context.measure_trails`` over the batch (trail profiles of the frames whose record has found != 0), sharded like
         ``detect``.  With calls in flight it runs after them: the calls that produced ``records`` have ended by then.

@@ -84,6 +84,17 @@ def process_frame_arrays(img, cat, filter, params_bright, params_dim, params_rem
     return _detection(rec, img.shape)
 
 
+def _frame_rounds(img, cat, filter, params_bright, params_dim, params_removestars, rounds_params):
+    """``process_frame_arrays`` through ``detect_rounds``: (what it returns for record 0, (records [K], n_found, dup_of [K]))"""
+    if img.dtype != _np.float32 or not img.flags.c_contiguous:
+        raise TypeError("process_frame_arrays needs a C-contiguous float32 frame")
+    packed = _pack_one(cat)
+    rs = _rs_struct(filter, params_removestars) if packed is not None else None
+    with use_context(*img.shape) as ctx:
+        recs, nf, dup = ctx.detect_rounds(img, params_bright, params_dim, packed, rs, **rounds_params)
+    return _detection(recs[0][0], img.shape), (recs[0], int(nf[0]), dup[0])
+
+
 def _pack_one(cat):
     if cat is None or not len(cat["NOBSERVE"]):
         return None
@@ -685,6 +696,23 @@ class _MaskStage:
         self.out.flush()
 
 
+class _RoundsStage:
+    """Several trails per frame for ``DetectTrails(max_trails=K)`` (include/lfdmi.h: detection rounds): the chunk's detect call
+    becomes ``detect_rounds`` with ``params`` (record 0 serves everything the plain record served), and every found trail of a
+    frame, round 0 included, gets its row in trails.txt."""
+
+    def __init__(self, out, params):
+        self.out, self.params = out, dict(params)
+
+    def rows(self, key, recs, n_found, dup_of):
+        from ..rounds import format_row
+        for k in range(int(n_found)):
+            self.out.write(format_row(key, k, recs[k], dup_of[k]) + "\n")
+
+    def flush(self):
+        self.out.flush()
+
+
 class _LcStage:
     """The light curves behind the measurements for ``DetectTrails(light_curves=True)`` (include/lfdmi.h: light curves): every
     results.txt row (source ``detect``) and, with ``radon_lines``, every found faint line (source ``radon``) is measured in
@@ -931,8 +959,10 @@ class _Chunk:
     per-frame product gets a slot here, a step in ``_run_group`` and ``_run_frame``, and its row in ``_emit``."""
 
     def __init__(self, n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon=None,
-                 stars=None, masks=None, lc=None, strip=None, sub=None, seeing=None):
+                 stars=None, masks=None, lc=None, strip=None, sub=None, seeing=None, rounds=None):
         self.results, self.errors, self.profiles, self.sky, self.radon, self.stars = results, errors, profiles, sky, radon, stars
+        self.rounds = rounds                          # a ``_RoundsStage``; ``trails[i]``: (records [K], n_found, dup_of [K])
+        self.trails = [None] * n
         self.seeing = seeing                          # a ``_SeeingStage``; ``seerecs[i]``: (frame record, seeing_arcsec) or the exception
         self.seerecs = [None] * n
         self.sub = sub                                # a ``_SubStage``; ``subs[i]``: (source, [(record, segment)], frame) or the exception
@@ -966,7 +996,7 @@ def _sub_segments(c, i, detection, res, line):
 def _run_frame(c, i, filter, frame):
     """Frame i on its own, under its own try: ``frame()`` -> (float32 img, cat); sky normalisation if on, detection, and the
     trail measurement of a detected frame."""
-    c.lcs[i] = c.strips[i] = c.subs[i] = None
+    c.lcs[i] = c.strips[i] = c.subs[i] = c.trails[i] = None
     try:
         img, cat = frame()
         c.shapes[i] = tuple(img.shape)
@@ -980,7 +1010,10 @@ def _run_frame(c, i, filter, frame):
                 c.seeing.note(c.keys[i], c.seerecs[i])
             except Exception as e:  # noqa: BLE001
                 c.seerecs[i] = e
-        c.rows[i] = process_frame_arrays(img, cat, filter, c.params_bright, c.params_dim, c.params_removestars)
+        if c.rounds is not None:
+            c.rows[i], c.trails[i] = _frame_rounds(img, cat, filter, c.params_bright, c.params_dim, c.params_removestars, c.rounds.params)
+        else:
+            c.rows[i] = process_frame_arrays(img, cat, filter, c.params_bright, c.params_dim, c.params_removestars)
         if c.profiles is not None and c.rows[i][0]:
             try:
                 c.meas[i] = measure_trail(img, c.rows[i][2], cat, filter, c.params_removestars, **c.trail_params)
@@ -1062,7 +1095,13 @@ def _run_group(c, idx, filter, shape, inflight, source, second, detect_kw=None, 
                 except Exception as e:  # noqa: BLE001
                     for i in idx:
                         c.seerecs[i] = e
-            recs = ctx.detect_batch(frames, c.params_bright, c.params_dim, packed, rs, **detect_kw)
+            if c.rounds is not None:
+                all_recs, nf, dup = ctx.detect_rounds(frames, c.params_bright, c.params_dim, packed, rs, **detect_kw, **c.rounds.params)
+                recs = _np.ascontiguousarray(all_recs[:, 0])
+                for j, i in enumerate(idx):
+                    c.trails[i] = (all_recs[j], int(nf[j]), dup[j])
+            else:
+                recs = ctx.detect_batch(frames, c.params_bright, c.params_dim, packed, rs, **detect_kw)
             c.gpu_s += time.perf_counter() - t0
             if c.profiles is not None:
                 try:
@@ -1163,6 +1202,8 @@ def _emit(c, i, key, head, shape):
     except Exception as e:  # noqa: BLE001
         _log_error(c.errors, key, e, c.debug)
         return
+    if c.rounds is not None and c.trails[i] is not None:
+        c.rounds.rows(key, *c.trails[i])
     line = c.rlines[i]
     if isinstance(line, Exception):
         _log_error(c.errors, key, line, c.debug)
@@ -1215,7 +1256,7 @@ def _emit(c, i, key, head, shape):
 
 def process_field(results, errors, run, camcol, filter, field, params_bright, params_dim,
                   params_removestars, profiles=None, trail_params=None, sky=None, radon=None, stars=None, masks=None, lc=None,
-                  strip=None, sub=None, seeing=None):
+                  strip=None, sub=None, seeing=None, rounds=None):
     """One frame end to end (reference: detecttrails.py:30-143): locate the frame (or its .bz2),
     read image + header + photoObj, detect, append ``run camcol filter field tai crpix1 crpix2
     crval1 crval2 cd11 cd12 cd21 cd22 x1 y1 x2 y2`` to ``results``; every exception is logged
@@ -1227,7 +1268,7 @@ def process_field(results, errors, run, camcol, filter, field, params_bright, pa
     normalisation, if on), and the frame's stars.txt row is written.  ``masks``: a ``_MaskStage``; a results row, and every found
     faint line of ``radon`` with lines, gets its masks.txt row."""
     c = _Chunk(1, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon, stars, masks, lc, strip, sub,
-               seeing)
+               seeing, rounds)
     c.keys[0] = (run, camcol, filter, field)
     head = None
     try:
@@ -1272,7 +1313,7 @@ def process_fields_batched(results, errors, ids, params_bright, params_dim, para
 
 
 def process_loaded(results, errors, loaded, params_bright, params_dim, params_removestars, profiles=None, trail_params=None, sky=None,
-                   radon=None, stars=None, masks=None, lc=None, strip=None, sub=None, seeing=None):
+                   radon=None, stars=None, masks=None, lc=None, strip=None, sub=None, seeing=None, rounds=None):
     """process_fields_batched for a chunk the loader has read (``loader.Loaded``): the frames that sit in pinned memory go to
     the GPU as contiguous same-filter slices of that memory with the matching rows of the padded catalogue arrays (no copy
     of a frame on the host, no per-frame Python), the others take the per-frame path; rows and errors entries come out in
@@ -1283,12 +1324,12 @@ def process_loaded(results, errors, loaded, params_bright, params_dim, params_re
     a detection are searched where that call left them, and the lines found get their radon.txt rows.  ``stars``: a
     ``_StarsStage``: every slice's catalogue is built on the device from the frames the detect call is about to read (the
     loader's catalogue rows are not used), and one stars.txt row per frame is written after its sky row.  ``masks``: a
-    ``_MaskStage``, as in ``process_field``."""
+    ``_MaskStage``, as in ``process_field``.  ``rounds``: a ``_RoundsStage``: every slice's detect call is ``detect_rounds``."""
     import time
     t_in = time.perf_counter()
     n = len(loaded.keys)
     c = _Chunk(n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon, stars, masks, lc, strip, sub,
-               seeing)
+               seeing, rounds)
     c.keys = list(loaded.keys)
     by_slot = {}
     for i in range(n):
@@ -1429,6 +1470,13 @@ class DetectTrails:
     source line status n_sec n_ok mean_rate mean_rate_err chi2 dof peak_section peak_rate length flux flux_err``.  The default
     ``clip`` (0.125) is the faint-trail units' star cut; a bright trail needs ``lc_params={"clip": ...}`` above its peak.  Rank files,
     resume and ``Jobs`` treat both like masks.txt; every other output stays byte for byte what it is.
+
+    ``max_trails=K`` (1 .. 8; unset or 1: nothing differs and no file appears): the chunk pipeline calls ``detect_rounds`` where it
+    called detect (include/lfdmi.h: detection rounds; ``rounds_params``: dict of half, dup_dist) and uses record 0 for everything
+    it did before, so results.txt and every other output stay byte for byte what they are; ``trails_file`` (default
+    ``<savepath>/trails.txt``) gets one row per found trail, round 0 included: ``run camcol filter field round found rho theta x1
+    y1 x2 y2 dup_of`` (``lfd_amd.rounds.read_trails``).  Rank files, resume and ``Jobs`` treat it like masks.txt.  The extra
+    trails are not fed to the other stages.
     ``trail_strips=True`` (default off): the same segments, at the same places, are straightened into maps of sections along the
     trail by offsets across it (include/lfdmi.h: trail strips; ``strips_params``: dict of lfdmi_strip_params fields), each
     half-width widened by ``wing`` so that the wings are sky.  ``strips_file`` (default ``<savepath>/strips.txt``) gets one row
@@ -1532,6 +1580,19 @@ class DetectTrails:
                 raise ValueError("radon_profiles=True needs radon=True and radon_lines=K: the segments it measures are theirs")
             from ..stack import as_params as stack_as_params
             self.stack_params = stack_as_params(kwargs.get("stack_params"))
+        self.trails_file = kwargs.get("trails_file", os.path.join(save, "trails.txt"))
+        self.max_trails = kwargs.get("max_trails")
+        self.rounds_params = None
+        if self.max_trails is not None:
+            from ..rounds import MAX_TRAILS, as_params as rounds_as_params
+            if int(self.max_trails) != self.max_trails or not 1 <= self.max_trails <= MAX_TRAILS:
+                raise ValueError("max_trails must be an integer, 1 .. %d" % MAX_TRAILS)
+            self.max_trails = int(self.max_trails)
+            self.rounds_params = rounds_as_params(kwargs.get("rounds_params"), max_trails=self.max_trails)
+            _native.make_rounds_params(**self.rounds_params)     # (bad values raise here, not per frame)
+        elif kwargs.get("rounds_params") is not None:
+            raise ValueError("rounds_params needs max_trails=K")
+        self.rounds = self.max_trails is not None and self.max_trails > 1
         self.trail_masks = bool(kwargs.get("trail_masks", False))
         self.masks_file = kwargs.get("masks_file", os.path.join(save, "masks.txt"))
         self.mask_dir = kwargs.get("mask_dir")
@@ -1735,7 +1796,8 @@ class DetectTrails:
                                   else contextlib.nullcontext()))) as (rprof_out, (null_out, (fap_out, rounds_out))), \
                 (open(self.radon_defocus_file + suffix, "a") if self.radon_profiles and self.defocus
                  else contextlib.nullcontext()) as rdef_out, \
-                (open(self.masks_file + suffix, "a") if self.trail_masks else contextlib.nullcontext()) as masks_out, \
+                _both(open(self.masks_file + suffix, "a") if self.trail_masks else contextlib.nullcontext(),
+                      open(self.trails_file + suffix, "a") if self.rounds else contextlib.nullcontext()) as (masks_out, trails_out), \
                 (open(self.lightcurves_file + suffix, "a") if self.light_curves else contextlib.nullcontext()) as lc_out, \
                 (open(self.lightcurve_summary_file + suffix, "a") if self.light_curves else contextlib.nullcontext()) as lcsum_out, \
                 _both(open(self.strips_file + suffix, "a") if self.trail_strips else contextlib.nullcontext(),
@@ -1783,6 +1845,9 @@ class DetectTrails:
             sub = None
             if self.subtract_trails:
                 sub = prof_kw["sub"] = _SubStage(sub_out, self.sub_params, self.mask_params, self.clean_dir)
+            rounds = None
+            if self.rounds:
+                rounds = prof_kw["rounds"] = _RoundsStage(trails_out, self.rounds_params)
             if fresh:
                 progress.write(header + "\n")
                 progress.flush()
@@ -1808,6 +1873,8 @@ class DetectTrails:
                     strip.flush()
                 if sub is not None:
                     sub.flush()
+                if rounds is not None:
+                    rounds.flush()
                 progress.write("".join("%s %s %s %s\n" % tuple(k) for k in done_keys))
                 progress.flush()
 

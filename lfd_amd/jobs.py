@@ -54,7 +54,8 @@ class Jobs:
     their masks.txt files, with ``light_curves=True`` (``lc_params``, ``lightcurves_file``, ``lightcurve_summary_file``) their
     lightcurves.txt and lightcurve_summary.txt files, with ``trail_strips=True`` (``strips_params``, ``strips_file``,
     ``strips_dir``) their strips.txt files, with ``radon_null=K`` their radon_null.txt and radon_fap.txt files and with
-    ``radon_null_rounds=True`` their radon_null_rounds.txt files (rows in selection order)."""
+    ``radon_null_rounds=True`` their radon_null_rounds.txt files, with ``max_trails=K`` > 1 (``rounds_params``, ``trails_file``)
+    their trails.txt files (rows in selection order)."""
 
     def __init__(self, n_workers, devices=None, python=None, **detecttrails_kwargs):
         self.n = int(n_workers)
@@ -88,7 +89,7 @@ class Jobs:
             ([probe.lightcurves_file, probe.lightcurve_summary_file] if probe.light_curves else []) + \
             ([probe.strips_file] if probe.trail_strips else []) + ([probe.subtracted_file] if probe.subtract_trails else []) + \
             ([probe.radon_null_file, probe.radon_fap_file] if probe.radon_null is not None else []) + \
-            ([probe.radon_null_rounds_file] if probe.radon_null_rounds else [])
+            ([probe.radon_null_rounds_file] if probe.radon_null_rounds else []) + ([probe.trails_file] if probe.rounds else [])
         if not resume:
             for path in joined:                           # the joined files are rewritten by this launch
                 if self.n > 1 and os.path.exists(path):
