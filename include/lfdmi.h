@@ -411,6 +411,8 @@ int lfdmi_debug_fail_chunk(lfdmi_ctx *ctx, int chunk);
  *                     (512 MiB; find_stars and stack_profiles: 1 GiB, frames per chunk or group); no effect on device buffers
  *   cell_bytes        bytes of 16-byte cells: trail_strips opens a new batch of segments, subtract_trails a new chunk of frames,
  *                     when the next segment's (frame's) cells no longer fit; one segment (frame) alone always does  (512 MiB)
+ *                     (frame_previews: bytes of its 8-byte cell plane, max(1, cell_bytes / (8 Hp Wp)) frames a chunk (1 GiB); its
+ *                     host frames by stage_bytes (1 GiB); its chunks of frames in out[0])
  *   render_blocks     persistent blocks that walk a chunk's list: the grid is min(pairs of the chunk, render_blocks)   (2048)
  *   stars_rec_bytes   find_stars: bytes of records a chunk returns to the host: max(1, bytes / (max_obj * 32)) frames   (256 MiB)
  *                     (measure_seeing: bytes of per-record sums of a chunk: max(1, bytes / (max_obj * 64)) frames; its host
@@ -1728,6 +1730,86 @@ void lfdmi_default_rounds_params(lfdmi_rounds_params *out);
 int lfdmi_detect_rounds(lfdmi_ctx *ctx, void *frames, int dtype, int n, int h, int w, const lfdmi_catalog *cat,
                         const lfdmi_rs_params *rs, const lfdmi_params *bright, const lfdmi_params *dim,
                         const lfdmi_rounds_params *params, lfdmi_result *records, int32_t *n_found, int32_t *dup_of, int loc);
+
+/* ---- frame previews ---------------------------------------------------------------------------------------------------------
+ * A detection ends as a row of numbers; whoever has to judge it needs to see the frame.  lfdmi_frame_previews turns frames into
+ * small 8-bit images -- binned, with robust limits, through a stretch table -- while they are on the device, so that a chunk that
+ * was decompressed there never has to come back at full size.  The reference leaves this to its user (its image checker browses
+ * PNG files somebody else made).  Overlays and PNG files are made on the host from these images (lfd_amd/previews.py).  The
+ * procedure below is the definition; tests/preview_ref.py restates it in numpy and the device reproduces every byte and every
+ * integer: a pixel enters as a fixed-point integer, the cell sums are integer sums, the limits are an exact selection, and the
+ * one division and one multiplication of step 5 are IEEE doubles.  No transcendental function appears: any stretch is the
+ * caller's table.
+ *
+ * params = {bin b, one of 1, 2, 4, 8, 16 (default 4); mode LFDMI_PREVIEW_RANK (default) or LFDMI_PREVIEW_GIVEN; lo_ppm, hi_ppm,
+ * 0 <= lo_ppm <= hi_ppm <= 1000000 (defaults 10000 and 995000, the percentiles strips.to_uint8 uses; read in RANK mode, checked
+ * in both)}; NULL: the defaults.
+ *
+ * 1. Geometry.  The preview shows the flipped frame, the coordinates of every record and of results.txt: flipped row y is buffer
+ *    row H-1-y.  Hp = ceil(H / b), Wp = ceil(W / b).  Preview row r, column i is the cell of the flipped rows [r b, min((r+1) b,
+ *    H)) and the columns [i b, min((i+1) b, W)): the last row and column of cells may be partial.
+ * 2. Pixels.  A pixel v is valid when it is finite (a big-endian frame: after the byte swap).  A blotted +0 is valid: the preview
+ *    shows what the detector saw.  A valid pixel enters as the integer
+ *        q = llrint(min(max((double)v, -16777216.0), 16777216.0) * 1073741824.0)      (clamped to +-2^24, times 2^30, ties to even),
+ *    the light curves' and strips' convention with a clamp, so |q| <= 2^54 and the 256 pixels of the largest cell stay inside
+ *    int64 (|sum| <= 2^62).  +-inf and NaN are not valid; a finite value beyond the clamp enters as +-2^54.
+ * 3. Cells.  Q = the sum of q over the cell's valid pixels, c = their count.  c == 0: the cell is EMPTY, its byte is 0, its value
+ *    in the cell plane is INT64_MIN, and it takes no part in step 4.  Otherwise m = Q / c as C divides int64 (towards zero).
+ *    |m| <= 2^54, so INT64_MIN is no cell's mean.
+ * 4. Limits of a frame.  M = the number of cells that are not EMPTY.  M == 0: the frame is LFDMI_PREVIEW_EMPTY (every byte 0).
+ *    RANK: over the M values m in ascending order (rank 0 the smallest), lo = rank (lo_ppm * (M-1)) / 1000000 and hi = rank
+ *    (hi_ppm * (M-1)) / 1000000, the products and quotients in int64.  A selection: equal values are equal, so no result depends
+ *    on an order.  An EMPTY frame has lo = hi = 0.
+ *    GIVEN: limits[2 i], limits[2 i + 1] are frame i's lo and hi as doubles x, each entering as llrint(min(max(x, -16777216.0),
+ *    16777216.0) * 1073741824.0); an EMPTY frame keeps them.  One stretch across a run, such as -2 sigma .. +10 sigma.
+ *    hi <= lo (and M > 0): the frame is LFDMI_PREVIEW_FLAT and every byte is 0.  Otherwise LFDMI_PREVIEW_OK.
+ * 5. Level of a cell that is not EMPTY in an OK frame:
+ *        d = min(max(m, lo), hi) - lo;   r = hi - lo;   k = (int)(((double)d / (double)r) * 4095.0)
+ *    (int64 differences, at most 2^55; each converted to double with one rounding; one division, one multiplication, both
+ *    rounded, no contraction; the cast truncates).  0 <= k <= 4095 and the byte is lut[k].
+ * 6. Record of a frame: status, n_cells = M, n_empty = Hp Wp - M, lo and hi as the int64 of step 4, and lo_f = (double)lo *
+ *    2^-30, hi_f likewise.
+ *
+ * The device works in three kernels (lfd_amd/csrc/preview/k_preview.h).  k_preview_bin streams the frames once, 4 B per pixel
+ * in and 8 B per cell out: a wavefront owns b rows of 256 columns, a lane four neighbouring pixels of each row, which it loads
+ * with one 16 B access when every row of the frames starts on a 16 B boundary (the frames' address and W are multiples of 16 B
+ * and of 4) and with 4 B accesses otherwise (no unaligned pointer is cast to a wider type); the byte swap and the row flip are in
+ * the load and in its address; the lane keeps the b rows' sums in registers, and lanes that share a cell (b = 8, 16) add theirs
+ * by shuffles.  k_preview_limits, a workgroup per frame, counts M and selects the two ranks by eight radix passes of 8 bits over
+ * the sign-flipped cells, from the top, with histograms in LDS (integer atomics; a wavefront whose cells share a bucket adds
+ * once); the two ranks share a histogram until their prefixes part.  k_preview_render keeps lut in LDS and writes a byte per
+ * thread, neighbouring threads neighbouring bytes.  The cell plane of a call is made in chunks of frames: max(1, cell_bytes /
+ * (8 Hp Wp)) frames (cell_bytes: 1 GiB), and host frames are staged max(1, stage_bytes / (4 H W)) at a time (1 GiB);
+ * lfdmi_debug_unit_limits lowers both and lfdmi_debug_unit_split's out[0] counts the chunks.  One frame alone always fits.  What
+ * bounds each kernel has not been measured (profiles/preview_probe.txt has the whole call against a copy). */
+enum { LFDMI_PREVIEW_RANK = 0, LFDMI_PREVIEW_GIVEN = 1 };
+enum { LFDMI_PREVIEW_OK = 0, LFDMI_PREVIEW_FLAT = 1, LFDMI_PREVIEW_EMPTY = 2 };
+#define LFDMI_PREVIEW_LUT 4096         /* entries of the stretch table */
+typedef struct {
+    int32_t bin;              /* 1, 2, 4, 8 or 16; default 4 */
+    int32_t mode;             /* LFDMI_PREVIEW_RANK (default) or LFDMI_PREVIEW_GIVEN */
+    int32_t lo_ppm, hi_ppm;   /* the two ranks in parts per million of M-1 (0 .. 1000000, lo_ppm <= hi_ppm); defaults 10000, 995000 */
+} lfdmi_preview_params;
+typedef struct {
+    int32_t status;           /* LFDMI_PREVIEW_* */
+    int32_t n_cells;          /* M */
+    int32_t n_empty;
+    int32_t pad;
+    int64_t lo, hi;           /* step 4 */
+    double lo_f, hi_f;        /* lo, hi times 2^-30: in the frames' units */
+} lfdmi_preview_frame;
+void lfdmi_default_preview_params(lfdmi_preview_params *out);
+/* frames: n frames of h x w, LFDMI_F32 or LFDMI_F32_BE, at loc (host, pinned or device); only read.  p NULL: the defaults.
+ * limits: 2 n doubles (host), read in GIVEN mode only.  lut: LFDMI_PREVIEW_LUT bytes (host).  out: n x Hp x Wp uint8 at out_loc
+ * (LFDMI_HOST / LFDMI_HOST_PINNED / LFDMI_DEVICE: a caller can preview a whole chunk and fetch the few frames it wants).  cells:
+ * NULL, or n x Hp x Wp int64 at out_loc, which get the values m of step 3.  records: n records (host).  n == 0 is a valid call
+ * that does nothing.  LFDMI_ERR_ARG, and nothing is written: a bad dtype, loc or out_loc; n < 0; h or w outside 1 .. 65536 or
+ * h * w > 1e9; a bad bin or mode; a ppm outside 0 .. 1000000 or lo_ppm > hi_ppm; in GIVEN mode a NULL limits or a limit that is
+ * not finite; a NULL lut, and with n > 0 a NULL frames, out or records; calls in flight.  The call keeps no state (its device
+ * memory comes from the stream's pool), runs on the context's stream and waits for it once, at its end. */
+int lfdmi_frame_previews(lfdmi_ctx *ctx, const void *frames, int dtype, int n, int h, int w, int loc, const lfdmi_preview_params *p,
+                         const double *limits, const uint8_t *lut, uint8_t *out, int out_loc, int64_t *cells,
+                         lfdmi_preview_frame *records);
 
 #ifdef __cplusplus
 }

@@ -54,6 +54,7 @@ SYMBOLS = (
     "lfdmi_default_stars_params", "lfdmi_find_stars", "lfdmi_stars_catalog",
     "lfdmi_default_psf_params", "lfdmi_measure_seeing",
     "lfdmi_default_rounds_params", "lfdmi_detect_rounds",
+    "lfdmi_default_preview_params", "lfdmi_frame_previews",
 )
 
 
@@ -513,6 +514,35 @@ def make_rounds_params(**params):
     return _make_params(RoundsParamsStruct, "lfdmi_default_rounds_params", "rounds", params)
 
 
+class PreviewParamsStruct(C.Structure):
+    """lfdmi_preview_params (include/lfdmi.h: frame previews)."""
+    _fields_ = [("bin", C.c_int32), ("mode", C.c_int32), ("lo_ppm", C.c_int32), ("hi_ppm", C.c_int32)]
+
+
+# lfdmi_preview_frame: one record per frame of lfdmi_frame_previews
+PREVIEW_FRAME_DTYPE = np.dtype([("status", "<i4"), ("n_cells", "<i4"), ("n_empty", "<i4"), ("pad", "<i4"),
+                                ("lo", "<i8"), ("hi", "<i8"), ("lo_f", "<f8"), ("hi_f", "<f8")])
+PREVIEW_RANK, PREVIEW_GIVEN = 0, 1
+PREVIEW_MODES = ("rank", "given")
+PREVIEW_OK, PREVIEW_FLAT, PREVIEW_EMPTY = 0, 1, 2
+PREVIEW_LUT = 4096
+PREVIEW_BINS = (1, 2, 4, 8, 16)
+PREVIEW_EMPTY_CELL = -2 ** 63
+
+
+def _preview_mode(k, v):
+    if k == "mode" and isinstance(v, str):
+        if v not in PREVIEW_MODES:
+            raise ValueError(f"unknown preview mode {v!r}")
+        return PREVIEW_MODES.index(v)
+    return v
+
+
+def make_preview_params(**params):
+    """lfdmi_default_preview_params with the given fields replaced (unknown names raise; mode: a name of PREVIEW_MODES or its code)."""
+    return _make_params(PreviewParamsStruct, "lfdmi_default_preview_params", "preview", params, _preview_mode)
+
+
 def make_radon_params(**params):
     """lfdmi_default_radon_params with the given fields replaced (unknown names raise)."""
     return _make_params(RadonParamsStruct, "lfdmi_default_radon_params", "radon", params)
@@ -631,6 +661,10 @@ def lib():
         _lib.lfdmi_default_rounds_params.argtypes = [C.c_void_p]
         _lib.lfdmi_detect_rounds.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        _lib.lfdmi_default_preview_params.restype = None
+        _lib.lfdmi_default_preview_params.argtypes = [C.c_void_p]
+        _lib.lfdmi_frame_previews.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         _lib.lfdmi_debug_unit_limits.argtypes = [C.c_void_p, C.c_void_p]
         _lib.lfdmi_debug_unit_split.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     return _lib
@@ -1654,6 +1688,45 @@ class Context:
         self._chk(self._lib.lfdmi_measure_seeing(self._h, _ptr(frames), code, n, h, w, loc, _ptr(sig), _ptr(records),
                                                  DEVICE if _is_dev(records) else HOST, _ptr(frec), m, C.byref(p), _ptr(out), _ptr(ofr)))
         return out, ofr
+
+    # -- frame previews (lfdmi_frame_previews) --------------------------------------------------------------------------------------
+    def frame_previews(self, frames, lut=None, limits=None, pinned=False, native_device=False, out_device=False, want_cells=False,
+                       **params):
+        """Binned, stretched 8-bit images of the flipped frames (include/lfdmi.h: frame previews).  frames: what ``find_stars``
+        takes, only read.  params: bin, mode ("rank" / "given"), lo_ppm, hi_ppm.  limits: with mode="given", (lo, hi) or one pair
+        per frame, in the frames' units.  lut: 4096 bytes (default: ``previews.lut()``).  Returns (uint8 images [n, Hp, Wp],
+        PREVIEW_FRAME_DTYPE records [n]), with want_cells=True (images, int64 cell means [n, Hp, Wp], records); out_device=True:
+        images and cells stay on the device as torch tensors."""
+        frames, code, n, h, w, loc = self._frames(frames, pinned, "frame_previews", native_device=native_device)
+        p = make_preview_params(**params)
+        if lut is None:
+            from .previews import lut as default_lut
+            lut = default_lut()
+        lut = np.ascontiguousarray(lut, np.uint8).reshape(-1)
+        if lut.size != PREVIEW_LUT:
+            raise ValueError(f"frame_previews: lut holds {PREVIEW_LUT} bytes")
+        lim = None
+        if limits is not None:
+            lim = np.ascontiguousarray(np.broadcast_to(np.asarray(limits, np.float64), (n, 2)))
+        elif p.mode == PREVIEW_GIVEN:
+            raise ValueError("frame_previews: mode='given' needs limits")
+        b = int(p.bin) if int(p.bin) in PREVIEW_BINS else 1     # (a bad bin: the library refuses it; the arrays just have to exist)
+        shape = (n, -(-h // b), -(-w // b))
+        cells = None
+        if out_device:
+            import torch
+            dev = f"cuda:{self.device}"
+            out = torch.empty(shape, dtype=torch.uint8, device=dev)        # (the library writes every byte on its own stream)
+            if want_cells:
+                cells = torch.empty(shape, dtype=torch.int64, device=dev)
+        else:
+            out = np.zeros(shape, np.uint8)
+            if want_cells:
+                cells = np.zeros(shape, np.int64)
+        rec = np.zeros(n, PREVIEW_FRAME_DTYPE)
+        self._chk(self._lib.lfdmi_frame_previews(self._h, _ptr(frames), code, n, h, w, loc, C.byref(p), _ptr(lim), _ptr(lut), _ptr(out),
+                                                 DEVICE if out_device else HOST, _ptr(cells), _ptr(rec)))
+        return (out, cells, rec) if want_cells else (out, rec)
 
     def pinned_buffer(self, nbytes):
         """Page-locked host memory next to this context's GPU (lfdmi_host_alloc) as a ``PinnedBuffer``."""

@@ -319,6 +319,59 @@ class _SeeingStage:
         self.by_key = {}
 
 
+class _PreviewStage:
+    """The frame previews in front of detection for ``DetectTrails(previews=...)`` (include/lfdmi.h: frame previews): every
+    chunk is previewed once where ``_SeeingStage`` measures, before the detect call blots it, and its images stay on the device;
+    the frames that get a results.txt row (``which`` = "detections") or every frame that loaded ("all") are copied back, overlaid
+    with their row's line (and the trails.txt lines with ``max_trails``) and written to ``out_dir`` under the image checker's
+    name, with a previews.txt row each.  ``params``: bin, mode, lo_ppm, hi_ppm, limits (one (lo, hi) pair for every frame, with
+    mode "given"), kind and softening of the stretch table or a ``lut`` of one's own, color and thick of the overlay."""
+
+    def __init__(self, out, which, params, out_dir):
+        from .. import masks, previews
+        p = previews.as_params(params)
+        self.out, self.which, self.out_dir = out, which, out_dir
+        self.lut = p["lut"] if p.get("lut") is not None else previews.lut(p.get("kind", "asinh"), p.get("softening", 0.1))
+        self.bin = int(p.get("bin", 4))
+        self.call = {k: p[k] for k in ("bin", "mode", "lo_ppm", "hi_ppm", "limits") if k in p}
+        self.draw = {k: p[k] for k in ("color", "thick") if k in p}
+        self.half = masks.half_width(float("nan"))        # no measurement is asked for: the default band
+        if out is not None:
+            os.makedirs(out_dir, exist_ok=True)
+
+    def wants(self, found):
+        return self.which == "all" or bool(found)
+
+    def batch(self, ctx, frames, **where):
+        """the frames where the detect call will read them, before it blots them -> (device images [n, Hp, Wp], records)"""
+        return ctx.frame_previews(frames, lut=self.lut, out_device=True, **self.call, **where)
+
+    def one(self, img):
+        """one host frame, not blotted yet -> (image, record)"""
+        img = _np.ascontiguousarray(img, _np.float32)
+        with use_context(*img.shape) as ctx:
+            out, rec = ctx.frame_previews(img, lut=self.lut, **self.call)
+        return out[0], rec[0]
+
+    def segments(self, res, trails):
+        """the lines of a frame as ``masks.SEGMENT_DTYPE``: its results row's, then the later rounds' found trails"""
+        from .. import masks
+        rows = [] if res is None else [(0, res["x1"], res["y1"], res["x2"], res["y2"], self.half)]
+        if trails is not None:
+            recs, n_found = trails[0], int(trails[1])
+            rows += [(0, recs[k]["x1"], recs[k]["y1"], recs[k]["x2"], recs[k]["y2"], self.half) for k in range(1, n_found)]
+        return masks.segments(rows)
+
+    def row(self, key, gray, rec, res, trails):
+        from .. import previews
+        name = previews.filename(*key)
+        previews.write_png(os.path.join(self.out_dir, name), previews.overlay(gray, self.segments(res, trails), self.bin, **self.draw))
+        self.out.write(previews.format_row(key, self.bin, rec, name) + "\n")
+
+    def flush(self):
+        self.out.flush()
+
+
 class _ShortRecord:
     """a frame's record of ``_RadonStage`` with ``short``: the record it has without (``base``), its short records [K], their
     n_lines and [(stack record, row)] per found short candidate (empty without ``prof_out``)"""
@@ -959,7 +1012,9 @@ class _Chunk:
     per-frame product gets a slot here, a step in ``_run_group`` and ``_run_frame``, and its row in ``_emit``."""
 
     def __init__(self, n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon=None,
-                 stars=None, masks=None, lc=None, strip=None, sub=None, seeing=None, rounds=None):
+                 stars=None, masks=None, lc=None, strip=None, sub=None, seeing=None, rounds=None, preview=None):
+        self.preview = preview                        # a ``_PreviewStage``; ``previews[i]``: (image, record) or the exception
+        self.previews = [None] * n
         self.results, self.errors, self.profiles, self.sky, self.radon, self.stars = results, errors, profiles, sky, radon, stars
         self.rounds = rounds                          # a ``_RoundsStage``; ``trails[i]``: (records [K], n_found, dup_of [K])
         self.trails = [None] * n
@@ -996,7 +1051,7 @@ def _sub_segments(c, i, detection, res, line):
 def _run_frame(c, i, filter, frame):
     """Frame i on its own, under its own try: ``frame()`` -> (float32 img, cat); sky normalisation if on, detection, and the
     trail measurement of a detected frame."""
-    c.lcs[i] = c.strips[i] = c.subs[i] = c.trails[i] = None
+    c.lcs[i] = c.strips[i] = c.subs[i] = c.trails[i] = c.previews[i] = None
     try:
         img, cat = frame()
         c.shapes[i] = tuple(img.shape)
@@ -1010,10 +1065,17 @@ def _run_frame(c, i, filter, frame):
                 c.seeing.note(c.keys[i], c.seerecs[i])
             except Exception as e:  # noqa: BLE001
                 c.seerecs[i] = e
+        if c.preview is not None:                     # likewise
+            try:
+                c.previews[i] = c.preview.one(img)
+            except Exception as e:  # noqa: BLE001
+                c.previews[i] = e
         if c.rounds is not None:
             c.rows[i], c.trails[i] = _frame_rounds(img, cat, filter, c.params_bright, c.params_dim, c.params_removestars, c.rounds.params)
         else:
             c.rows[i] = process_frame_arrays(img, cat, filter, c.params_bright, c.params_dim, c.params_removestars)
+        if c.preview is not None and not c.preview.wants(c.rows[i][0]):
+            c.previews[i] = None
         if c.profiles is not None and c.rows[i][0]:
             try:
                 c.meas[i] = measure_trail(img, c.rows[i][2], cat, filter, c.params_removestars, **c.trail_params)
@@ -1095,6 +1157,12 @@ def _run_group(c, idx, filter, shape, inflight, source, second, detect_kw=None, 
                 except Exception as e:  # noqa: BLE001
                     for i in idx:
                         c.seerecs[i] = e
+            pv = None
+            if c.preview is not None:                 # likewise; the images stay on the device until the records say which are wanted
+                try:
+                    pv = c.preview.batch(ctx, frames, **detect_kw)
+                except Exception as e:  # noqa: BLE001
+                    pv = e
             if c.rounds is not None:
                 all_recs, nf, dup = ctx.detect_rounds(frames, c.params_bright, c.params_dim, packed, rs, **detect_kw, **c.rounds.params)
                 recs = _np.ascontiguousarray(all_recs[:, 0])
@@ -1103,6 +1171,10 @@ def _run_group(c, idx, filter, shape, inflight, source, second, detect_kw=None, 
             else:
                 recs = ctx.detect_batch(frames, c.params_bright, c.params_dim, packed, rs, **detect_kw)
             c.gpu_s += time.perf_counter() - t0
+            if pv is not None:
+                for j, r in enumerate(recs):
+                    if c.preview.wants(not int(r["status"]) and int(r["found"])):
+                        c.previews[idx[j]] = pv if isinstance(pv, Exception) else (pv[0][j].cpu().numpy(), pv[1][j])
             if c.profiles is not None:
                 try:
                     trails, profs = ctx.measure_trails(frames, recs, packed, rs, **measure_kw, **c.trail_params)
@@ -1204,6 +1276,13 @@ def _emit(c, i, key, head, shape):
         return
     if c.rounds is not None and c.trails[i] is not None:
         c.rounds.rows(key, *c.trails[i])
+    if c.preview is not None and c.previews[i] is not None:
+        try:
+            if isinstance(c.previews[i], Exception):
+                raise c.previews[i]
+            c.preview.row(key, *c.previews[i], res if detection else None, c.trails[i] if detection else None)
+        except Exception as e:  # noqa: BLE001 - a picture that cannot be made costs no other row
+            _log_error(c.errors, key, e, c.debug)
     line = c.rlines[i]
     if isinstance(line, Exception):
         _log_error(c.errors, key, line, c.debug)
@@ -1256,7 +1335,7 @@ def _emit(c, i, key, head, shape):
 
 def process_field(results, errors, run, camcol, filter, field, params_bright, params_dim,
                   params_removestars, profiles=None, trail_params=None, sky=None, radon=None, stars=None, masks=None, lc=None,
-                  strip=None, sub=None, seeing=None, rounds=None):
+                  strip=None, sub=None, seeing=None, rounds=None, preview=None):
     """One frame end to end (reference: detecttrails.py:30-143): locate the frame (or its .bz2),
     read image + header + photoObj, detect, append ``run camcol filter field tai crpix1 crpix2
     crval1 crval2 cd11 cd12 cd21 cd22 x1 y1 x2 y2`` to ``results``; every exception is logged
@@ -1268,7 +1347,7 @@ def process_field(results, errors, run, camcol, filter, field, params_bright, pa
     normalisation, if on), and the frame's stars.txt row is written.  ``masks``: a ``_MaskStage``; a results row, and every found
     faint line of ``radon`` with lines, gets its masks.txt row."""
     c = _Chunk(1, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon, stars, masks, lc, strip, sub,
-               seeing, rounds)
+               seeing, rounds, preview)
     c.keys[0] = (run, camcol, filter, field)
     head = None
     try:
@@ -1313,7 +1392,7 @@ def process_fields_batched(results, errors, ids, params_bright, params_dim, para
 
 
 def process_loaded(results, errors, loaded, params_bright, params_dim, params_removestars, profiles=None, trail_params=None, sky=None,
-                   radon=None, stars=None, masks=None, lc=None, strip=None, sub=None, seeing=None, rounds=None):
+                   radon=None, stars=None, masks=None, lc=None, strip=None, sub=None, seeing=None, rounds=None, preview=None):
     """process_fields_batched for a chunk the loader has read (``loader.Loaded``): the frames that sit in pinned memory go to
     the GPU as contiguous same-filter slices of that memory with the matching rows of the padded catalogue arrays (no copy
     of a frame on the host, no per-frame Python), the others take the per-frame path; rows and errors entries come out in
@@ -1329,7 +1408,7 @@ def process_loaded(results, errors, loaded, params_bright, params_dim, params_re
     t_in = time.perf_counter()
     n = len(loaded.keys)
     c = _Chunk(n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon, stars, masks, lc, strip, sub,
-               seeing, rounds)
+               seeing, rounds, preview)
     c.keys = list(loaded.keys)
     by_slot = {}
     for i in range(n):
@@ -1409,6 +1488,16 @@ class DetectTrails:
     ell``.  With ``defocus=True`` every fit behind defocus.txt and radon_defocus.txt gets its frame's ``seeing_arcsec`` as
     ``fit_defocus``'s ``seeing`` (NaN, a free fit, for a frame with too few stars).  Rank files, resume and ``Jobs`` treat
     seeing.txt like stars.txt; a run without ``seeing`` stays byte for byte what it is.
+    ``previews="detections"`` or ``"all"`` (default None: nothing differs and no file appears): every chunk is turned into small
+    8-bit images on the device (include/lfdmi.h: frame previews; ``preview_params``: dict of bin, mode, lo_ppm, hi_ppm, limits,
+    kind, softening, lut, color, thick) before detection blots it, after the normalisation when that is on.  The images of the
+    frames that get a results.txt row (``"detections"``), or of every frame that loaded (``"all"``), are copied back, overlaid
+    with the row's line (and the trails.txt lines with ``max_trails``; ``lfd_amd.previews.overlay``) and written to
+    ``preview_dir`` (default ``<savepath>/previews``) as ``frame-{filter}-{run:06d}-{camcol}-{field:04}.fits.png``, the name the
+    reference's image checker looks for.  ``previews_file`` (default ``<savepath>/previews.txt``) gets one row per picture: ``run
+    camcol filter field status bin lo hi n_cells n_empty file``.  Rank files, resume and ``Jobs`` treat previews.txt like
+    seeing.txt; the pictures' names are unique per frame and carry no rank suffix.  Every other output stays byte for byte what
+    it is.
     ``radon=True`` (default off): after each chunk's detection call the frames WITHOUT a detection are searched for a trail that
     is faint in every pixel but long (include/lfdmi.h: faint-trail search; ``radon_params``: dict or
     ``lfd_amd.radon.RadonParams``), with the sky sigma ``target_sigma`` under ``normalize=True`` and 0.025 otherwise.  A line
@@ -1522,6 +1611,13 @@ class DetectTrails:
         self.seeing_file = kwargs.get("seeing_file", os.path.join(save, "seeing.txt"))
         from ..psf import as_params as psf_as_params
         self.seeing_params = psf_as_params(kwargs.get("seeing_params"))  # (likewise)
+        self.previews = kwargs.get("previews")
+        if self.previews not in (None, "detections", "all"):
+            raise ValueError("previews must be None, 'detections' or 'all'")
+        self.preview_dir = kwargs.get("preview_dir", os.path.join(save, "previews"))
+        self.previews_file = kwargs.get("previews_file", os.path.join(save, "previews.txt"))
+        from ..previews import as_params as preview_as_params
+        self.preview_params = preview_as_params(kwargs.get("preview_params"))   # (likewise)
         self.radon = bool(kwargs.get("radon", False))
         self.radon_file = kwargs.get("radon_file", os.path.join(save, "radon.txt"))
         from ..radon import as_params as radon_as_params
@@ -1801,7 +1897,9 @@ class DetectTrails:
                 (open(self.lightcurves_file + suffix, "a") if self.light_curves else contextlib.nullcontext()) as lc_out, \
                 (open(self.lightcurve_summary_file + suffix, "a") if self.light_curves else contextlib.nullcontext()) as lcsum_out, \
                 _both(open(self.strips_file + suffix, "a") if self.trail_strips else contextlib.nullcontext(),
-                      open(self.subtracted_file + suffix, "a") if self.subtract_trails else contextlib.nullcontext()) as (strips_out, sub_out):
+                      _both(open(self.subtracted_file + suffix, "a") if self.subtract_trails else contextlib.nullcontext(),
+                            open(self.previews_file + suffix, "a") if self.previews is not None
+                            else contextlib.nullcontext())) as (strips_out, (sub_out, previews_out)):
             seeing = None
             if self.seeing:
                 sigma = _native.make_sky_params(**self.sky_params).target_sigma if self.normalize else 0.025
@@ -1848,6 +1946,9 @@ class DetectTrails:
             rounds = None
             if self.rounds:
                 rounds = prof_kw["rounds"] = _RoundsStage(trails_out, self.rounds_params)
+            preview = None
+            if self.previews is not None:
+                preview = prof_kw["preview"] = _PreviewStage(previews_out, self.previews, self.preview_params, self.preview_dir)
             if fresh:
                 progress.write(header + "\n")
                 progress.flush()
@@ -1875,6 +1976,8 @@ class DetectTrails:
                     sub.flush()
                 if rounds is not None:
                     rounds.flush()
+                if preview is not None:
+                    preview.flush()
                 progress.write("".join("%s %s %s %s\n" % tuple(k) for k in done_keys))
                 progress.flush()
 

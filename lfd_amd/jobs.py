@@ -50,7 +50,7 @@ class Jobs:
     trail_profiles, profiles, trail_params, defocus, defocus_file, defocus_params, normalize, sky_params, sky_file, find_stars, stars_params, stars_file, trail_masks, mask_params, masks_file, mask_dir).  With
     ``trail_profiles=True`` the workers' profiles files are joined like results.txt, with ``defocus=True`` their defocus files
     and with ``normalize=True`` / ``find_stars=True`` / ``seeing=True`` (``seeing_params``, ``seeing_file``) their sky.txt /
-    stars.txt / seeing.txt files too, and with ``trail_masks=True``
+    stars.txt / seeing.txt files too, with ``previews=`` (``preview_params``, ``previews_file``, ``preview_dir``) their previews.txt files, and with ``trail_masks=True``
     their masks.txt files, with ``light_curves=True`` (``lc_params``, ``lightcurves_file``, ``lightcurve_summary_file``) their
     lightcurves.txt and lightcurve_summary.txt files, with ``trail_strips=True`` (``strips_params``, ``strips_file``,
     ``strips_dir``) their strips.txt files, with ``radon_null=K`` their radon_null.txt and radon_fap.txt files and with
@@ -85,7 +85,7 @@ class Jobs:
         results, errors = probe.results, probe.errors
         joined = [results, errors] + ([probe.profiles] if probe.trail_profiles else []) + ([probe.defocus_file] if probe.defocus else []) + \
             ([probe.sky_file] if probe.normalize else []) + ([probe.stars_file] if probe.find_stars else []) + \
-            ([probe.seeing_file] if probe.seeing else []) + ([probe.masks_file] if probe.trail_masks else []) + \
+            ([probe.seeing_file] if probe.seeing else []) + ([probe.previews_file] if probe.previews is not None else []) + ([probe.masks_file] if probe.trail_masks else []) + \
             ([probe.lightcurves_file, probe.lightcurve_summary_file] if probe.light_curves else []) + \
             ([probe.strips_file] if probe.trail_strips else []) + ([probe.subtracted_file] if probe.subtract_trails else []) + \
             ([probe.radon_null_file, probe.radon_fap_file] if probe.radon_null is not None else []) + \
