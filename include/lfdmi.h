@@ -668,7 +668,9 @@ int lfdmi_fit_defocus(lfdmi_ctx *ctx, const lfdmi_defocus_bank *bank, const lfdm
  *        top = m[j][i] + tx*(m[j][i'] - m[j][i]);  bot = m[j'][i] + tx*(m[j'][i'] - m[j'][i]);  bkg = top + ty*(bot - top)
  * 7. Output.  out = (x - bkg) * gain in float32 (two rounded operations); a non-finite x gives 0.
  * Units afterwards: value = (flux - sky) * gain, so flux = value / gain + sky(pixel); trail profiles and defocus fits of a
- * normalised frame are in these units. */
+ * normalised frame are in these units.
+ * Supported range: every float32 difference v - med_t of step 2 must be finite, which pixels of magnitude up to 1.7e38 always
+ * give; where one overflows, the result is not defined.  Subnormal pixels and differences are kept, never flushed to zero. */
 enum { LFDMI_SKY_SUBTRACT = 0, LFDMI_SKY_NORMALISE = 1 };
 enum { LFDMI_SKY_OK = 0, LFDMI_SKY_NO_SKY = 1, LFDMI_SKY_NO_NOISE = 2 };
 typedef struct {
