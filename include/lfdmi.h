@@ -1420,6 +1420,79 @@ int lfdmi_radon_null_scheme(lfdmi_ctx *ctx, lfdmi_radon *radon, const void *fram
                             const uint64_t *seeds, int K, int kind, const void *kind_params, int scheme,
                             const lfdmi_radon_peel *peel, int n_peel, void *records);
 
+/* ---- short-streak search ----------------------------------------------------------------------------------------------------
+ * The three searches above need a long trail: the detector needs pixels that survive the 8-bit conversion, lfdmi_radon_search
+ * a trail that crosses the frame, and lfdmi_radon_search_short scores only strips of 64 binned columns and up that are aligned
+ * to their dyadic grid (its step 10 deliberately leaves the levels of 32 columns and below alone).  lfdmi_streak_search finds
+ * a streak of 20 to 120 px that starts and stops anywhere: a slow satellite in a short exposure, an asteroid trailed by the
+ * drift scan, a meteor's end piece.  It sums the binned frame along every oriented segment of one length L, anchored at every
+ * cell, and reports the segment of largest signal-to-noise.  The reference has no such step.  The procedure below is the
+ * definition; tests/streak_ref.py restates it in numpy.  Every sum is an integer, so the device equals it in every integer and
+ * in every bit of every float and double, whatever its tiling, its order of reduction or its atomics.
+ *
+ * 1. Pixels.  Coordinates and validity are those of faint-trail step 1: the flipped frame, a pixel valid when it is finite, not
+ *    +-0 and |x| <= clip.  g = llrint((double)x * 2^20) where valid, else 0; m = 1 where valid, else 0.
+ * 2. Binning by b = bin (1, 2 or 4).  Hb, Wb and the cells' pixels are those of faint-trail step 2.  G[j][i] = the integer sum
+ *    of g over the cell, M[j][i] = the integer sum of m.  Range rule: llrint(clip * 2^20) * b * b * L < 2^31 (clip: the float32
+ *    parameter), otherwise LFDMI_ERR_ARG; under it every sum below fits int32.  The defaults (clip 0.125, b 2, L 32) give
+ *    2^24 at most.
+ * 3. Orientations.  q = 0: Q[r][c] = G[r][c], R = Hb, C = Wb.  q = 1: Q[r][c] = G[c][r], R = Wb, C = Hb.  The same of M.
+ * 4. Segments.  L = length, a power of two from 8 to 64.  The slope s runs over -(L-1) .. L-1, and
+ *        off(i; s) = sgn(s) * ((2 |s| i + (L-1)) / (2 (L-1)))          (integer division; i = 0 .. L-1)
+ *    so off(0) = 0 and off(L-1) = s.  Segment (q, s, r0, c0) is the cells Q[r0 + off(i; s)][c0 + i].  It exists only when all L
+ *    cells lie inside [0, R) x [0, C): there are no partial segments, and an orientation with C < L has none.  S = the sum of Q
+ *    over the segment, N = the sum of M.
+ * 5. Score.  A segment is a candidate when 2 N >= L b b (the short search's half-valid rule).  A = (float)((double)S * 2^-20):
+ *    one rounding.  snr = A / (sigma * sqrtf((float)N)) with faint-trail step 5's three roundings.  The frame's streak is the
+ *    candidate of largest snr; ties go to the lowest (q, s + L-1, r0, c0).  Without a candidate the record is
+ *    LFDMI_STREAK_NONE (snr 0, found 0, every other field 0), otherwise LFDMI_STREAK_OK.  found = snr >= threshold (float32).
+ *    threshold defaults to 8: sixteen noise-only 372 x 512 frames of sigma 0.025 (the faint-trail search's figures' frames) peak,
+ *    at the defaults, at 5.18 5.05 5.08 4.85 4.58 5.41 4.86 4.98 5.30 4.97 4.84 5.03 4.87 5.02 5.19 5.12; 1.4 times the largest,
+ *    the margin the short search keeps, is 7.58, rounded up to the next 0.5.
+ * 6. Record.  status, found, q, s, r0, c0, n_pix (N), sum (A), snr, and x1, y1, x2, y2, rho, theta (double, on the host): the
+ *    working points (c0, r0) and (c0 + L-1, r0 + s) map to binned (i, j) as (c, r) for q = 0 and (r, c) for q = 1, and to pixels
+ *    as b i + (b-1)/2, b j + (b-1)/2.  theta and rho follow faint-trail step 6.
+ * 7. Rounds.  Up to max_streaks records per frame.  A frame goes on to round k+1 when its round-k record is LFDMI_STREAK_OK
+ *    with found = 1 and k+1 < max_streaks.  With hw = ceil(peel_halfwidth / b), every cell of G and M is set to 0 whose working
+ *    coordinates (r, c) in the record's orientation satisfy, with i = c - c0 and ic = min(max(i, 0), L-1),
+ *        -hw <= i <= L-1+hw     and     |r - (r0 + off(ic; s))| <= hw
+ *    and steps 3 - 6 run again on the peeled arrays.  n_streaks and the stopping record are laid out as
+ *    lfdmi_radon_search_lines' step 8 lays out n_lines: records 0 .. n_streaks-1 have found = 1; if n_streaks < max_streaks,
+ *    record n_streaks is the round that stopped the frame, and later records are all zero.  Record 0 does not depend on
+ *    max_streaks.  A streak longer than L comes back as consecutive pieces; joining them is left to the caller. */
+enum { LFDMI_STREAK_OK = 0, LFDMI_STREAK_NONE = 1 };
+#define LFDMI_STREAK_MAX_STREAKS 8
+typedef struct {
+    int32_t bin;              /* 1, 2 or 4; default 2: binning is the search's width knob */
+    int32_t length;           /* L in binned cells: 8, 16, 32 or 64; default 32 */
+    int32_t max_streaks;      /* records per frame at most, 1 .. LFDMI_STREAK_MAX_STREAKS; default 4 */
+    int32_t peel_halfwidth;   /* half-width in pixels of the footprint blotted around a found streak, 0 .. 65536; default 8 */
+    float clip;               /* pixels above it in magnitude are not summed (> 0, step 2's range rule); default 0.125 */
+    float threshold;          /* found = snr >= threshold; finite and > 0; default 8 (step 5) */
+} lfdmi_streak_params;
+typedef struct {
+    int32_t status;       /* LFDMI_STREAK_* */
+    int32_t found;
+    int32_t q, s, r0, c0; /* the segment in working coordinates (steps 3, 4) */
+    int32_t n_pix;        /* N: valid pixels on it */
+    float sum, snr;       /* A and its score */
+    int32_t pad;
+    double x1, y1, x2, y2, rho, theta;
+} lfdmi_streak;
+void lfdmi_default_streak_params(lfdmi_streak_params *out);
+/* frames: n frames of h x w, LFDMI_F32 or LFDMI_F32_BE, loc LFDMI_HOST / LFDMI_HOST_PINNED / LFDMI_DEVICE; only read.  sigma: n
+ * float32 (host), > 0; NULL: 0.025 for every frame.  p NULL: the defaults.  out: n * max_streaks records (host), frame i's at
+ * out[i * max_streaks ..]; n_streaks: n counts (host).  LFDMI_ERR_ARG, and nothing runs: parameters out of range (the range
+ * rule among them), a sigma that is not positive, h or w below 2 bin or above 4096 bin (r0 and c0 take 12 bits each of the key
+ * that orders the candidates).  The call keeps no state (its device memory comes from the stream's pool and goes back before
+ * it returns), splits into chunks of frames by the unit limits (staging of host frames, bytes of binned cells), refuses
+ * while calls are in flight, runs on the context's stream and waits for it once per round of each chunk (the host decides
+ * which frames continue). */
+int lfdmi_streak_search(lfdmi_ctx *ctx, const void *frames, int dtype, int n, int h, int w, int loc, const float *sigma,
+                        const lfdmi_streak_params *p, lfdmi_streak *out, int32_t *n_streaks);
+/* the anchors a workgroup of the search kernel owns (rows x columns of the working array); any pointer may be NULL */
+void lfdmi_streak_tile(int32_t *rows, int32_t *cols);
+
 /* ---- stacked cross-sections -------------------------------------------------------------------------------------------------
  * lfdmi_measure_trails needs every 64-position piece of a trail to stand 5 sigma on its own; a trail of the faint-trail search
  * never does.  lfdmi_stack_profiles measures such a trail's cross-section by the Radon idea turned by 90 degrees: the frame is

@@ -55,6 +55,7 @@ SYMBOLS = (
     "lfdmi_default_psf_params", "lfdmi_measure_seeing",
     "lfdmi_default_rounds_params", "lfdmi_detect_rounds",
     "lfdmi_default_preview_params", "lfdmi_frame_previews",
+    "lfdmi_default_streak_params", "lfdmi_streak_search", "lfdmi_streak_tile",
 )
 
 
@@ -543,6 +544,38 @@ def make_preview_params(**params):
     return _make_params(PreviewParamsStruct, "lfdmi_default_preview_params", "preview", params, _preview_mode)
 
 
+class StreakParamsStruct(C.Structure):
+    """lfdmi_streak_params (include/lfdmi.h: short-streak search)."""
+    _fields_ = [("bin", C.c_int32), ("length", C.c_int32), ("max_streaks", C.c_int32), ("peel_halfwidth", C.c_int32),
+                ("clip", C.c_float), ("threshold", C.c_float)]
+
+
+class Streak(C.Structure):
+    """lfdmi_streak: one record per frame and round of lfdmi_streak_search."""
+    _fields_ = [("status", C.c_int32), ("found", C.c_int32), ("q", C.c_int32), ("s", C.c_int32), ("r0", C.c_int32), ("c0", C.c_int32),
+                ("n_pix", C.c_int32), ("sum", C.c_float), ("snr", C.c_float), ("pad", C.c_int32),
+                ("x1", C.c_double), ("y1", C.c_double), ("x2", C.c_double), ("y2", C.c_double), ("rho", C.c_double), ("theta", C.c_double)]
+
+
+STREAK_DTYPE = np.dtype([("status", "<i4"), ("found", "<i4"), ("q", "<i4"), ("s", "<i4"), ("r0", "<i4"), ("c0", "<i4"), ("n_pix", "<i4"),
+                         ("sum", "<f4"), ("snr", "<f4"), ("pad", "<i4"), ("x1", "<f8"), ("y1", "<f8"), ("x2", "<f8"), ("y2", "<f8"),
+                         ("rho", "<f8"), ("theta", "<f8")])
+STREAK_OK, STREAK_NONE = 0, 1
+STREAK_MAX_STREAKS = 8
+
+
+def make_streak_params(**params):
+    """lfdmi_default_streak_params with the given fields replaced (unknown names raise)."""
+    return _make_params(StreakParamsStruct, "lfdmi_default_streak_params", "streak", params)
+
+
+def streak_tile():
+    """(rows, columns) of anchors a workgroup of k_streak_search owns"""
+    r, c = C.c_int32(), C.c_int32()
+    lib().lfdmi_streak_tile(C.byref(r), C.byref(c))
+    return r.value, c.value
+
+
 def make_radon_params(**params):
     """lfdmi_default_radon_params with the given fields replaced (unknown names raise)."""
     return _make_params(RadonParamsStruct, "lfdmi_default_radon_params", "radon", params)
@@ -665,6 +698,12 @@ def lib():
         _lib.lfdmi_default_preview_params.argtypes = [C.c_void_p]
         _lib.lfdmi_frame_previews.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        _lib.lfdmi_default_streak_params.restype = None
+        _lib.lfdmi_default_streak_params.argtypes = [C.c_void_p]
+        _lib.lfdmi_streak_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]
+        _lib.lfdmi_streak_tile.restype = None
+        _lib.lfdmi_streak_tile.argtypes = [C.c_void_p, C.c_void_p]
         _lib.lfdmi_debug_unit_limits.argtypes = [C.c_void_p, C.c_void_p]
         _lib.lfdmi_debug_unit_split.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     return _lib
@@ -1727,6 +1766,20 @@ class Context:
         self._chk(self._lib.lfdmi_frame_previews(self._h, _ptr(frames), code, n, h, w, loc, C.byref(p), _ptr(lim), _ptr(lut), _ptr(out),
                                                  DEVICE if out_device else HOST, _ptr(cells), _ptr(rec)))
         return (out, cells, rec) if want_cells else (out, rec)
+
+    # -- short-streak search (lfdmi_streak_search) -----------------------------------------------------------------------------------
+    def streak_search(self, frames, sigma=None, pinned=False, native_device=False, **params):
+        """The short streaks of every frame (include/lfdmi.h: short-streak search).  frames: what ``find_stars`` takes, only read;
+        sigma: None (0.025), a number or one value per frame; ``params``: the fields of lfdmi_streak_params.  Returns
+        (STREAK_DTYPE records [n, max_streaks], int32 n_streaks [n])."""
+        frames, code, n, h, w, loc = self._frames(frames, pinned, "streak_search", native_device=native_device)
+        p = make_streak_params(**params)
+        sig = _sigma(sigma, n)
+        m = max(1, min(int(p.max_streaks), STREAK_MAX_STREAKS))
+        rec = np.zeros((n, m), STREAK_DTYPE)
+        ns = np.zeros(n, np.int32)
+        self._chk(self._lib.lfdmi_streak_search(self._h, _ptr(frames), code, n, h, w, loc, _ptr(sig), C.byref(p), _ptr(rec), _ptr(ns)))
+        return rec, ns
 
     def pinned_buffer(self, nbytes):
         """Page-locked host memory next to this context's GPU (lfdmi_host_alloc) as a ``PinnedBuffer``."""

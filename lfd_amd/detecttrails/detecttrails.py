@@ -372,6 +372,35 @@ class _PreviewStage:
         self.out.flush()
 
 
+class _StreakStage:
+    """The short-streak search behind detection for ``DetectTrails(streaks=True)`` (include/lfdmi.h: short-streak search): every
+    chunk is searched after its detect call, while its frames are on the device and blotted by remove_stars, and streaks.txt
+    gets one row per found streak.  ``params``: the fields of lfdmi_streak_params; ``sigma``: the frames' sky sigma."""
+
+    def __init__(self, out, params, sigma):
+        from ..streaks import as_params
+        self.out, self.params, self.sigma = out, as_params(params), sigma
+
+    def batch(self, ctx, frames, **where):
+        """the frames where the detect call left them -> [(records [K], n_streaks)] per frame"""
+        rec, ns = ctx.streak_search(frames, sigma=self.sigma, **where, **self.params)
+        return [(rec[j], int(ns[j])) for j in range(len(ns))]
+
+    def one(self, img):
+        """one host frame, blotted by its detection -> (records [K], n_streaks)"""
+        img = _np.ascontiguousarray(img, _np.float32)
+        with use_context(*img.shape) as ctx:
+            return self.batch(ctx, img)[0]
+
+    def rows(self, key, recs, n):
+        from ..streaks import format_row
+        for k in range(n):
+            self.out.write(format_row(key, k, recs[k]) + "\n")
+
+    def flush(self):
+        self.out.flush()
+
+
 class _ShortRecord:
     """a frame's record of ``_RadonStage`` with ``short``: the record it has without (``base``), its short records [K], their
     n_lines and [(stack record, row)] per found short candidate (empty without ``prof_out``)"""
@@ -1012,7 +1041,9 @@ class _Chunk:
     per-frame product gets a slot here, a step in ``_run_group`` and ``_run_frame``, and its row in ``_emit``."""
 
     def __init__(self, n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon=None,
-                 stars=None, masks=None, lc=None, strip=None, sub=None, seeing=None, rounds=None, preview=None):
+                 stars=None, masks=None, lc=None, strip=None, sub=None, seeing=None, rounds=None, preview=None, streak=None):
+        self.streak = streak                          # a ``_StreakStage``; ``streaks[i]``: (records [K], n_streaks) or the exception
+        self.streaks = [None] * n
         self.preview = preview                        # a ``_PreviewStage``; ``previews[i]``: (image, record) or the exception
         self.previews = [None] * n
         self.results, self.errors, self.profiles, self.sky, self.radon, self.stars = results, errors, profiles, sky, radon, stars
@@ -1051,7 +1082,7 @@ def _sub_segments(c, i, detection, res, line):
 def _run_frame(c, i, filter, frame):
     """Frame i on its own, under its own try: ``frame()`` -> (float32 img, cat); sky normalisation if on, detection, and the
     trail measurement of a detected frame."""
-    c.lcs[i] = c.strips[i] = c.subs[i] = c.trails[i] = c.previews[i] = None
+    c.lcs[i] = c.strips[i] = c.subs[i] = c.trails[i] = c.previews[i] = c.streaks[i] = None
     try:
         img, cat = frame()
         c.shapes[i] = tuple(img.shape)
@@ -1112,6 +1143,11 @@ def _run_frame(c, i, filter, frame):
                     c.nulls[i] = c.radon.null_one(img, null_seed(*c.keys[i]), c.rlines[i])
                 except Exception as e:  # noqa: BLE001
                     c.nulls[i] = e
+        if c.streak is not None:                      # the frame as its detection left it
+            try:
+                c.streaks[i] = c.streak.one(img)
+            except Exception as e:  # noqa: BLE001
+                c.streaks[i] = e
         if c.sub is not None:                         # last: it changes the frame (a copy of it here)
             try:
                 todo = _sub_segments(c, i, c.rows[i][0], c.rows[i][1], c.rlines[i])
@@ -1224,6 +1260,13 @@ def _run_group(c, idx, filter, shape, inflight, source, second, detect_kw=None, 
                         except Exception as e:  # noqa: BLE001
                             for j in todo:
                                 c.nulls[idx[j]] = e
+            if c.streak is not None:                  # every frame of the chunk, where the detect call left it
+                try:
+                    for j, item in enumerate(c.streak.batch(ctx, frames, **measure_kw)):
+                        c.streaks[idx[j]] = item
+                except Exception as e:  # noqa: BLE001
+                    for i in idx:
+                        c.streaks[i] = e
             if c.sub is not None:                     # after every other measurement of the chunk: it changes the frames
                 per_frame = {}
                 try:
@@ -1292,6 +1335,10 @@ def _emit(c, i, key, head, shape):
             _log_error(c.errors, key, c.nulls[i], c.debug)
         elif c.nulls[i] is not None:
             c.radon.null_rows(key, line, c.nulls[i])
+    if isinstance(c.streaks[i], Exception):
+        _log_error(c.errors, key, c.streaks[i], c.debug)
+    elif c.streaks[i] is not None:
+        c.streak.rows(key, *c.streaks[i])
     if c.masks is not None:                           # (after the rows above, which it does not touch)
         try:
             shp = c.shapes[i] or tuple(shape)           # (a frame that ran on its own may differ from the chunk's shape)
@@ -1335,7 +1382,7 @@ def _emit(c, i, key, head, shape):
 
 def process_field(results, errors, run, camcol, filter, field, params_bright, params_dim,
                   params_removestars, profiles=None, trail_params=None, sky=None, radon=None, stars=None, masks=None, lc=None,
-                  strip=None, sub=None, seeing=None, rounds=None, preview=None):
+                  strip=None, sub=None, seeing=None, rounds=None, preview=None, streak=None):
     """One frame end to end (reference: detecttrails.py:30-143): locate the frame (or its .bz2),
     read image + header + photoObj, detect, append ``run camcol filter field tai crpix1 crpix2
     crval1 crval2 cd11 cd12 cd21 cd22 x1 y1 x2 y2`` to ``results``; every exception is logged
@@ -1347,7 +1394,7 @@ def process_field(results, errors, run, camcol, filter, field, params_bright, pa
     normalisation, if on), and the frame's stars.txt row is written.  ``masks``: a ``_MaskStage``; a results row, and every found
     faint line of ``radon`` with lines, gets its masks.txt row."""
     c = _Chunk(1, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon, stars, masks, lc, strip, sub,
-               seeing, rounds, preview)
+               seeing, rounds, preview, streak)
     c.keys[0] = (run, camcol, filter, field)
     head = None
     try:
@@ -1392,7 +1439,8 @@ def process_fields_batched(results, errors, ids, params_bright, params_dim, para
 
 
 def process_loaded(results, errors, loaded, params_bright, params_dim, params_removestars, profiles=None, trail_params=None, sky=None,
-                   radon=None, stars=None, masks=None, lc=None, strip=None, sub=None, seeing=None, rounds=None, preview=None):
+                   radon=None, stars=None, masks=None, lc=None, strip=None, sub=None, seeing=None, rounds=None, preview=None,
+                   streak=None):
     """process_fields_batched for a chunk the loader has read (``loader.Loaded``): the frames that sit in pinned memory go to
     the GPU as contiguous same-filter slices of that memory with the matching rows of the padded catalogue arrays (no copy
     of a frame on the host, no per-frame Python), the others take the per-frame path; rows and errors entries come out in
@@ -1408,7 +1456,7 @@ def process_loaded(results, errors, loaded, params_bright, params_dim, params_re
     t_in = time.perf_counter()
     n = len(loaded.keys)
     c = _Chunk(n, results, errors, params_bright, params_dim, params_removestars, profiles, trail_params, sky, radon, stars, masks, lc, strip, sub,
-               seeing, rounds, preview)
+               seeing, rounds, preview, streak)
     c.keys = list(loaded.keys)
     by_slot = {}
     for i in range(n):
@@ -1488,6 +1536,12 @@ class DetectTrails:
     ell``.  With ``defocus=True`` every fit behind defocus.txt and radon_defocus.txt gets its frame's ``seeing_arcsec`` as
     ``fit_defocus``'s ``seeing`` (NaN, a free fit, for a frame with too few stars).  Rank files, resume and ``Jobs`` treat
     seeing.txt like stars.txt; a run without ``seeing`` stays byte for byte what it is.
+    ``streaks=True`` (default False: nothing differs and no file appears): every chunk is searched for short streaks after its
+    detect call, while its frames are on the device and blotted by remove_stars (include/lfdmi.h: short-streak search;
+    ``streaks_params``: dict of bin, length, max_streaks, peel_halfwidth, clip, threshold, checked here), and ``streaks_file``
+    (default ``<savepath>/streaks.txt``) gets one row per found streak: ``run camcol filter field streak q s r0 c0 n_pix snr x1 y1
+    x2 y2``.  Rank files, resume and ``Jobs`` treat streaks.txt like previews.txt.
+
     ``previews="detections"`` or ``"all"`` (default None: nothing differs and no file appears): every chunk is turned into small
     8-bit images on the device (include/lfdmi.h: frame previews; ``preview_params``: dict of bin, mode, lo_ppm, hi_ppm, limits,
     kind, softening, lut, color, thick) before detection blots it, after the normalisation when that is on.  The images of the
@@ -1611,6 +1665,10 @@ class DetectTrails:
         self.seeing_file = kwargs.get("seeing_file", os.path.join(save, "seeing.txt"))
         from ..psf import as_params as psf_as_params
         self.seeing_params = psf_as_params(kwargs.get("seeing_params"))  # (likewise)
+        self.streaks = bool(kwargs.get("streaks", False))
+        self.streaks_file = kwargs.get("streaks_file", os.path.join(save, "streaks.txt"))
+        from ..streaks import as_params as streak_as_params
+        self.streaks_params = streak_as_params(kwargs.get("streaks_params"))   # (a bad value stops here, not in the first chunk)
         self.previews = kwargs.get("previews")
         if self.previews not in (None, "detections", "all"):
             raise ValueError("previews must be None, 'detections' or 'all'")
@@ -1898,8 +1956,10 @@ class DetectTrails:
                 (open(self.lightcurve_summary_file + suffix, "a") if self.light_curves else contextlib.nullcontext()) as lcsum_out, \
                 _both(open(self.strips_file + suffix, "a") if self.trail_strips else contextlib.nullcontext(),
                       _both(open(self.subtracted_file + suffix, "a") if self.subtract_trails else contextlib.nullcontext(),
-                            open(self.previews_file + suffix, "a") if self.previews is not None
-                            else contextlib.nullcontext())) as (strips_out, (sub_out, previews_out)):
+                            _both(open(self.previews_file + suffix, "a") if self.previews is not None
+                                  else contextlib.nullcontext(),
+                                  open(self.streaks_file + suffix, "a") if self.streaks
+                                  else contextlib.nullcontext()))) as (strips_out, (sub_out, (previews_out, streaks_out))):
             seeing = None
             if self.seeing:
                 sigma = _native.make_sky_params(**self.sky_params).target_sigma if self.normalize else 0.025
@@ -1949,6 +2009,10 @@ class DetectTrails:
             preview = None
             if self.previews is not None:
                 preview = prof_kw["preview"] = _PreviewStage(previews_out, self.previews, self.preview_params, self.preview_dir)
+            streak = None
+            if self.streaks:
+                sigma = _native.make_sky_params(**self.sky_params).target_sigma if self.normalize else 0.025
+                streak = prof_kw["streak"] = _StreakStage(streaks_out, self.streaks_params, sigma)
             if fresh:
                 progress.write(header + "\n")
                 progress.flush()
@@ -1978,6 +2042,8 @@ class DetectTrails:
                     rounds.flush()
                 if preview is not None:
                     preview.flush()
+                if streak is not None:
+                    streak.flush()
                 progress.write("".join("%s %s %s %s\n" % tuple(k) for k in done_keys))
                 progress.flush()
 

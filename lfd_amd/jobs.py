@@ -89,7 +89,8 @@ class Jobs:
             ([probe.lightcurves_file, probe.lightcurve_summary_file] if probe.light_curves else []) + \
             ([probe.strips_file] if probe.trail_strips else []) + ([probe.subtracted_file] if probe.subtract_trails else []) + \
             ([probe.radon_null_file, probe.radon_fap_file] if probe.radon_null is not None else []) + \
-            ([probe.radon_null_rounds_file] if probe.radon_null_rounds else []) + ([probe.trails_file] if probe.rounds else [])
+            ([probe.radon_null_rounds_file] if probe.radon_null_rounds else []) + ([probe.trails_file] if probe.rounds else []) + \
+            ([probe.streaks_file] if probe.streaks else [])
         if not resume:
             for path in joined:                           # the joined files are rewritten by this launch
                 if self.n > 1 and os.path.exists(path):

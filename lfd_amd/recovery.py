@@ -1,7 +1,7 @@
 """Injection and recovery: add model trails of known line and brightness to frames, detect, and count what comes back -- the
 detector's efficiency as a function of the trail's peak (include/lfdmi.h: trail injection).
 
-    python -m lfd_amd.recovery --synth K0:N --peaks 0.05,0.1,0.2,5 --out DIR [--detector radon | radon-short] [--length-frac F] [--null K [--null-scheme S]]
+    python -m lfd_amd.recovery --synth K0:N --peaks 0.05,0.1,0.2,5 --out DIR [--detector radon | radon-short | streak] [--length-frac F] [--null K [--null-scheme S]]
 
 The plan (``draw_trails``), the matching (``match``) and the rows use integer RNG draws and IEEE + - * / sqrt only -- cos and sin
 come from ``cos_sin`` below, a fixed sequence of multiplications and additions -- so every machine draws the same plan and
@@ -183,6 +183,52 @@ def make_rows(records, trails, params_bright, params_dim, shape, k=K_MATCH, meas
     return rows
 
 
+def match_streaks(records, n_streaks, trails, shape, reach):
+    """Is one of the found streaks of a trail's frame the injected trail?  records: STREAK_DTYPE [n, K] and n_streaks [n] of
+    ``streaks.search_frames``; trails: PLAN_DTYPE records; reach: L b / 2 px.  A found streak matches when both its ends lie
+    within ``reach`` of the injected segment's line and its midpoint lies inside the injected extent (the part of [t0, t1] on
+    the frame).  Returns (matched bool, d_rho, d_theta, length, found): of the first matching streak in peel order, otherwise
+    of the frame's first found streak; d_rho is the distance of the streak's midpoint from the injected line, d_theta the
+    difference of the normals' angles folded into [-pi/2, pi/2]; NaN where nothing was found."""
+    n = len(trails)
+    matched = np.zeros(n, bool)
+    found = np.zeros(n, np.int64)
+    d_rho = np.full(n, np.nan)
+    d_theta = np.full(n, np.nan)
+    length = np.zeros(n)
+    for i, tr in enumerate(trails):
+        rho, theta = float(tr["rho"]), float(tr["theta"])
+        ta, tb = extent(rho, theta, float(tr["t0"]), float(tr["t1"]), shape)
+        length[i] = max(0.0, tb - ta)
+        f = int(tr["frame"])
+        found[i] = int(n_streaks[f])
+        c, s = math.cos(theta), math.sin(theta)
+        for k in range(found[i]):
+            rec = records[f][k]
+            ends = [abs(float(x) * c + float(y) * s - rho) for x, y in ((rec["x1"], rec["y1"]), (rec["x2"], rec["y2"]))]
+            mx, my = 0.5 * (float(rec["x1"]) + float(rec["x2"])), 0.5 * (float(rec["y1"]) + float(rec["y2"]))
+            ok = ta <= tb and max(ends) <= reach and ta <= -mx * s + my * c <= tb
+            if ok or k == 0:
+                d_rho[i] = mx * c + my * s - rho
+                d_theta[i] = (float(rec["theta"]) - theta + _HALF_PI) % math.pi - _HALF_PI
+            if ok:
+                matched[i] = True
+                break
+    return matched, d_rho, d_theta, length, found
+
+
+def streak_rows(records, n_streaks, trails, shape, reach):
+    """One ROW_DTYPE row per injected trail from its frame's streak records (``match_streaks``); found: the frame's n_streaks"""
+    matched, d_rho, d_theta, length, found = match_streaks(records, n_streaks, trails, shape, reach)
+    rows = np.zeros(len(trails), ROW_DTYPE)
+    for key in ("frame", "peak", "rho", "theta"):
+        rows[key] = trails[key]
+    rows["length"], rows["found"], rows["matched"] = length, found, matched
+    rows["d_rho"], rows["d_theta"] = d_rho, d_theta
+    rows["fwhm"] = np.nan
+    return rows
+
+
 def radon_records(lines):
     """RADON_DTYPE records -> RESULT_DTYPE records ``match`` can judge: found 1 (so that the cell is params_bright's
     houghMethod) where the search found a line, with that line's rho and theta"""
@@ -193,7 +239,8 @@ def radon_records(lines):
 
 
 def run(ctx, frames, cats, rs, trails, tables, table_step, params_bright=None, params_dim=None, subsample=4, profiles=False,
-        k=K_MATCH, detector="hough", radon_params=None, sigma=None, short_params=None, null=0, null_scheme="scramble"):
+        k=K_MATCH, detector="hough", radon_params=None, sigma=None, short_params=None, null=0, null_scheme="scramble",
+        streak_params=None):
     """Copy ``frames`` ((n, h, w) float32 numpy or torch CUDA), inject the plan ``trails`` (tables of peak 1: see
     ``inject.normalise_peak``), run ``detect_batch`` and match: ROW_DTYPE rows, one per trail.  cats: the frames' catalogues
     (a list of dicts, a packed dict or None) and rs their remove_stars parameters; profiles=True also runs ``measure_trails``
@@ -204,12 +251,14 @@ def run(ctx, frames, cats, rs, trails, tables, table_step, params_bright=None, p
     radon detectors): the frames' null peaks of that search (include/lfdmi.h: null peaks; frame f has seed f) are measured on
     the same frames, and the call returns (rows, fap): float64 [n trails], ``radon.false_alarm`` of each trail's frame's line
     among its frame's K null peaks; ``null_scheme``: how the null frames are made ("scramble", "signflip", "rowshift",
-    "colshift": steps 21 - 22 of that definition)."""
+    "colshift": steps 21 - 22 of that definition).  detector="streak": the stars are removed and the short-streak search
+    (include/lfdmi.h: short-streak search; ``streak_params``, ``sigma``) runs; a trail is matched by ``match_streaks`` with
+    reach L b / 2."""
     if null_scheme not in _native.RADON_NULL_SCHEMES:
         raise ValueError("null_scheme: one of %s" % ", ".join(_native.RADON_NULL_SCHEMES))
-    if detector not in ("hough", "radon", "radon-short"):
-        raise ValueError("detector: 'hough', 'radon' or 'radon-short'")
-    if null and detector == "hough":
+    if detector not in ("hough", "radon", "radon-short", "streak"):
+        raise ValueError("detector: 'hough', 'radon', 'radon-short' or 'streak'")
+    if null and detector in ("hough", "streak"):
         raise ValueError("null: the null peaks belong to the radon detectors")
     from .catalogs import pack_catalogs
     from .detecttrails import default_params
@@ -220,6 +269,14 @@ def run(ctx, frames, cats, rs, trails, tables, table_step, params_bright=None, p
     n, h, w = work.shape
     packed = pack_catalogs(list(cats)) if isinstance(cats, (list, tuple)) else cats
     ctx.inject_trails(work, to_inject(trails), np.asarray(tables, np.float32), table_step, subsample=subsample)
+    if detector == "streak":
+        from . import streaks as _streaks
+        if packed is not None:
+            ctx.remove_stars(work, packed, rs)
+        sp = _streaks.as_params(streak_params)
+        full = dict(_streaks.default_params(), **sp)
+        recs, ns = _streaks.search_frames(ctx, work, sigma=sigma, **sp)
+        return streak_rows(recs, ns, trails, (h, w), full["length"] * full["bin"] / 2.0)
     if detector in ("radon", "radon-short"):
         from . import radon as _radon
         if packed is not None:
@@ -322,9 +379,11 @@ def main(argv=None):
     ap.add_argument("--sigma", type=float, default=2.0, help="Gaussian cross-section sigma in px")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--profiles", action="store_true", help="also measure the recovered trails' fwhm")
-    ap.add_argument("--detector", choices=("hough", "radon", "radon-short"), default="hough",
+    ap.add_argument("--detector", choices=("hough", "radon", "radon-short", "streak"), default="hough",
                     help="hough: the detector (default); radon: the faint-trail search in its place; radon-short: its "
-                         "short-trail search, matched by the candidate's parent line")
+                         "short-trail search, matched by the candidate's parent line; streak: the short-streak search, "
+                         "matched by both ends within L b / 2 px of the injected line and the midpoint inside its extent")
+    ap.add_argument("--streak-length", type=int, default=None, help="--detector streak: lfdmi_streak_params.length")
     ap.add_argument("--bin", type=int, default=None, help="--detector radon / radon-short: lfdmi_radon_params.bin")
     ap.add_argument("--length-frac", type=float, default=1.0,
                     help="inject every trail over this fraction of its crossing, at a random place along it (default 1: the whole crossing)")
@@ -335,7 +394,7 @@ def main(argv=None):
                     help="--null K: how the null frames are made (default scramble; signflip, rowshift and colshift leave every "
                          "pixel in its place, row or column)")
     a = ap.parse_args(argv)
-    if a.null and a.detector == "hough":
+    if a.null and a.detector in ("hough", "streak"):
         ap.error("--null needs --detector radon or radon-short")
     k0, n = (int(v) for v in a.synth.split(":"))
     peaks = [float(v) for v in a.peaks.split(",")]
@@ -350,7 +409,8 @@ def main(argv=None):
     plan = shorten(draw_trails(len(keep), frames.shape[1:], a.seed, peaks), frames.shape[1:], a.length_frac, a.seed)
     with _native.Context(0, frames.shape[1], frames.shape[2], 16) as ctx:
         rows = run(ctx, frames, cats, rs, plan, _inject.normalise_peak(table), step, pb, pd, profiles=a.profiles,
-                   detector=a.detector, radon_params={"bin": a.bin} if a.bin else None, null=a.null, null_scheme=a.null_scheme)
+                   detector=a.detector, radon_params={"bin": a.bin} if a.bin else None, null=a.null, null_scheme=a.null_scheme,
+                   streak_params=dict(({"bin": a.bin} if a.bin else {}), **({"length": a.streak_length} if a.streak_length else {})))
     rows, fap = rows if a.null else (rows, None)
     os.makedirs(a.out, exist_ok=True)
     write_recovery(os.path.join(a.out, "recovery.txt"), rows)
